@@ -11,8 +11,13 @@ N > 1: one simulated client per GPU (weak scaling, no data-path collective insid
 local epoch and are followed, inside the timed region, by the round's FedAvg exchange — one RCCL all-reduce of the
 flat model state over xGMI (reference server.py:25-34) — so ms_total is the FedAvg round time at N clients.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant MFMA kernel, timed live
-with HIP events on its stream) and `cpu_baseline` (the CPU oracle timed on this host's cores on a bounded sample).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the K steps and
+prints the line: `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` and the timed region's own fields.
+--full adds every other leg, each after the timed region: `roofline` (dominant MFMA kernel, timed live with HIP events on
+its stream), `parity` (whole-network error on a committed fixture), `cpu_baseline` (the CPU oracle timed on this host's
+cores on a bounded sample), `bf16_build`, `end_to_end`, `concurrent_clients`, `fedavg`, `fedavg_round` and the host
+enqueue probe; --no-profile / --no-cpu-baseline / --no-bf16-build switch parts of it off again.
+--dump-outputs DIR writes what the last timed step computed (see dump_outputs) as DIR/<name>.npy.
 """
 import argparse
 import ctypes as C
@@ -382,6 +387,34 @@ def parity_leg(dev):
     return out
 
 
+DUMP_BUDGET_FLOATS = 16 * 2 ** 20       # --dump-outputs: at most 64 MB of float32 in all
+DUMP_WHOLE_FLOATS = 2 ** 20             # arrays up to this size are written whole, larger ones as a fixed seeded sample
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: write [(name, tensor)] as out_dir/<name>.npy in float32 — the arrays a caller of the timed path receives after its
+    last step (the loss it returns, the updated backbone parameters and BatchNorm buffers, the updated head).  Arrays of at most
+    DUMP_WHOLE_FLOATS elements are written whole; the rest of DUMP_BUDGET_FLOATS is shared equally by the larger ones, each written as the
+    elements at sorted indices drawn by a generator seeded from its name (the same sample in every run with the same arguments)."""
+    import zlib
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    small = [(n, t) for n, t in arrays if t.numel() <= DUMP_WHOLE_FLOATS]
+    large = [(n, t) for n, t in arrays if t.numel() > DUMP_WHOLE_FLOATS]
+    share = (DUMP_BUDGET_FLOATS - sum(t.numel() for _, t in small)) // max(1, len(large))
+    total = 0
+    for name, t in small + large:
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_WHOLE_FLOATS:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(0, flat.numel(), (min(share, flat.numel()),), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        a = flat.float().cpu().numpy().astype(np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+    print("bench.py: wrote %d arrays (%.1f MB) to %s" % (len(arrays), total / 2 ** 20, out_dir), file=sys.stderr, flush=True)
+
+
 ROUND_LOCAL_STEPS = 8     # local steps per client in the `fedavg_round` leg (the reference: local_epoch x len(loader), client.py:537)
 
 
@@ -492,14 +525,21 @@ def main():
     ap.add_argument("--lib", default="fp16", choices=["fp16", "bf16"],
                     help="storage type of activations / gradients / MFMA operands: fp16 = libfedfr_hip.so (product default), bf16 = libfedfr_hip_bf16.so (`make bf16`)")
     ap.add_argument("--secondary", action="store_true",
-                    help="timed region + parity leg only (what the default run's `bf16_build` child process executes)")
+                    help="timed region + parity leg only (what the --full run's `bf16_build` child process executes)")
     ap.add_argument("--no-bf16-build", action="store_true", help="skip the secondary bf16-build line (a child process after the legs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, run every other leg too (roofline, parity, CPU baseline, bf16 build, end to end, concurrent "
+                         "clients, FedAvg, FedAvg round, host enqueue probe); a plain run prints the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
     args = ap.parse_args()
     secondary = args.secondary
     if secondary:
         args.no_profile = args.no_cpu_baseline = args.no_bf16_build = True
+    elif not args.full:
+        args.no_profile = args.no_cpu_baseline = args.no_bf16_build = True      # a plain run: the timed region and the JSON line only
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -585,10 +625,9 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        loss = tr.step(imgs[i % nbuf], labs[i % nbuf])
+        step_out = tr.step(imgs[i % nbuf], labs[i % nbuf])
     t_enqueue = time.perf_counter() - t0         # host time to ENQUEUE the K steps (no sync inside): well below dt = the GPU is never waiting for the host
-    if isinstance(loss, tuple):
-        loss = loss[0]
+    loss = step_out[0] if isinstance(step_out, tuple) else step_out
     t_local = None
     if use_dist:
         tr.finish()
@@ -603,10 +642,20 @@ def main():
         dist.all_reduce(tt, dist.ReduceOp.MAX)
         dt, t_local = float(tt[0]), float(tt[1])
     final_loss = float(loss)
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller (the device is synchronised: barrier() above), before any leg steps the trainer again
+        parts = step_out if isinstance(step_out, tuple) else (step_out,)
+        arrays = [("loss" if k == 0 else "loss_part%d" % k, t) for k, t in enumerate(parts) if torch.is_tensor(t)]
+        arrays += [("backbone_params", model._flat_params), ("backbone_buffers", model._flat_bufs)]
+        if args.head == "pfc-sharded":
+            arrays += [("head_weight", pfc.weight)] + [("bce_" + n.replace(".", "_"), p) for n, p in bce.named_parameters()]
+        else:
+            arrays.append(("head_weight", tr.fc))
+        dump_outputs(args.dump_outputs, arrays)
     # host cost of one step: enqueue time of a step issued into an EMPTY queue (the timed loop's own enqueue time includes the back-pressure of
     # a full queue).  Far below ms_per_step = the GPU never waits for the host.
     host_ms = []
-    if not use_dist:
+    if not use_dist and (args.full or secondary):
         for i in range(5):
             torch.cuda.synchronize()
             th = time.perf_counter()

@@ -103,43 +103,45 @@ def test_fedavg_all_reduce_two_ranks_gloo(tmp_path, arch, port):
 
 def test_checkpoint_interchange_with_reference():
     """checkpoints in the reference's `torch.save(backbone.state_dict())` format (client.py:484-495, server.py:148)
-    load into this package's backbone and vice versa, key for key and bit for bit (runs where /root/reference is present)."""
-    import os
-    import sys
+    load into this package's backbone and vice versa, key for key and bit for bit.  The reference's format is the inventory
+    tests/golden/ckpt_r18.npz captured from its iresnet18 (tools/make_golden.py): key order, shapes, dtypes and module versions."""
     import tempfile
-    if not os.path.isdir("/root/reference/backbones"):
-        pytest.skip("reference checkout not present on this machine")
-    sys.path.insert(0, "/root/reference")
-    try:
-        import importlib
-        ref_backbones = importlib.import_module("backbones")
-        if not hasattr(ref_backbones, "iresnet18") or ref_backbones.__file__.startswith(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))):
-            pytest.skip("reference backbones shadowed")
-    finally:
-        sys.path.remove("/root/reference")
+    from collections import OrderedDict
+    from conftest import load_golden
     from fedfr_amd import backbones as my_backbones
-    torch.manual_seed(1)
-    ref = ref_backbones.iresnet18(False, dropout=0, fp16=False)
-    for m in ref.modules():                                     # non-trivial BN buffers
-        if isinstance(m, (torch.nn.BatchNorm2d, torch.nn.BatchNorm1d)):
-            m.running_mean.normal_()
-            m.running_var.uniform_(0.5, 2.0)
-            m.num_batches_tracked.fill_(7)
+    g = load_golden("ckpt_r18")
+    dims, shapes = list(g["dims"]), []
+    for r in g["ranks"]:
+        shapes.append(tuple(int(d) for d in dims[:r]))
+        dims = dims[r:]
+    assert not dims
+    inventory = [(str(k), s, getattr(torch, str(d).split(".")[-1])) for k, s, d in zip(g["keys"], shapes, g["dtypes"])]
+    gen = torch.Generator().manual_seed(1)
+    sd_ref = OrderedDict()
+    for k, s, dt in inventory:                                  # non-trivial values, BN buffers included
+        if dt == torch.int64:
+            sd_ref[k] = torch.full(s, 7, dtype=dt)
+        elif k.endswith("running_var"):
+            sd_ref[k] = torch.rand(s, generator=gen) * 1.5 + 0.5
+        else:
+            sd_ref[k] = torch.randn(s, generator=gen)
+    sd_ref._metadata = OrderedDict((str(p), {"version": int(v)} if v >= 0 else {}) for p, v in zip(g["meta_prefixes"], g["meta_versions"]))
     with tempfile.TemporaryDirectory() as td:
         p1, p2 = os.path.join(td, "ref.pth"), os.path.join(td, "mine.pth")
-        torch.save(ref.state_dict(), p1)
+        torch.save(sd_ref, p1)
         mine = my_backbones.iresnet18(False, dropout=0, fp16=True)
         missing = mine.load_state_dict(torch.load(p1))
         assert not missing.missing_keys and not missing.unexpected_keys
-        sd_ref, sd_mine = ref.state_dict(), mine.state_dict()
+        sd_mine = mine.state_dict()
         assert list(sd_ref.keys()) == list(sd_mine.keys())
         for k in sd_ref:
             assert sd_ref[k].shape == sd_mine[k].shape and sd_ref[k].dtype == sd_mine[k].dtype, k
             assert torch.equal(sd_ref[k], sd_mine[k]), k
         torch.save(mine.state_dict(), p2)
-        ref2 = ref_backbones.iresnet18(False, dropout=0, fp16=False)
-        ref2.load_state_dict(torch.load(p2))                    # strict
-        for k, v in ref2.state_dict().items():
+        back = torch.load(p2)
+        # what the reference's strict load_state_dict requires of it: exactly its keys, in its order, with its shapes and dtypes
+        assert [(k, tuple(v.shape), v.dtype) for k, v in back.items()] == inventory
+        for k, v in back.items():
             assert torch.equal(v, sd_ref[k]), k
 
 
@@ -274,6 +276,31 @@ def test_bench_self_launch_starts_the_ranks_before_any_gpu_call(monkeypatch, cap
     capsys.readouterr()
     assert bench.self_launch(["--gpus=2"]) == 124
     assert capsys.readouterr().out.strip() == ""
+
+
+def test_bench_dump_outputs_is_float32_bounded_and_repeatable(tmp_path):
+    """`bench.py --dump-outputs DIR`: every array as DIR/<name>.npy in float32, small arrays whole, large ones as the same seeded sample in every
+    run, 64 MB in all."""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(3)
+    arrays = [("loss", torch.tensor(2.5)), ("head", torch.randn(1000, 512, generator=g)), ("params", torch.randn(12 * 2 ** 20, generator=g)),
+              ("bufs", torch.randn(10 * 2 ** 20, generator=g).double()), ("empty", torch.zeros(0))]
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    total = 0
+    for name, t in arrays:
+        a, b = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert a.dtype == np.float32 and np.array_equal(a, b), name
+        total += a.nbytes
+        if t.numel() <= bench.DUMP_WHOLE_FLOATS:
+            assert np.array_equal(a, t.float().reshape(-1).numpy()), name
+        else:
+            assert 0 < a.size < t.numel() and np.isin(a, t.float().numpy()).all(), name
+    assert total <= 64 * 2 ** 20
 
 
 def test_flat_state_dict_lazy_views_behave_like_a_dict():

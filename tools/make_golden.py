@@ -730,8 +730,24 @@ def gen_freeze_bn():
     save("freeze_bn_r18", **out)
 
 
+def gen_checkpoint():
+    """The inventory of the reference's checkpoint format (`torch.save(backbone.state_dict())`, client.py:484-495, server.py:148) for
+    iresnet18: key order, shape and dtype of every entry and the module versions torch.save stores beside them (state_dict._metadata).
+    tests/test_host_cpu.py rebuilds such a checkpoint from it and checks that it loads into this package's backbone and back."""
+    model = backbones.iresnet18(False, dropout=0, fp16=False)
+    sd = model.state_dict()
+    meta = sd._metadata
+    save("ckpt_r18", keys=np.array(list(sd.keys())), dtypes=np.array([str(v.dtype) for v in sd.values()]),
+         ranks=np.array([v.dim() for v in sd.values()], dtype=np.int64),
+         dims=np.array([d for v in sd.values() for d in v.shape], dtype=np.int64),
+         meta_prefixes=np.array(list(meta.keys())), meta_versions=np.array([meta[k].get("version", -1) for k in meta], dtype=np.int64))
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["block", "r50", "r100", "heads", "bce", "sgd", "fedavg", "pfc", "client", "public", "mining", "roc", "sphnet", "sphnet64", "freeze_bn"]
+    which = sys.argv[1:] or ["block", "r50", "r100", "heads", "bce", "sgd", "fedavg", "pfc", "client", "public", "mining", "roc", "sphnet", "sphnet64", "freeze_bn",
+                             "checkpoint"]
+    if "checkpoint" in which:
+        gen_checkpoint()
     if "freeze_bn" in which:
         gen_freeze_bn()
     if "block" in which:
