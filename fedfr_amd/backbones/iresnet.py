@@ -602,11 +602,11 @@ class IResNet(nn.Module):
         plan = self._plan(x.shape[0])
         if training or self._shadow_dirty:
             self.refresh_shadows(True)
-        feats = torch.empty(x.shape[0], self.num_features, dtype=torch.float32, device=self.device)
         mode = (2 if self._bn_frozen else 1) if training else 0
         if self.validation_fp32:
             if mode == 2 or (training and self.dropout_p > 0):
                 raise NotImplementedError("fedfr_amd: the fp32 validation path covers train / eval forward + backward with dropout 0")
+            feats = torch.empty(x.shape[0], self.num_features, dtype=torch.float32, device=self.device)
             arena, ws = self._f32_buffers(plan)
             _C.call("fedfr_net_f32_forward", plan.handle, x.data_ptr(), self._flat_params.data_ptr(), self._flat_bufs.data_ptr(),
                     arena.data_ptr(), ws.data_ptr(), feats.data_ptr(), mode, _C.stream())
@@ -614,11 +614,18 @@ class IResNet(nn.Module):
                 self._flat_nbt += 1
             self._fwd_generation += 1
             return feats
+        feats = self._enqueue_forward(plan, x, mode)
+        if mode == 1:                           # frozen BatchNorms track nothing (num_batches_tracked included)
+            self._flat_nbt += 1
+        return feats
+
+    def _enqueue_forward(self, plan, x, mode: int) -> torch.Tensor:
+        """``fedfr_net_forward`` of ``x`` on ``plan`` (``mode``: see ``_fwd_mode``) into a new [B, num_features] tensor — the forward pass of
+        ``_run_forward`` and of the fused trainers.  Advances ``_fwd_generation``; num_batches_tracked is the caller's to count."""
+        feats = torch.empty(x.shape[0], self.num_features, dtype=torch.float32, device=self.device)
         self._pre_forward(plan, mode)
         _C.call("fedfr_net_forward", plan.handle, x.data_ptr(), self._flat_params.data_ptr(), self._flat_bufs.data_ptr(),
                 self._shadow.data_ptr(), plan.act.data_ptr(), plan.ws.data_ptr(), feats.data_ptr(), mode, _C.stream())
-        if mode == 1:                           # frozen BatchNorms track nothing (num_batches_tracked included)
-            self._flat_nbt += 1
         self._fwd_generation += 1
         return feats
 

@@ -8,7 +8,10 @@ The hot loop (reference client.py:536-551: zero_grad â†’ fwd â†’ margin â†’ CE â
 """
 from __future__ import annotations
 
+import ctypes
 import logging
+import os
+import threading
 from collections import OrderedDict
 from typing import Iterable, Optional, Tuple
 
@@ -177,44 +180,30 @@ class Sequential_model(nn.Module):
 # fused train step
 # ------------------------------------------------------------------------------------------------
 _AUX_STREAMS = {}      # device index -> the one auxiliary stream every trainer on that device shares (created once, lives with the process)
-_AUX_LOCK = __import__("threading").Lock()
+_AUX_LOCK = threading.Lock()
 
 
 def _make_aux_stream(device, slot: int = 0):
     """Second HIP stream of the dual-stream backward (None with FEDFR_DUAL_STREAM=0): created at the LOWEST priority the device offers
     (through the C ABI: torch clamps stream priorities to [-1, 0], HIP has +1), so that workgroups of the critical path on the caller's
-    stream are dispatched first whenever both streams have work.  FEDFR_AUX_PRIORITY=0 keeps a default-priority torch stream.
+    stream are dispatched first whenever both streams have work.
     ONE stream per (device, slot) for the life of the process: trainers are re-created every FL round for every client (the reference
     re-creates its optimiser the same way), a stream per trainer would leak a HIP stream each time.  ``slot`` > 0: further streams
     for clients that train CONCURRENTLY on one device (one slot per concurrent client)."""
-    import os
     if os.environ.get("FEDFR_DUAL_STREAM", "1") == "0":
         return None
     device = torch.device(device)
     idx = device.index if device.index is not None else torch.cuda.current_device()
-    with _AUX_LOCK:
-        return _aux_stream_locked(idx, int(slot))
-
-
-def _aux_stream_locked(idx, slot):
-    import os
+    slot = int(slot)
     key = idx if slot == 0 else (idx, slot)
-    s = _AUX_STREAMS.get(key)
-    if s is None:
-        if os.environ.get("FEDFR_AUX_PRIORITY", "1") != "0":
-            import ctypes
+    with _AUX_LOCK:
+        s = _AUX_STREAMS.get(key)
+        if s is None:
             h = ctypes.c_void_p()
             with torch.cuda.device(idx):
                 _C.call("fedfr_stream_create_low_priority", ctypes.byref(h))
-            s = torch.cuda.ExternalStream(h.value, device=torch.device("cuda", idx))
-        else:
-            s = torch.cuda.Stream(device=torch.device("cuda", idx))
-        _AUX_STREAMS[key] = s
+            s = _AUX_STREAMS[key] = torch.cuda.ExternalStream(h.value, device=torch.device("cuda", idx))
     return s
-
-
-_HEAD_OFF_PATH = __import__("os").environ.get("FEDFR_HEAD_OFF_PATH", "1") != "0"
-_HEAD_SPLITK = __import__("os").environ.get("FEDFR_HEAD_SPLITK", "1") != "0"
 
 
 def _split_for(k: int) -> int:
@@ -275,10 +264,126 @@ class _LossScaleGuard:
         return hit
 
 
-class FusedTrainer(_LossScaleGuard):
-    """One optimiser lifetime (= one FL round for one client: the reference re-creates SGD every round, F8).
+class _BackboneTrainer(_LossScaleGuard):
+    """The backbone half of every fused train step: ``fedfr_net_forward``, one ``fedfr_net_backward2*`` call from d(loss)/d(features)
+    (weight-gradient GEMMs on the aux stream), the flat SGD update of the backbone and the rebuild of its dgrad-layout weight copies.
+    One optimiser lifetime (= one FL round for one client: the reference re-creates SGD every round, F8)."""
 
-    step(imgs, labels) == the body of the reference hot loop (client.py:537-550) for the Sequential model:
+    def __init__(self, backbone: "backbones.IResNet", lr: float, momentum: float, weight_decay: float, aux_slot: int):
+        bb = self.bb = backbone
+        self.lr, self.mu, self.wd = float(lr), float(momentum), float(weight_decay)
+        bb._ensure_device_state()
+        bb.train()
+        bb.require_all_trainable(type(self).__name__)
+        self.n_train = bb.trainable_count()
+        self.mom = torch.empty(self.n_train, dtype=f32, device=bb.device)
+        self.first = True
+        # weight-gradient GEMMs run on a second HIP stream (fedfr_net_backward2) unless FEDFR_DUAL_STREAM=0
+        self.aux_stream = _make_aux_stream(bb.device, aux_slot)
+        self._shadows_pending = None
+        if self.aux_stream is not None:       # the shared aux stream may still carry the previous trainer's shadow rebuild of this backbone
+            torch.cuda.current_stream().wait_stream(self.aux_stream)
+        bb.refresh_shadows(True)
+        # SGD folded into the backward pass (fedfr_net_backward2_sgd*) unless FEDFR_FUSE_SGD=0
+        self.fuse_sgd = os.environ.get("FEDFR_FUSE_SGD", "1") != "0"
+        self._sgd_done_from = None          # the last backward pass updated [done_from, n_train) itself (None: nothing)
+        self._grads_scaled = False          # fp16-storage library: the rest of the gradient buffer still carries the loss scale ...
+        self._scale_used = 1.0              # ... namely this one (another trainer's poll may lower the device's scale before the update)
+        self._init_loss_scale(bb.device)
+
+    def set_lr(self, lr: float):
+        self.lr = float(lr)
+
+    @property
+    def _sgd_overflow(self) -> Optional[torch.Tensor]:
+        """the overflow word every update of the fp16-storage library is guarded by (``ops.sgd_step``); None for the bf16 library"""
+        return self._overflow if self.guarded else None
+
+    def _wait_shadows(self):
+        if self._shadows_pending is not None:
+            torch.cuda.current_stream().wait_stream(self._shadows_pending)
+            self._shadows_pending = None
+
+    def finish(self):
+        """Order the aux-stream shadow rebuild of the last step before anything the caller does next on the current stream
+        (state_dict snapshot, load_state_dict of the next round, a new trainer), and read the overflow word."""
+        self._wait_shadows()
+        self.check_overflow()
+
+    def _track_bn(self):
+        if not self.bb._bn_frozen:            # frozen BatchNorms track nothing (num_batches_tracked included)
+            self.bb._flat_nbt += 1
+
+    def _forward(self, imgs, labels, track_bn: bool = True):
+        """Training forward pass of the backbone -> (plan, features, labels); ``track_bn`` False leaves the num_batches_tracked increment
+        to the caller."""
+        bb = self.bb
+        bb._check_input(imgs)
+        labels = _C.require_gpu_tensor(labels, torch.int64, "labels")
+        plan = bb._plan(imgs.shape[0])
+        feats = bb._enqueue_forward(plan, imgs, bb._fwd_mode())
+        if track_bn:
+            self._track_bn()
+        return plan, feats, labels
+
+    def _backward(self, plan, imgs, dfeats, fuse: bool, unscale: bool):
+        """Backbone backward pass from d(loss)/d(features).  ``fuse``: the update of every parameter range whose gradient is final rides on the
+        weight-gradient stream inside the pass (the same kernels and arithmetic, enqueued earlier: bit-identical to backward + one flat update);
+        ``_update_backbone()`` finishes [0, done_from).  fp16-storage library: the gradient enters multiplied by the loss scale S and the fused
+        update kernels undo it in place; for the rest of the buffer ``unscale`` chooses who does: True multiplies it by 1/S now
+        (``FusedTrainer.forward_backward()`` hands out true gradients), False leaves it to the update kernel (gscale = 1/S)."""
+        bb = self.bb
+        self._wait_shadows()                  # dgrad shadows rebuilt on aux after the last update
+        st = _C.stream()
+        aux = self.aux_stream.cuda_stream if self.aux_stream is not None else None
+        S = self._scale_used = self.loss_scale
+        if self.guarded:
+            dfeats = dfeats * S
+        args = (plan.handle, imgs.data_ptr(), dfeats.data_ptr(), bb._flat_params.data_ptr(), bb._shadow.data_ptr(), plan.act.data_ptr(),
+                plan.ws.data_ptr(), bb._flat_grads.data_ptr())
+        self._sgd_done_from = None
+        self._grads_scaled = self.guarded and (fuse or not unscale)
+        if not fuse:
+            _C.call("fedfr_net_backward2", *args, st, aux)
+            if self.guarded and unscale:
+                bb._flat_grads.mul_(1.0 / S)  # (inf / NaN stay what they are: the guarded update skips those elements)
+            return
+        done = ctypes.c_longlong(0)
+        sgd = (self.mom.data_ptr(), self.lr, self.mu, self.wd, 1 if self.first else 0)
+        if self.guarded:
+            _C.call("fedfr_net_backward2_sgd_scaled", *args, *sgd, 1.0 / S, self._overflow.data_ptr(), ctypes.byref(done), st, aux)
+        else:
+            _C.call("fedfr_net_backward2_sgd", *args, *sgd, ctypes.byref(done), st, aux)
+        self._sgd_done_from = int(done.value)
+
+    def _update_backbone(self):
+        """SGD update of the backbone range the last backward pass did not update itself ([0, done_from), or all of it)."""
+        bb = self.bb
+        n = self.n_train if self._sgd_done_from is None else self._sgd_done_from
+        gscale = 1.0 / self._scale_used if self._grads_scaled else 1.0
+        self._sgd_done_from, self._grads_scaled = None, False
+        if n > 0:
+            ops.sgd_step(bb._flat_params, bb._flat_grads, self.mom, bb._shadow, n, self.lr, self.mu, self.wd, self.first, gscale,
+                         self._sgd_overflow)
+
+    def _end_step(self):
+        """After the step's last update: count the step for the overflow poll, then rebuild the dgrad-layout weight copies (only the NEXT
+        backward needs them; the forward mirror was written by the SGD kernels) on the aux stream, where they overlap the next forward pass."""
+        bb = self.bb
+        if self.guarded:
+            self._count_step()
+        if self.aux_stream is not None:
+            self.aux_stream.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(self.aux_stream):
+                bb.refresh_shadows(False)
+            self._shadows_pending = self.aux_stream
+        else:
+            bb.refresh_shadows(False)
+        self.first = False
+
+
+class FusedTrainer(_BackboneTrainer):
+    """step(imgs, labels) == the body of the reference hot loop (client.py:537-550) for the Sequential model:
     zero_grad; logits = fc(backbone(imgs)); logits = margin(logits, labels); loss = CE; backward; SGD step.
     """
 
@@ -292,79 +397,37 @@ class FusedTrainer(_LossScaleGuard):
             fc = self.pfc.weight
         if loss_name not in ("CosFace", "ArcFace"):
             raise ValueError("loss must be CosFace or ArcFace")
-        self.bb = backbone
         self.fc = _C.require_gpu_tensor(fc, f32, "fc weight")
         self.arc = loss_name == "ArcFace"
-        self.s, self.m, self.lr, self.mu, self.wd = float(s), float(m), float(lr), float(momentum), float(weight_decay)
-        bb = backbone
-        bb._ensure_device_state()
-        bb.train()
-        bb.require_all_trainable("FusedTrainer")
-        self.n_train = bb.trainable_count()
-        self.mom = torch.empty(self.n_train, dtype=f32, device=bb.device)
+        self.s, self.m = float(s), float(m)
+        super().__init__(backbone, lr, momentum, weight_decay, aux_slot)
         if self.pfc is None:
             self.fc_mom = torch.empty_like(self.fc)
             self.fc_grad = torch.empty_like(self.fc)
-        self.first = True
-        # weight-gradient GEMMs run on a second HIP stream (fedfr_net_backward2) unless FEDFR_DUAL_STREAM=0
-        self.aux_stream = _make_aux_stream(bb.device, aux_slot)
-        self._shadows_pending = None
-        if self.aux_stream is not None:       # the shared aux stream may still carry the previous trainer's shadow rebuild of this backbone
-            torch.cuda.current_stream().wait_stream(self.aux_stream)
-        bb.refresh_shadows(True)
-        # step(): SGD folded into the backward pass (fedfr_net_backward2_sgd) unless FEDFR_FUSE_SGD=0; forward_backward() + optimizer_step()
-        # called separately keep the gradients-then-update contract
-        import os
-        self.fuse_sgd = os.environ.get("FEDFR_FUSE_SGD", "1") != "0"
+        # step() folds the update into the backward pass (fuse_sgd); forward_backward() + optimizer_step() called separately keep the
+        # gradients-then-update contract
         self._fuse_sgd = False
-        self._sgd_done_from = None
-        self._grads_scaled = False          # fp16-storage build: [0, _sgd_done_from) of the gradient buffer still carries the loss scale
-        self._scale_used = 1.0              # ... namely this one (the scale the last backward pass multiplied in)
-        self._init_loss_scale(bb.device)
-
-    def set_lr(self, lr: float):
-        self.lr = float(lr)
-
-    def finish(self):
-        """Order the aux-stream shadow rebuild of the last step before anything the caller does next on the current stream
-        (state_dict snapshot, load_state_dict of the next round, a new trainer)."""
-        if self._shadows_pending is not None:
-            torch.cuda.current_stream().wait_stream(self._shadows_pending)
-            self._shadows_pending = None
-        self.check_overflow()
 
     @_C.on_device(lambda self: self.bb.device)
     def forward_backward(self, imgs: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
-        bb = self.bb
-        bb._check_input(imgs)
-        labels = _C.require_gpu_tensor(labels, torch.int64, "labels")
+        plan, feats, labels = self._forward(imgs, labels, track_bn=self.pfc is not None)
         B = imgs.shape[0]
-        plan = bb._plan(B)
-        st = _C.stream()
-        feats = torch.empty(B, bb.num_features, dtype=f32, device=bb.device)
-        bb._pre_forward(plan, bb._fwd_mode())
-        _C.call("fedfr_net_forward", plan.handle, imgs.data_ptr(), bb._flat_params.data_ptr(), bb._flat_bufs.data_ptr(),
-                bb._shadow.data_ptr(), plan.act.data_ptr(), plan.ws.data_ptr(), feats.data_ptr(), bb._fwd_mode(), st)
-        bb._fwd_generation += 1
+        fn, finv = ops.normalize_rows(feats)
         if self.pfc is not None:
-            if not bb._bn_frozen:
-                bb._flat_nbt += 1
             # upstream PartialFC protocol (SURVEY Â§3.5): normalised embeddings in, d(embedding) out
-            fn, finv = ops.normalize_rows(feats)
             if self.pfc.world_size == 1:
                 x_slabs, loss = self.pfc.forward_backward(labels, fn, None, x_grad_slabs=True)      # split-K slabs, added by the pass below
                 dfeats = ops.normalize_rows_bwd_slabs(fn, finv, x_slabs.contiguous())
             else:
                 x_grad, loss = self.pfc.forward_backward(labels, fn, None)
                 dfeats = ops.normalize_rows_bwd(fn, finv, x_grad.contiguous())
-            self._backward(plan, imgs, dfeats, st)
+            self._backward(plan, imgs, dfeats, self._fuse_sgd, unscale=True)
             return loss
         # head: cosine logits -> margin -> softmax CE, gradient wrt cosine written in place
-        fn, finv = ops.normalize_rows(feats)
         wn, winv = ops.normalize_rows(self.fc)
         C_, D_ = wn.shape
-        if _HEAD_SPLITK and C_ <= 4096 and D_ >= 256 and C_ >= 256:
-            # round 3: the two GEMMs on the path are latency chains (16 / 32 dependent k-steps on 32 / 16 workgroups): split-K slabs that
+        if C_ <= 4096 and D_ >= 256 and C_ >= 256:
+            # the two GEMMs on the path are latency chains (16 / 32 dependent k-steps on 32 / 16 workgroups): split-K slabs that
             # the consumer adds in order, and margin -> softmax -> gradient as one launch
             ks, kd = _split_for(D_), _split_for(C_)
             prob_t, g = ops.softmax_ce_fused(ops.sgemm(fn, wn, trans_b=True, splits=ks), labels, self.s, self.m, self.arc, 1.0 / B)
@@ -381,17 +444,16 @@ class FusedTrainer(_LossScaleGuard):
             dwn = ops.sgemm(g, fn, trans_a=True)
             _C.call("fedfr_normalize_rows_bwd", wn.data_ptr(), winv.data_ptr(), dwn.data_ptr(), self.fc_grad.data_ptr(),
                     wn.shape[0], wn.shape[1], 0.0, _C.stream())
-            if not bb._bn_frozen:
-                bb._flat_nbt += 1
+            self._track_bn()
             return loss
 
-        if self.aux_stream is None or not _HEAD_OFF_PATH:
+        if self.aux_stream is None:
             loss = off_path()
-            self._backward(plan, imgs, dfeats, st)
+            self._backward(plan, imgs, dfeats, self._fuse_sgd, unscale=True)
             return loss
-        # round 3: those ~25 us of launches go to the weight-gradient stream BEHIND the backward pass's own work there (that stream is
-        # ordered after the head kernels above by the pass's first fork) and the main stream joins it again before anything else runs
-        self._backward(plan, imgs, dfeats, st)
+        # those ~25 us of launches go to the weight-gradient stream BEHIND the backward pass's own work there (that stream is ordered
+        # after the head kernels above by the pass's first fork) and the main stream joins it again before anything else runs
+        self._backward(plan, imgs, dfeats, self._fuse_sgd, unscale=True)
         main = torch.cuda.current_stream()
         try:
             with torch.cuda.stream(self.aux_stream):
@@ -403,89 +465,16 @@ class FusedTrainer(_LossScaleGuard):
         loss.record_stream(main)
         return loss
 
-    def _backward(self, plan, imgs, dfeats, st):
-        bb = self.bb
-        if self._shadows_pending is not None:
-            torch.cuda.current_stream().wait_stream(self._shadows_pending)   # dgrad shadows rebuilt on aux after the last SGD step
-            self._shadows_pending = None
-        aux = self.aux_stream.cuda_stream if self.aux_stream is not None else None
-        S = self._scale_used = self.loss_scale      # (the device's scale may be lowered by another trainer's poll before optimizer_step(): remember ours)
-        self._grads_scaled = False
-        if self.guarded:
-            # fp16-storage library: the gradient enters the backbone multiplied by the loss scale S
-            ds = dfeats * S
-            if self._fuse_sgd:
-                # step(): the update kernels undo the scale themselves (fedfr_sgd_step_scaled: g * 1/S, stored back), so the update rides inside
-                # the backward pass exactly as in the bf16 build; optimizer_step() finishes [0, done_from) the same way
-                import ctypes
-                done = ctypes.c_longlong(0)
-                _C.call("fedfr_net_backward2_sgd_scaled", plan.handle, imgs.data_ptr(), ds.data_ptr(), bb._flat_params.data_ptr(),
-                        bb._shadow.data_ptr(), plan.act.data_ptr(), plan.ws.data_ptr(), bb._flat_grads.data_ptr(), self.mom.data_ptr(),
-                        self.lr, self.mu, self.wd, 1 if self.first else 0, 1.0 / S, self._overflow.data_ptr(), ctypes.byref(done), st, aux)
-                self._sgd_done_from = int(done.value)
-                self._grads_scaled = True
-                return
-            # forward_backward(): the parameter gradients are unscaled before anything reads them
-            _C.call("fedfr_net_backward2", plan.handle, imgs.data_ptr(), ds.data_ptr(), bb._flat_params.data_ptr(),
-                    bb._shadow.data_ptr(), plan.act.data_ptr(), plan.ws.data_ptr(), bb._flat_grads.data_ptr(), st, aux)
-            bb._flat_grads.mul_(1.0 / S)         # (inf / NaN stay what they are: optimizer_step()'s guarded kernel skips those elements)
-            self._sgd_done_from = None
-            return
-        if self._fuse_sgd:
-            # step(): the optimiser update of every parameter range whose gradient is final rides on the weight-gradient stream inside the
-            # backward pass (bn2 / fc / features first, then stage by stage); optimizer_step() finishes [0, done_from)
-            import ctypes
-            done = ctypes.c_longlong(0)
-            _C.call("fedfr_net_backward2_sgd", plan.handle, imgs.data_ptr(), dfeats.data_ptr(), bb._flat_params.data_ptr(),
-                    bb._shadow.data_ptr(), plan.act.data_ptr(), plan.ws.data_ptr(), bb._flat_grads.data_ptr(), self.mom.data_ptr(),
-                    self.lr, self.mu, self.wd, 1 if self.first else 0, ctypes.byref(done), st, aux)
-            self._sgd_done_from = int(done.value)
-            return
-        _C.call("fedfr_net_backward2", plan.handle, imgs.data_ptr(), dfeats.data_ptr(), bb._flat_params.data_ptr(),
-                bb._shadow.data_ptr(), plan.act.data_ptr(), plan.ws.data_ptr(), bb._flat_grads.data_ptr(), st, aux)
-
     @_C.on_device(lambda self: self.bb.device)
     def optimizer_step(self):
-        bb = self.bb
-        st = _C.stream()
-        first = 1 if self.first else 0
-        n_rest = self.n_train if self._sgd_done_from is None else self._sgd_done_from      # the rest was updated inside the backward pass
-        self._sgd_done_from = None
-        scaled, self._grads_scaled = self._grads_scaled, False
-        if self.guarded:
-            # fp16-storage library: EVERY update is the guarded kernel â€” the rest of a fused step still carries the scale (gscale = 1/S),
-            # the gradients of forward_backward() were unscaled there already (gscale = 1); non-finite elements are skipped and flagged either way
-            ovf = self._overflow.data_ptr()
-            if n_rest > 0:
-                _C.call("fedfr_sgd_step_scaled", bb._flat_params.data_ptr(), bb._flat_grads.data_ptr(), self.mom.data_ptr(),
-                        bb._shadow.data_ptr(), n_rest, self.lr, self.mu, self.wd, first, 1.0 / self._scale_used if scaled else 1.0, ovf, st)
-            if self.pfc is not None:
-                self.pfc.fused_sgd_update(self.lr, self.mu, self.wd, overflow=self._overflow)      # sampled rows: guarded SGD + scatter back
-            else:
-                # (fp32 head: no scale to undo, but a forward pass that overflowed fp16 hands it non-finite gradients too: same guard)
-                _C.call("fedfr_sgd_step_scaled", self.fc.data_ptr(), self.fc_grad.data_ptr(), self.fc_mom.data_ptr(), None, self.fc.numel(),
-                        self.lr, self.mu, self.wd, first, 1.0, ovf, st)
-            self._count_step()
+        self._update_backbone()
+        if self.pfc is not None:
+            self.pfc.fused_sgd_update(self.lr, self.mu, self.wd, overflow=self._sgd_overflow)      # sampled rows: SGD + scatter back
         else:
-            if n_rest > 0:
-                _C.call("fedfr_sgd_step", bb._flat_params.data_ptr(), bb._flat_grads.data_ptr(), self.mom.data_ptr(),
-                        bb._shadow.data_ptr(), n_rest, self.lr, self.mu, self.wd, first, st)
-            if self.pfc is not None:
-                self.pfc.fused_sgd_update(self.lr, self.mu, self.wd)      # sampled rows: SGD + scatter back
-            else:
-                _C.call("fedfr_sgd_step", self.fc.data_ptr(), self.fc_grad.data_ptr(), self.fc_mom.data_ptr(), None, self.fc.numel(),
-                        self.lr, self.mu, self.wd, first, st)
-        # dgrad-layout weight copies (only needed by the NEXT backward; the forward mirror was written by the SGD kernel):
-        # rebuilt on the aux stream so they overlap the next forward pass
-        if self.aux_stream is not None:
-            main = torch.cuda.current_stream()
-            self.aux_stream.wait_stream(main)
-            with torch.cuda.stream(self.aux_stream):
-                bb.refresh_shadows(False)
-            self._shadows_pending = self.aux_stream
-        else:
-            bb.refresh_shadows(False)
-        self.first = False
+            # (fp16 library: the fp32 head has no scale to undo, but a forward pass that overflowed fp16 hands it non-finite gradients too)
+            ops.sgd_step(self.fc, self.fc_grad, self.fc_mom, None, self.fc.numel(), self.lr, self.mu, self.wd, self.first,
+                         overflow=self._sgd_overflow)
+        self._end_step()
 
     def step(self, imgs: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
         self._fuse_sgd = self.fuse_sgd
@@ -497,94 +486,25 @@ class FusedTrainer(_LossScaleGuard):
         return loss
 
 
-class FusedHeadTrainer(_LossScaleGuard):
+class FusedHeadTrainer(_BackboneTrainer):
     """Fused backbone step with an arbitrary differentiable head â€” the training body of ``train_with_public_data``
-    (reference client.py:354-441): the backbone runs as ``fedfr_net_forward`` / ``fedfr_net_backward2`` + the flat SGD
-    kernel exactly as in ``FusedTrainer``; the head (FC_module / BCE_module / margin / CE / contrastive â€” each a HIP-backed
-    autograd Function of this package) is evaluated on the embedding leaf, and its few parameters get the same
-    ``fedfr_sgd_step`` (torch.optim.SGD semantics: coupled weight decay, momentum buffer created on first use)."""
+    (reference client.py:354-441): the backbone step is ``FusedTrainer``'s; the head (FC_module / BCE_module / margin / CE / contrastive â€”
+    each a HIP-backed autograd Function of this package) is evaluated on the embedding leaf, and its few parameters get the same
+    SGD kernel (torch.optim.SGD semantics: coupled weight decay, momentum buffer created on first use)."""
 
     def __init__(self, backbone: "backbones.IResNet", head_params: Iterable[nn.Parameter], lr: float = 0.1,
                  momentum: float = 0.9, weight_decay: float = 5e-4, aux_slot: int = 0):
-        import os
-        self.bb = backbone
         self.head_params = list(head_params)
-        self.lr, self.mu, self.wd = float(lr), float(momentum), float(weight_decay)
-        bb = backbone
-        bb._ensure_device_state()
-        bb.train()
-        bb.require_all_trainable("FusedHeadTrainer")
         for hp in self.head_params:
             _C.require_gpu_tensor(hp.data, f32, "head parameter")
-        self.n_train = bb.trainable_count()
-        self.mom = torch.empty(self.n_train, dtype=f32, device=bb.device)
         self.head_mom = {}
-        self.first = True
-        self.fuse_sgd = os.environ.get("FEDFR_FUSE_SGD", "1") != "0"
-        self._init_loss_scale(bb.device)
-        self.aux_stream = _make_aux_stream(bb.device, aux_slot)
-        self._shadows_pending = None
-        if self.aux_stream is not None:
-            torch.cuda.current_stream().wait_stream(self.aux_stream)
-        bb.refresh_shadows(True)
-
-    def set_lr(self, lr: float):
-        self.lr = float(lr)
-
-    def _forward(self, imgs, labels):
-        bb = self.bb
-        bb._check_input(imgs)
-        labels = _C.require_gpu_tensor(labels, torch.int64, "labels")
-        plan = bb._plan(imgs.shape[0])
-        feats = torch.empty(imgs.shape[0], bb.num_features, dtype=f32, device=bb.device)
-        bb._pre_forward(plan, bb._fwd_mode())
-        _C.call("fedfr_net_forward", plan.handle, imgs.data_ptr(), bb._flat_params.data_ptr(), bb._flat_bufs.data_ptr(),
-                bb._shadow.data_ptr(), plan.act.data_ptr(), plan.ws.data_ptr(), feats.data_ptr(), bb._fwd_mode(), _C.stream())
-        if not bb._bn_frozen:
-            bb._flat_nbt += 1
-        bb._fwd_generation += 1
-        return plan, feats, labels
+        super().__init__(backbone, lr, momentum, weight_decay, aux_slot)
 
     def _backward_and_update(self, plan, imgs, dfeats):
         """backbone backward from d(loss)/d(features), then opt.step() for the backbone (flat) and every head parameter with a grad."""
-        bb, st = self.bb, _C.stream()
         dfeats = _C.require_gpu_tensor(dfeats.contiguous(), f32, "d(loss)/d(features)")
-        if self._shadows_pending is not None:
-            torch.cuda.current_stream().wait_stream(self._shadows_pending)
-            self._shadows_pending = None
-        S = self.loss_scale                               # the fp16-storage library scales the incoming gradient (bf16 library: no scale)
-        guarded = self.guarded
-        if guarded:
-            dfeats = dfeats * S
-        aux = self.aux_stream.cuda_stream if self.aux_stream is not None else None
-        ovf = self._overflow.data_ptr()
-        first = 1 if self.first else 0
-        n_rest = self.n_train
-        # ---- backward + opt.step() of the backbone.  Round 5: as in FusedTrainer.step(), the update of every parameter range whose gradient is final
-        # rides on the weight-gradient stream INSIDE the backward pass (fedfr_net_backward2_sgd: the same kernels, the same elementwise arithmetic,
-        # enqueued earlier â€” bit-identical to backward + one flat update, FEDFR_FUSE_SGD=0); the flat kernel finishes [0, done_from).
-        # (fp16-storage library: the kernels undo the scale in place and skip non-finite elements, _LossScaleGuard)
-        if self.fuse_sgd:
-            import ctypes
-            done = ctypes.c_longlong(0)
-            if guarded:
-                _C.call("fedfr_net_backward2_sgd_scaled", plan.handle, imgs.data_ptr(), dfeats.data_ptr(), bb._flat_params.data_ptr(),
-                        bb._shadow.data_ptr(), plan.act.data_ptr(), plan.ws.data_ptr(), bb._flat_grads.data_ptr(), self.mom.data_ptr(),
-                        self.lr, self.mu, self.wd, first, 1.0 / S, ovf, ctypes.byref(done), st, aux)
-            else:
-                _C.call("fedfr_net_backward2_sgd", plan.handle, imgs.data_ptr(), dfeats.data_ptr(), bb._flat_params.data_ptr(),
-                        bb._shadow.data_ptr(), plan.act.data_ptr(), plan.ws.data_ptr(), bb._flat_grads.data_ptr(), self.mom.data_ptr(),
-                        self.lr, self.mu, self.wd, first, ctypes.byref(done), st, aux)
-            n_rest = int(done.value)
-        else:
-            _C.call("fedfr_net_backward2", plan.handle, imgs.data_ptr(), dfeats.data_ptr(), bb._flat_params.data_ptr(),
-                    bb._shadow.data_ptr(), plan.act.data_ptr(), plan.ws.data_ptr(), bb._flat_grads.data_ptr(), st, aux)
-        if n_rest > 0 and guarded:
-            _C.call("fedfr_sgd_step_scaled", bb._flat_params.data_ptr(), bb._flat_grads.data_ptr(), self.mom.data_ptr(),
-                    bb._shadow.data_ptr(), n_rest, self.lr, self.mu, self.wd, first, 1.0 / S, ovf, st)
-        elif n_rest > 0:
-            _C.call("fedfr_sgd_step", bb._flat_params.data_ptr(), bb._flat_grads.data_ptr(), self.mom.data_ptr(),
-                    bb._shadow.data_ptr(), n_rest, self.lr, self.mu, self.wd, first, st)
+        self._backward(plan, imgs, dfeats, self.fuse_sgd, unscale=False)
+        self._update_backbone()
         for hp in self.head_params:
             if hp.grad is None:                                       # torch.optim.SGD skips parameters without a gradient
                 continue
@@ -594,23 +514,8 @@ class FusedHeadTrainer(_LossScaleGuard):
             first = buf is None
             if first:
                 buf = self.head_mom[hp] = torch.empty_like(hp.data)
-            if guarded:
-                _C.call("fedfr_sgd_step_scaled", hp.data.data_ptr(), hp.grad.data_ptr(), buf.data_ptr(), None, hp.numel(), self.lr, self.mu,
-                        self.wd, 1 if first else 0, 1.0, ovf, st)
-            else:
-                _C.call("fedfr_sgd_step", hp.data.data_ptr(), hp.grad.data_ptr(), buf.data_ptr(), None, hp.numel(), self.lr, self.mu,
-                        self.wd, 1 if first else 0, st)
-        if self.aux_stream is not None:
-            main = torch.cuda.current_stream()
-            self.aux_stream.wait_stream(main)
-            with torch.cuda.stream(self.aux_stream):
-                bb.refresh_shadows(False)
-            self._shadows_pending = self.aux_stream
-        else:
-            bb.refresh_shadows(False)
-        self.first = False
-        if guarded:
-            self._count_step()
+            ops.sgd_step(hp.data, hp.grad, buf, None, hp.numel(), self.lr, self.mu, self.wd, first, overflow=self._sgd_overflow)
+        self._end_step()
 
     @_C.on_device(lambda self: self.bb.device)
     def step(self, imgs: torch.Tensor, labels: torch.Tensor, head_loss):
@@ -627,13 +532,6 @@ class FusedHeadTrainer(_LossScaleGuard):
         if isinstance(out, tuple):
             return tuple(o.detach() if torch.is_tensor(o) else o for o in out)
         return loss.detach()
-
-    def finish(self):
-        """Order the aux-stream shadow rebuild before anything the caller does next on the current stream."""
-        if self._shadows_pending is not None:
-            torch.cuda.current_stream().wait_stream(self._shadows_pending)
-            self._shadows_pending = None
-        self.check_overflow()
 
 
 class ShardedHeadTrainer(FusedHeadTrainer):
@@ -684,7 +582,7 @@ class ShardedHeadTrainer(FusedHeadTrainer):
             ops.axpy_(dfeats, leaf.grad, 1.0)
             bce = bce.detach()
         self._backward_and_update(plan, imgs, dfeats)
-        self.pfc.fused_sgd_update(self.lr, self.mu, self.wd, overflow=self._overflow if self.guarded else None)
+        self.pfc.fused_sgd_update(self.lr, self.mu, self.wd, overflow=self._sgd_overflow)
         loss = cos_loss if bce is None else ops.axpy_(ops.scale(bce.reshape(1), self.bce_weight), cos_loss.reshape(1), 1.0).reshape(())
         return loss, cos_loss, bce
 

@@ -211,6 +211,22 @@ def colsum(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def sgd_step(param: torch.Tensor, grad: torch.Tensor, mom: torch.Tensor, shadow: Optional[torch.Tensor], n: int, lr: float, mu: float,
+             wd: float, first: bool, gscale: float = 1.0, overflow: Optional[torch.Tensor] = None) -> None:
+    """torch.optim.SGD step (coupled weight decay, momentum buffer set on ``first``) of elements [0, n) in place; ``shadow``: the 16-bit
+    mirror the kernel rewrites alongside.  With the fp16-storage library's device word ``overflow`` it is the guarded kernel
+    (``fedfr_sgd_step_scaled``: gradient times ``gscale`` stored back, non-finite elements skipped and flagged in the word); without one
+    the plain kernel, which has no scale to undo."""
+    if overflow is None and gscale != 1.0:
+        raise ValueError("sgd_step: a gradient scale needs the guarded kernel (pass the overflow word)")
+    sh = shadow.data_ptr() if shadow is not None else None
+    if overflow is not None:
+        _C.call("fedfr_sgd_step_scaled", param.data_ptr(), grad.data_ptr(), mom.data_ptr(), sh, n, lr, mu, wd, 1 if first else 0, gscale,
+                overflow.data_ptr(), _C.stream())
+    else:
+        _C.call("fedfr_sgd_step", param.data_ptr(), grad.data_ptr(), mom.data_ptr(), sh, n, lr, mu, wd, 1 if first else 0, _C.stream())
+
+
 # ------------------------------------------------------------------------------------------ autograd bridges
 class CosineLinearFn(torch.autograd.Function):
     """normalize(x) @ normalize(w).T  (reference FC_module.forward, client.py:69-74)."""

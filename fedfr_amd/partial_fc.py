@@ -237,11 +237,7 @@ class PartialFC(Module):
         exist, so this is never a 'first' step — partial_fc.py:124-126).  ``overflow``: the fp16-storage library's device word
         (client._LossScaleGuard) — the update then skips and flags non-finite gradient elements like every other update of that library."""
         sw = self.sub_weight.data
-        if overflow is not None:
-            _C.call("fedfr_sgd_step_scaled", sw.data_ptr(), self.sub_weight.grad.data_ptr(), self.sub_weight_mom.data_ptr(), None, sw.numel(),
-                    float(lr), float(momentum), float(weight_decay), 0, 1.0, overflow.data_ptr(), _C.stream())
-        else:
-            _C.call("fedfr_sgd_step", sw.data_ptr(), self.sub_weight.grad.data_ptr(), self.sub_weight_mom.data_ptr(), None, sw.numel(),
-                    float(lr), float(momentum), float(weight_decay), 0, _C.stream())
+        ops.sgd_step(sw, self.sub_weight.grad, self.sub_weight_mom, None, sw.numel(), float(lr), float(momentum), float(weight_decay), False,
+                     overflow=overflow)
         if int(self.sample_rate) != 1:
             self.update()
