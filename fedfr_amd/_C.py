@@ -103,6 +103,8 @@ SIGNATURES = {
     "fedfr_pad_input_nhwc": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "fedfr_preprocess_u8": (i32, [vp, vp, vp, i32, i32, i32, vp]),
     "fedfr_roc_histogram": (i32, [vp, vp, i32, i32, i32, vp, vp]),
+    "fedfr_ident_workspace_bytes": (sz, [i32, i32, i32]),
+    "fedfr_ident_topk": (i32, [vp, vp, i32, vp, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, sz, vp]),
     "fedfr_contrastive": (i32, [vp, vp, vp, i32, i32, f32, vp, vp, vp]),
     "fedfr_sum_scale": (i32, [vp, i32, f32, vp, vp]),
     "fedfr_sgd_step": (i32, [vp, vp, vp, vp, sz, f32, f32, f32, i32, vp]),

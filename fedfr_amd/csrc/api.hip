@@ -619,6 +619,12 @@ int fedfr_class_accumulate(const float* feats, const long long* label, int B, in
 int fedfr_roc_histogram(const float* feats, const long long* label, int N, int D, int T, unsigned long long* hist, void* stream) {
   return head_roc_histogram(feats, label, N, D, T, hist, ST(stream));
 }
+size_t fedfr_ident_workspace_bytes(int Q, int S, int K) { return ident_workspace_bytes(Q, S, K); }
+int fedfr_ident_topk(const float* query, const long long* qid, int Q, const float* gallery, const long long* gid, int G, int D,
+                     const long long* seg, int S, int K, double* pos, double* neg_topk, long long* neg_count, void* ws, size_t ws_bytes,
+                     void* stream) {
+  return ident_topk(query, qid, Q, gallery, gid, G, D, seg, S, K, pos, neg_topk, neg_count, ws, ws_bytes, ST(stream));
+}
 int fedfr_bias_prelu_bwd(const uint16_t* dy, const uint16_t* x, const float* bias, const float* alpha, int M, int C, float* partials,
                          float* coef, float* dbias, float* dalpha, const uint16_t* add, uint16_t* dx, void* stream) {
   return ew_bias_prelu_bwd(BF(dy), BF(x), bias, alpha, M, C, partials, coef, dbias, dalpha, BF(add), BFM(dx), ST(stream));

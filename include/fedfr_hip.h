@@ -333,6 +333,17 @@ int fedfr_preprocess_u8(const unsigned char* src_hwc, const unsigned char* flip,
  * bin = int((<feats[a], feats[b]> + 1) * 1000) in fp64; hist[2*bin] += same label, hist[2*bin+1] += different label.
  * hist: 4002 uint64 counters, accumulated (zero them first). */
 int fedfr_roc_histogram(const float* feats, const long long* label, int N, int D, int T, unsigned long long* hist, void* stream);
+/* 1:N identification (local_all.py:142-176 evaluation, one launch for all clients of :274-297): query [Q][D] fp32 with per-query id
+ * qid[Q] (-1: not enrolled), gallery [G][D] fp32 with per-column id gid[G] (distinct among the ids >= 0), columns split into S client
+ * segments by seg[S+1] (HOST memory, 0 = seg[0] < seg[1] < ... < seg[S] = G).  Scores are fp64 dot products of the fp32 features.
+ * Pair (q, c) is positive iff qid[q] >= 0 && qid[q] == gid[c]; every other pair is a negative of the segment owning column c.
+ * Outputs: pos[Q] fp64 (NaN where a query has no positive), neg_topk[S][K] fp64 (the K largest negatives of each segment, duplicates
+ * counted, descending, -inf past neg_count), neg_count[S] int64.  1 <= K <= 1024.  The matrix is never materialised; results are exact
+ * and run-to-run identical.  ws: fedfr_ident_workspace_bytes(Q, S, K) bytes of device memory. */
+size_t fedfr_ident_workspace_bytes(int Q, int S, int K);
+int fedfr_ident_topk(const float* query, const long long* qid, int Q, const float* gallery, const long long* gid, int G, int D,
+                     const long long* seg, int S, int K, double* pos, double* neg_topk, long long* neg_count, void* ws, size_t ws_bytes,
+                     void* stream);
 /* model-contrastive term (client.py:372-375, :415-418): row_loss[b] = CE([cos(x,g)/T, cos(x,l)/T], 0) with
  * nn.CosineSimilarity(dim=1, eps=1e-8); dx = d(mean_b row_loss)/dx (optional).  g, l: frozen global / last-round embeddings. */
 int fedfr_contrastive(const float* feats, const float* global_feats, const float* last_feats, int B, int D, float temperature,

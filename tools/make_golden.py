@@ -17,6 +17,7 @@ What is captured (reference symbol → fixture):
   roc_cuda.calc_ROC / plot_ROC (kernel body executed through a numba stub) → roc.npz
   eval-mode embedding sweeps, class centres and feature-based hard-negative mining → mining_r18.npz
   the train_with_public_data loop body (Branch_model + BCE + contrastive; Sequential + reweight) → client_public_{full,seq}.npz
+  local_all.combine_features / evaluation (the --task 1:n client loop) → ident_1n.npz
 """
 import os
 import sys
@@ -743,9 +744,67 @@ def gen_checkpoint():
          meta_prefixes=np.array(list(meta.keys())), meta_versions=np.array([meta[k].get("version", -1) for k in meta], dtype=np.int64))
 
 
+# ---- 12. 1:N identification (local_all.py:131-176 combine_features / evaluation, the --task 1:n client loop :274-297) ---------------
+def _ident_inputs(seed, nid, ipi, extra, gimgs, D):
+    """fp16-representable features: one normalised centre per id, queries / gallery images = centre + noise of a per-row strength,
+    normalised.  The last ``extra`` ids have queries only (never enrolled in any client's gallery)."""
+    g = torch.Generator().manual_seed(seed)
+    centers = F.normalize(torch.randn(nid + extra, D, generator=g))
+    qlab = torch.arange(nid + extra).repeat_interleave(ipi)
+    qs = 0.6 + 1.2 * torch.rand(len(qlab), 1, generator=g)
+    query = F.normalize(centers[qlab] + qs * torch.randn(len(qlab), D, generator=g) / D ** 0.5).half()
+    glab = torch.arange(nid).repeat_interleave(gimgs)
+    gs = 0.3 + 0.6 * torch.rand(len(glab), 1, generator=g)
+    gallery = F.normalize(centers[glab] + gs * torch.randn(len(glab), D, generator=g) / D ** 0.5).half()
+    return query.numpy(), qlab.numpy().astype(np.int64), gallery.numpy(), glab.numpy().astype(np.int64)
+
+
+def _ident_run(local_all, query, qlab, gallery, glab, nid, num_client, ipi):
+    """local_all.py:274-297 for one client count; returns per-client results, their mean, the printed thresholds, the galleries and
+    the positive scores (for the margin check)."""
+    import io
+    import re
+    results, ths, gals, pos = [], [], [], []
+    per = nid // num_client
+    for c in range(num_client):
+        start_ID, end_ID = c * per, (c + 1) * per
+        gallery_feats, _ = local_all.combine_features(gallery, glab, start_ID, end_ID)
+        query_labels = qlab.copy()
+        true_idx = np.zeros(len(query_labels), dtype=bool)
+        true_idx[start_ID * ipi:end_ID * ipi] = True
+        query_labels[true_idx] -= start_ID
+        query_labels[~true_idx] = -1
+        buf = io.StringIO()
+        with contextlib.redirect_stdout(buf):
+            result, fars = local_all.evaluation(query, gallery_feats, query_labels)
+        results.append(result)
+        ths.append([float(t) for t in re.findall(r"th = (-?[0-9.]+)", buf.getvalue())])
+        gals.append(gallery_feats)
+        sim = query[true_idx].astype(np.float64) @ gallery_feats.astype(np.float64).T
+        pos.append(sim[np.arange(true_idx.sum()), query_labels[true_idx]])
+    return np.array(results), np.mean(np.array(results), axis=0), np.array(ths), np.concatenate(gals), pos, fars
+
+
+def gen_ident_1n():
+    import local_all                                           # noqa: E402  (reference)
+    nid, ipi, extra, gimgs, D = 60, 40, 1, 3, 128
+    for seed in range(100):                                    # first seed whose every |pos - th| > 1e-5 (fp32 vs fp64 cannot flip)
+        q, ql, g, gl = _ident_inputs(seed, nid, ipi, extra, gimgs, D)
+        query, gallery = q.astype(np.float32), g.astype(np.float32)
+        runs = {n: _ident_run(local_all, query, ql, gallery, gl, nid, n, ipi) for n in (3, 1)}
+        margin = min(np.min(np.abs(p - t)) for r in runs.values() for p, th in zip(r[4], r[2]) for t in th)
+        rates = np.concatenate([r[0].ravel() for r in runs.values()])
+        if margin > 1e-5 and 0.0 < rates.min() and rates.max() < 1.0:
+            break
+    r3, r1 = runs[3], runs[1]
+    save("ident_1n", query=q, query_labels=ql, gallery=g, gallery_labels=gl, num_ids=nid, imgs_per_id=ipi, seed=seed,
+         fars=np.array(r3[5]), result_c3=r3[0], mean_c3=r3[1], th_c3=r3[2], gallery_mean_c3=r3[3],
+         result_c1=r1[0], mean_c1=r1[1], th_c1=r1[2], min_margin=margin)
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["block", "r50", "r100", "heads", "bce", "sgd", "fedavg", "pfc", "client", "public", "mining", "roc", "sphnet", "sphnet64", "freeze_bn",
-                             "checkpoint"]
+                             "checkpoint", "ident_1n"]
     if "checkpoint" in which:
         gen_checkpoint()
     if "freeze_bn" in which:
@@ -776,6 +835,8 @@ if __name__ == "__main__":
         gen_roc()
     if "mining" in which:
         gen_mining()
+    if "ident_1n" in which:
+        gen_ident_1n()
     if "public" in which:
         for v in ("full", "seq", "bce_rw"):
             gen_public(v)
