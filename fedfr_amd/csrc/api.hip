@@ -625,6 +625,23 @@ int fedfr_ident_topk(const float* query, const long long* qid, int Q, const floa
                      void* stream) {
   return ident_topk(query, qid, Q, gallery, gid, G, D, seg, S, K, pos, neg_topk, neg_count, ws, ws_bytes, ST(stream));
 }
+size_t fedfr_template_pool_workspace_bytes(int N, int norm_images) { return ijbc_template_pool_workspace_bytes(N, norm_images); }
+int fedfr_template_pool(const float* feats, int N, int D, int flip, const float* faceness, int norm_images, const int* t_off, int T,
+                        const int* m_off, int M, const int* img, int NI, int mode, float* raw, double* out, void* ws, size_t ws_bytes,
+                        int* status, void* stream) {
+  return ijbc_template_pool(feats, N, D, flip, faceness, norm_images, t_off, T, m_off, M, img, NI, mode, raw, out, ws, ws_bytes, status,
+                            ST(stream));
+}
+size_t fedfr_roc_counts_workspace_bytes(long long P, int G) { return ijbc_roc_workspace_bytes(P, G); }
+int fedfr_pair_scores_roc(const double* feats, int T, int D, const int* lut, long long lut_n, const long long* p1, const long long* p2,
+                          long long P, double* score, const long long* label, const double* genuine, int G, unsigned long long* counts,
+                          void* ws, size_t ws_bytes, int* status, void* stream) {
+  return ijbc_pair_scores_roc(feats, T, D, lut, lut_n, p1, p2, P, score, label, genuine, G, counts, ws, ws_bytes, status, ST(stream));
+}
+int fedfr_roc_counts(const double* score, const long long* label, long long P, const double* genuine, int G, unsigned long long* counts,
+                     void* ws, size_t ws_bytes, int* status, void* stream) {
+  return ijbc_roc_counts(score, label, P, genuine, G, counts, ws, ws_bytes, status, ST(stream));
+}
 int fedfr_bias_prelu_bwd(const uint16_t* dy, const uint16_t* x, const float* bias, const float* alpha, int M, int C, float* partials,
                          float* coef, float* dbias, float* dalpha, const uint16_t* add, uint16_t* dx, void* stream) {
   return ew_bias_prelu_bwd(BF(dy), BF(x), bias, alpha, M, C, partials, coef, dbias, dalpha, BF(add), BFM(dx), ST(stream));

@@ -43,3 +43,14 @@ size_t ident_workspace_bytes(int Q, int S, int K);
 int ident_topk(const float* query, const long long* qid, int Q, const float* gallery, const long long* gid, int G, int D,
                const long long* seg, int S, int K, double* pos, double* neg_topk, long long* neg_count, void* ws, size_t ws_bytes,
                hipStream_t st);
+// IJB-C template evaluation (ijbc.hip): template pooling, pair scores fused with the ROC counts at the genuine scores
+size_t ijbc_template_pool_workspace_bytes(int N, int norm_images);
+int ijbc_template_pool(const float* feats, int N, int D, int flip, const float* face, int norm_images, const int* t_off, int T,
+                       const int* m_off, int M, const int* img, int NI, int mode, float* raw, double* out, void* ws, size_t ws_bytes,
+                       int* status, hipStream_t st);
+size_t ijbc_roc_workspace_bytes(long long P, int G);
+int ijbc_pair_scores_roc(const double* feats, int T, int D, const int* lut, long long lut_n, const long long* p1, const long long* p2,
+                         long long P, double* score, const long long* label, const double* gv, int G, unsigned long long* counts, void* ws,
+                         size_t ws_bytes, int* status, hipStream_t st);
+int ijbc_roc_counts(const double* score, const long long* label, long long P, const double* gv, int G, unsigned long long* counts, void* ws,
+                    size_t ws_bytes, int* status, hipStream_t st);

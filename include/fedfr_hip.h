@@ -344,6 +344,33 @@ size_t fedfr_ident_workspace_bytes(int Q, int S, int K);
 int fedfr_ident_topk(const float* query, const long long* qid, int Q, const float* gallery, const long long* gid, int G, int D,
                      const long long* seg, int S, int K, double* pos, double* neg_topk, long long* neg_count, void* ws, size_t ws_bytes,
                      void* stream);
+/* IJB-C template evaluation (ijbc_all.py image2template_feature_11/_1n, verification and the TPR@FPR table).
+ * fedfr_template_pool: image features feats [N][D] fp32, or [N][2D] with flip = 1 (the two halves added, test mode F1); optional
+ * faceness [N] (D1: an fp32 multiply); norm_images = 1 divides every image by its fp32 L2 norm first (use_norm_score=False; needs
+ * fedfr_template_pool_workspace_bytes(N, 1) bytes of ws).  The CSR (device int32) lists template t's medias t_off[t] .. t_off[t+1]-1
+ * (t_off [T+1] into [0, M]) and media m's images img[m_off[m]] .. (m_off [M+1] into [0, NI], every media non-empty, img[] < N).  Media
+ * vector: the image itself, or the fp32 sum in list order divided once by the count; template vector: the fp32 sum of its medias in
+ * order, written to raw [T][D] (optional).  out [T][D] fp64 = raw / ||raw||: mode 0 as sklearn normalize (a zero row stays zero),
+ * mode 1 as the explicit divide.  A bad CSR entry sets bit 1 of the device word *status (the template is written as zeros).
+ * D <= 128 or D in {256, 512, 1024}. */
+size_t fedfr_template_pool_workspace_bytes(int N, int norm_images);
+int fedfr_template_pool(const float* feats, int N, int D, int flip, const float* faceness, int norm_images, const int* t_off, int T,
+                        const int* m_off, int M, const int* img, int NI, int mode, float* raw, double* out, void* ws, size_t ws_bytes,
+                        int* status, void* stream);
+/* fedfr_pair_scores_roc: for P pairs of template ids p1/p2 (int64, device), rows lut[id] (int32 [lut_n], -1 = no row) of feats [T][D]
+ * fp64: score[p] = np.sum(f1 * f2, -1) bit for bit (numpy's pairwise order; optional).  With genuine != NULL also the ROC counts at the
+ * G distinct genuine scores genuine[0] > genuine[1] > ... (label[p] == 1: genuine pair), accumulated into counts [3G+1] uint64 (zero
+ * them first): [k] for k in [0, G] = impostors strictly between genuine[k-1] and genuine[k] (k = 0: above all, k = G: below all),
+ * [G+1+k] = impostors equal to genuine[k], [2G+1+k] = genuine pairs equal to genuine[k].  ws: fedfr_roc_counts_workspace_bytes(P, G).
+ * *status bit 2: a pair id without a row (its score is NaN); bit 4: a genuine score missing from the table; bit 8: a non-finite
+ * score (not counted).  1 <= G <= 40000.
+ * fedfr_roc_counts: the same counts for given scores. */
+size_t fedfr_roc_counts_workspace_bytes(long long P, int G);
+int fedfr_pair_scores_roc(const double* feats, int T, int D, const int* lut, long long lut_n, const long long* p1, const long long* p2,
+                          long long P, double* score, const long long* label, const double* genuine, int G, unsigned long long* counts,
+                          void* ws, size_t ws_bytes, int* status, void* stream);
+int fedfr_roc_counts(const double* score, const long long* label, long long P, const double* genuine, int G, unsigned long long* counts,
+                     void* ws, size_t ws_bytes, int* status, void* stream);
 /* model-contrastive term (client.py:372-375, :415-418): row_loss[b] = CE([cos(x,g)/T, cos(x,l)/T], 0) with
  * nn.CosineSimilarity(dim=1, eps=1e-8); dx = d(mean_b row_loss)/dx (optional).  g, l: frozen global / last-round embeddings. */
 int fedfr_contrastive(const float* feats, const float* global_feats, const float* last_feats, int B, int D, float temperature,

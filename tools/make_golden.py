@@ -14,6 +14,7 @@ What is captured (reference symbol → fixture):
   server.FedPavg / FedAvg_on_FC           → fedavg.npz
   partial_fc.PartialFC (W=1, and W=2 over gloo) → pfc_w1_*.npz / pfc_w2.npz
   a 3-step Client.train-equivalent loop on iresnet18 → client_r18.npz
+  ijbc_all.image2template_feature_11 / verification + roc_curve and the TPR@FPR pick → ijbc.npz
   roc_cuda.calc_ROC / plot_ROC (kernel body executed through a numba stub) → roc.npz
   eval-mode embedding sweeps, class centres and feature-based hard-negative mining → mining_r18.npz
   the train_with_public_data loop body (Branch_model + BCE + contrastive; Sequential + reweight) → client_public_{full,seq}.npz
@@ -23,6 +24,7 @@ import os
 import sys
 import types
 import contextlib
+import io
 
 sys.dont_write_bytecode = True
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -802,9 +804,67 @@ def gen_ident_1n():
          result_c1=r1[0], mean_c1=r1[1], th_c1=r1[2], min_margin=margin)
 
 
+# ---- 13. IJB-C job 1:1 (ijbc_all.py:225-326 image2template_feature_11 / verification, the table of :570-586) ---------------------------
+def _ijbc_inputs(seed, n_img=1200, n_tpl=200, D=128, n_pairs=10000, n_subj=40):
+    """fp16-representable image features around one centre per subject, faceness in (0.5, 1], templates of 1 .. 20 images whose
+    medias are single images or multi-frame videos, pairs over the templates (label 1 = same subject)."""
+    rng = np.random.default_rng(seed)
+    subj_of_tpl = rng.integers(0, n_subj, n_tpl)
+    tpl_ids = np.sort(rng.choice(np.arange(100, 100000), n_tpl, replace=False))
+    templates = np.concatenate([np.arange(n_tpl), rng.integers(0, n_tpl, n_img - n_tpl)])
+    medias = np.zeros(n_img, dtype=np.int64)
+    for t in range(n_tpl):
+        rows = np.nonzero(templates == t)[0]
+        medias[rows] = 10 * tpl_ids[t] + rng.integers(0, max(1, len(rows) // 3), len(rows))   # some medias hold several frames
+    perm = rng.permutation(n_img)
+    templates, medias = templates[perm], medias[perm]
+    centers = rng.standard_normal((n_subj, D))
+    feats = (0.25 * centers[subj_of_tpl[templates]] + rng.standard_normal((n_img, D))).astype(np.float16)
+    face = rng.uniform(0.5, 1.0, n_img).astype(np.float16)
+    t1, t2 = rng.integers(0, n_tpl, n_pairs), rng.integers(0, n_tpl, n_pairs)
+    same = rng.random(n_pairs) < 0.1
+    for i in np.nonzero(same)[0]:                              # a tenth of the pairs: another template of the same subject
+        cand = np.nonzero(subj_of_tpl == subj_of_tpl[t1[i]])[0]
+        t2[i] = rng.choice(cand)
+    while np.any(t1 == t2):                                    # no self pairs: their scores all round to about 1.0
+        k = t1 == t2
+        t2[k] = rng.integers(0, n_tpl, int(k.sum()))
+    label = (subj_of_tpl[t1] == subj_of_tpl[t2]).astype(np.int64)
+    return feats, face, tpl_ids[templates], medias, tpl_ids[t1], tpl_ids[t2], label
+
+
+def gen_ijbc():
+    sys.modules["skimage"] = types.ModuleType("skimage")
+    sys.modules["skimage.transform"] = types.ModuleType("skimage.transform")
+    sys.modules["skimage"].transform = sys.modules["skimage.transform"]
+    from sklearn.metrics import roc_curve
+    import ijbc_all                                            # noqa: E402  (reference)
+    x_labels = [10 ** -6, 10 ** -5, 10 ** -4, 10 ** -3, 10 ** -2, 10 ** -1]
+    for seed in range(100):                                    # first seed whose distinct scores are > 1e-9 apart: no order can flip
+        feats, face, templates, medias, p1, p2, label = _ijbc_inputs(seed)
+        x = feats.astype(np.float32) * face.astype(np.float32)[:, np.newaxis]      # test mode N1 + D1 (:523-533)
+        with contextlib.redirect_stdout(io.StringIO()):
+            tf, uniq = ijbc_all.image2template_feature_11(x, templates, medias)
+            score = ijbc_all.verification(tf, uniq, p1, p2)
+        u = np.unique(score)
+        margin = np.min(np.diff(u))
+        if margin > 1e-9:
+            break
+    fpr, tpr, _ = roc_curve(label, score)                      # :578-585
+    fpr, tpr = np.flipud(fpr), np.flipud(tpr)
+    row = []
+    for xl in x_labels:
+        _, i = min(list(zip(abs(fpr - xl), range(len(fpr)))))
+        row.append(tpr[i])
+    save("ijbc", img_feats=feats, faceness=face, templates=templates.astype(np.int32), medias=medias.astype(np.int32),
+         p1=p1.astype(np.int32), p2=p2.astype(np.int32), label=label.astype(np.uint8), seed=seed, min_margin=margin,
+         template_feats=tf, unique_templates=uniq, score=score, x_labels=np.array(x_labels), tpr=np.array(row),
+         table=np.array(["%.2f" % (t * 100) for t in row]))
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["block", "r50", "r100", "heads", "bce", "sgd", "fedavg", "pfc", "client", "public", "mining", "roc", "sphnet", "sphnet64", "freeze_bn",
-                             "checkpoint", "ident_1n"]
+                             "checkpoint", "ident_1n", "ijbc"]
     if "checkpoint" in which:
         gen_checkpoint()
     if "freeze_bn" in which:
@@ -837,6 +897,8 @@ if __name__ == "__main__":
         gen_mining()
     if "ident_1n" in which:
         gen_ident_1n()
+    if "ijbc" in which:
+        gen_ijbc()
     if "public" in which:
         for v in ("full", "seq", "bce_rw"):
             gen_public(v)
