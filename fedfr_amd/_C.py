@@ -105,6 +105,8 @@ SIGNATURES = {
     "fedfr_roc_histogram": (i32, [vp, vp, i32, i32, i32, vp, vp]),
     "fedfr_ident_workspace_bytes": (sz, [i32, i32, i32]),
     "fedfr_ident_topk": (i32, [vp, vp, i32, vp, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, sz, vp]),
+    "fedfr_ident_rank_workspace_bytes": (sz, [i32, i32, i32]),
+    "fedfr_ident_rank_topk": (i32, [vp, i32, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, sz, vp, vp]),
     "fedfr_template_pool_workspace_bytes": (sz, [i32, i32]),
     "fedfr_template_pool": (i32, [vp, i32, i32, i32, vp, i32, vp, i32, vp, i32, vp, i32, i32, vp, vp, vp, sz, vp, vp]),
     "fedfr_roc_counts_workspace_bytes": (sz, [i64, i32]),

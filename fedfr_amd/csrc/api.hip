@@ -625,6 +625,12 @@ int fedfr_ident_topk(const float* query, const long long* qid, int Q, const floa
                      void* stream) {
   return ident_topk(query, qid, Q, gallery, gid, G, D, seg, S, K, pos, neg_topk, neg_count, ws, ws_bytes, ST(stream));
 }
+size_t fedfr_ident_rank_workspace_bytes(int Q, int G, int K) { return ident_rank_workspace_bytes(Q, G, K); }
+int fedfr_ident_rank_topk(const double* query, int Q, const double* gallery, int G, int D, const long long* mask, int K, double* pos,
+                          double* neg_topk, long long* neg_count, int* rank_gt, int* rank_eq, void* ws, size_t ws_bytes, int* status,
+                          void* stream) {
+  return ident_rank_topk(query, Q, gallery, G, D, mask, K, pos, neg_topk, neg_count, rank_gt, rank_eq, ws, ws_bytes, status, ST(stream));
+}
 size_t fedfr_template_pool_workspace_bytes(int N, int norm_images) { return ijbc_template_pool_workspace_bytes(N, norm_images); }
 int fedfr_template_pool(const float* feats, int N, int D, int flip, const float* faceness, int norm_images, const int* t_off, int T,
                         const int* m_off, int M, const int* img, int NI, int mode, float* raw, double* out, void* ws, size_t ws_bytes,

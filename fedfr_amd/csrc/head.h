@@ -43,6 +43,11 @@ size_t ident_workspace_bytes(int Q, int S, int K);
 int ident_topk(const float* query, const long long* qid, int Q, const float* gallery, const long long* gid, int G, int D,
                const long long* seg, int S, int K, double* pos, double* neg_topk, long long* neg_count, void* ws, size_t ws_bytes,
                hipStream_t st);
+// IJB-C job 1:N (ident64.hip): fp64 features, one gallery, K up to 4096, positive score + ranks per query
+size_t ident_rank_workspace_bytes(int Q, int G, int K);
+int ident_rank_topk(const double* query, int Q, const double* gallery, int G, int D, const long long* mask, int K, double* pos,
+                    double* neg_topk, long long* neg_count, int* rank_gt, int* rank_eq, void* ws, size_t ws_bytes, int* status,
+                    hipStream_t st);
 // IJB-C template evaluation (ijbc.hip): template pooling, pair scores fused with the ROC counts at the genuine scores
 size_t ijbc_template_pool_workspace_bytes(int N, int norm_images);
 int ijbc_template_pool(const float* feats, int N, int D, int flip, const float* face, int norm_images, const int* t_off, int T,

@@ -1,14 +1,20 @@
-"""IJB-C template evaluation, job 1:1 (reference ijbc_all.py, driven by ijbc_conti.py): everything after the forward pass.
+"""IJB-C template evaluation, jobs 1:1 and 1:N (reference ijbc_all.py, driven by ijbc_conti.py): everything after the forward pass.
 
-GPU part (``fedfr_amd/csrc/ijbc.hip``): template pooling in the reference's fp32 order with the fp64 normalisation
+GPU part of job 1:1 (``fedfr_amd/csrc/ijbc.hip``): template pooling in the reference's fp32 order with the fp64 normalisation
 (``fedfr_template_pool``), pair scores in numpy's summation order fused with the exact ROC counts at the genuine scores
 (``fedfr_pair_scores_roc``).  The TPR@FPR table is read out on the host from those counts with the float operations of
 ``sklearn.metrics.roc_curve`` and the reference's nearest-FPR pick (:570-586), so no sort of the scores is needed.
 
-Not ported: face alignment (cv2 / skimage ``warpAffine``), the embedding loop and the 1:N template job (its ``evaluation`` needs an
-fp64, K > 1024 form of the identification kernel).  ``template_pool(mode=1)`` already gives the 1:N template features, bit for bit."""
+Job 1:N (:261-298, 356-427, 592-627): ``template_pool(mode=1)`` gives the gallery and probe template features bit for bit, and
+``fedfr_ident_rank_topk`` (``fedfr_amd/csrc/ident64.hip``) scores probes x gallery in fp64 without writing the matrix: per probe the score
+of its own gallery row and the number of other rows that score higher (top-1 / 5 / 10), over all probes the exact top-K negatives
+(TPIR at FAR 0.01 and 0.1).  Scores are summed in another order than the reference's BLAS ``np.dot``, so a comparison decided within
+about D * 2^-52 can fall the other way; exact ties are reported (``evaluation(..., return_ties=True)``).
+
+Not ported: face alignment (cv2 / skimage ``warpAffine``) and the embedding loop."""
 from __future__ import annotations
 
+import math
 from typing import Callable, Dict, Sequence, Tuple
 
 import numpy as np
@@ -17,6 +23,8 @@ import torch
 from . import _C
 
 X_LABELS = (1e-6, 1e-5, 1e-4, 1e-3, 1e-2, 1e-1)
+FARS_1N = (0.01, 0.1)           # ijbc_all.py:368
+MAX_K_1N = 4096                 # fedfr_ident_rank_topk's limit on K (include/fedfr_hip.h)
 
 
 # ---- meta lists of job 1:1 (ijbc_all.py:119-134, without the removed np.int) ---------------------------------------------------------------------
@@ -40,6 +48,11 @@ def read_template_media_list(path):
 def read_template_pair_list(path):
     """``ijbc_template_pair_label.txt`` (``t1 t2 label`` per pair): t1, t2, label."""
     return _read_columns(path, (0, 1, 2))
+
+
+def read_template_subject_id_list(path):
+    """``ijbc_1N_gallery_G1.csv`` / ``..._probe_mixed.csv`` (a header row, then ``template_id,subject_id,...``): templates, subject ids."""
+    return _read_columns(path, (0, 1), sep=",", skiprows=1)
 
 
 # ---- template pooling ----------------------------------------------------------------------------------------------------------
@@ -333,6 +346,134 @@ def ijbc_11(img_feats, templates, medias, p1, p2, label, faceness=None, use_norm
     lab = _gpu(label, torch.int64, "label").reshape(-1)
     tprs = table_from_counts(gv, counts, x_labels, _impostor_fetch(score, lab))
     return {"score": score, "tpr": tprs, "table": format_table(tprs)}
+
+
+# ---- job 1:N -------------------------------------------------------------------------------------------------------------------
+def unique_template_ids(choose_templates, choose_ids):
+    """ijbc_all.py:271-272: the sorted distinct template ids of a gallery / probe list and the subject id of each (its first listing)."""
+    choose_templates = _host(choose_templates, np.int64).reshape(-1)
+    choose_ids = _host(choose_ids).reshape(-1)
+    if choose_templates.shape != choose_ids.shape:
+        raise ValueError("unique_template_ids: choose_templates and choose_ids must have one entry per listed template")
+    uniq, first = np.unique(choose_templates, return_index=True)
+    return uniq, choose_ids[first]
+
+
+def image2template_feature_1n(img_feats=None, templates=None, medias=None, choose_templates=None, choose_ids=None, on_gpu: bool = False,
+                              **pool_args):
+    """Drop-in for ijbc_all.image2template_feature_1n: (template_norm_feats [T, D] fp64, unique_templates, unique_subjectids) of the
+    templates named in ``choose_templates``.  ``on_gpu=True`` leaves the features on the device (a torch tensor) instead of returning
+    numpy; ``pool_args`` go to ``template_pool`` (faceness, flip, norm_images)."""
+    uniq, ids = unique_template_ids(choose_templates, choose_ids)
+    feats, _ = template_pool(img_feats, templates, medias, choose_templates=choose_templates, mode=1, **pool_args)
+    return (feats if on_gpu else feats.cpu().numpy()), uniq, ids
+
+
+def gen_mask(query_ids, reg_ids):
+    """Drop-in for ijbc_all.gen_mask (vectorised; an int64 array instead of a list): the gallery row of every query id.  RuntimeError when
+    a query id matches no gallery id or several."""
+    q, r = _host(query_ids).reshape(-1), _host(reg_ids).reshape(-1)
+    order = np.argsort(r, kind="stable")
+    rs = r[order]
+    lo = np.searchsorted(rs, q, side="left")
+    cnt = np.searchsorted(rs, q, side="right") - lo
+    bad = np.nonzero(cnt != 1)[0]
+    if bad.size:
+        raise RuntimeError("RegIdsError with id = {}, duplicate = {} ".format(q[bad[0]], cnt[bad[0]]))
+    return order[lo].astype(np.int64)
+
+
+@torch.no_grad()
+def identification_rank_topk(query: torch.Tensor, gallery: torch.Tensor, mask: torch.Tensor, K: int):
+    """fp64 scores <query[q], gallery[c]> of every pair, never stored.  ``query`` [Q, D] / ``gallery`` [G, D] fp64 and ``mask`` [Q] int64
+    (the gallery row of the query's identity, or -1) on the GPU, 1 <= K <= MAX_K_1N.  Returns ``pos`` [Q] fp64 (NaN where mask is -1),
+    ``neg_topk`` [K] fp64 (the K largest scores of the pairs c != mask[q], duplicates counted, descending, -inf past ``neg_count``),
+    ``neg_count`` (0-dim int64), ``rank_gt`` / ``rank_eq`` [Q] int32: the number of columns c != mask[q] that score higher than / equal
+    to pos[q] (-1 where mask is -1).  ValueError on a non-finite score (a NaN / inf feature)."""
+    query = _C.require_gpu_tensor(query.contiguous(), torch.float64, "query")
+    gallery = _C.require_gpu_tensor(gallery.contiguous(), torch.float64, "gallery")
+    mask = _C.require_gpu_tensor(mask.contiguous(), torch.int64, "mask")
+    if query.dim() != 2 or gallery.dim() != 2 or query.shape[1] != gallery.shape[1]:
+        raise ValueError("identification_rank_topk: query [Q, D] and gallery [G, D] must share D (got %s, %s)"
+                         % (tuple(query.shape), tuple(gallery.shape)))
+    Q, D = query.shape
+    G = gallery.shape[0]
+    if tuple(mask.shape) != (Q,):
+        raise ValueError("identification_rank_topk: mask must be [Q] (got %s for Q = %d)" % (tuple(mask.shape), Q))
+    K = int(K)
+    if not 1 <= K <= MAX_K_1N:
+        raise ValueError("identification_rank_topk: K = %d outside [1, %d]" % (K, MAX_K_1N))
+    dev = query.device
+    pos = torch.empty(Q, dtype=torch.float64, device=dev)
+    neg_topk = torch.empty(K, dtype=torch.float64, device=dev)
+    neg_count = torch.empty((), dtype=torch.int64, device=dev)
+    rank_gt = torch.empty(Q, dtype=torch.int32, device=dev)
+    rank_eq = torch.empty(Q, dtype=torch.int32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    ws = torch.empty(int(_C.lib().fedfr_ident_rank_workspace_bytes(Q, G, K)), dtype=torch.uint8, device=dev)
+    _C.call("fedfr_ident_rank_topk", query.data_ptr(), Q, gallery.data_ptr(), G, D, mask.data_ptr(), K, pos.data_ptr(),
+            neg_topk.data_ptr(), neg_count.data_ptr(), rank_gt.data_ptr(), rank_eq.data_ptr(), ws.data_ptr(), ws.numel(),
+            status.data_ptr(), _C.stream(query))
+    s = int(status.item())
+    if s & 2:
+        raise ValueError("identification_rank_topk: mask entries must be -1 or a gallery row in [0, %d)" % G)
+    if s & 1:
+        raise ValueError("identification_rank_topk: scores must be finite (a feature is NaN or inf)")
+    return pos, neg_topk, neg_count, rank_gt, rank_eq
+
+
+def _evaluate_1n(query_feats, gallery_feats, mask, fars):
+    query = _gpu(query_feats, torch.float64, "query_feats")
+    gallery = _gpu(gallery_feats, torch.float64, "gallery_feats")
+    if query.dim() != 2 or gallery.dim() != 2:
+        raise ValueError("evaluation: query_feats [Q, D] and gallery_feats [G, D] expected")
+    Q, G = query.shape[0], gallery.shape[0]
+    m = _host(mask, np.int64).reshape(-1)
+    if m.shape[0] != Q:
+        raise ValueError("evaluation: mask has %d entries for %d queries" % (m.shape[0], Q))
+    if np.any((m < -1) | (m >= G)):
+        raise ValueError("evaluation: mask entries must be -1 or a gallery row in [0, %d)" % G)
+    need = [math.ceil(Q * x) for x in fars]                     # :406, Q counts every query
+    K = max(need)
+    negatives = Q * G - int(np.sum(m >= 0))
+    if K < 1 or negatives < K:
+        raise ValueError("evaluation: %d negative pairs but the threshold at the largest FAR needs the %d-th largest (the reference "
+                         "raises IndexError here)" % (negatives, K))
+    if K > MAX_K_1N:
+        raise ValueError("evaluation: ceil(Q * far) = %d exceeds the kernel's K limit %d" % (K, MAX_K_1N))
+    pos, neg, _, rank_gt, rank_eq = identification_rank_topk(query, gallery, torch.from_numpy(m).to(query.device), K)
+    pos, neg, rank_gt, rank_eq = pos.cpu().numpy(), neg.cpu().numpy(), rank_gt.cpu().numpy(), rank_eq.cpu().numpy()
+    rank = {"top%d" % k: int(np.sum((rank_gt >= 0) & (rank_gt < k))) / Q for k in (1, 5, 10)}
+    th = {far: float(neg[k - 1]) for far, k in zip(fars, need)}
+    pr = {far: int(np.sum(pos > th[far])) / Q for far in fars}  # NaN (no positive) never counts
+    return rank, pr, th, int(np.sum(rank_eq > 0))
+
+
+def evaluation(query_feats, gallery_feats, mask, fars: Sequence[float] = FARS_1N, return_ties: bool = False):
+    """Drop-in for ijbc_all.evaluation: query [Q, D], gallery [G, D] (numpy, or torch tensors on the GPU; used in fp64), ``mask`` [Q] =
+    the gallery row of each query's identity (or -1: never a hit).  Returns (rank, pr): rank = {'top1', 'top5', 'top10'} (query i is a
+    top-k hit iff fewer than k other gallery rows score strictly higher than its own), pr = {far: rate of own-row scores above the
+    ceil(Q * far)-th largest negative}.  Where a query's own score ties another row's exactly, the reference's argsort order is
+    unspecified; ``return_ties=True`` adds the number of such queries as a third value."""
+    rank, pr, _, ties = _evaluate_1n(query_feats, gallery_feats, mask, tuple(fars))
+    return (rank, pr, ties) if return_ties else (rank, pr)
+
+
+def ijbc_1n(img_feats, templates, medias, gallery_templates, gallery_ids, probe_templates, probe_ids, faceness=None,
+            use_norm_score: bool = True, use_detector_score: bool = True, use_flip_test: bool = False,
+            fars: Sequence[float] = FARS_1N) -> Dict[str, object]:
+    """Job 1:N of ijbc_all.py after the embeddings (:515-533, 592-627): gallery (G1 + G2 lists concatenated) and probe template
+    features, gen_mask and evaluation, the features staying on the device.  Returns dict(rank, pr, th = {far: threshold}, ties = queries
+    whose own score ties another row's, lines = what the reference appends to log.txt after the epoch line)."""
+    if use_detector_score and faceness is None:
+        raise ValueError("ijbc_1n: use_detector_score needs the faceness scores")
+    pool = dict(faceness=faceness if use_detector_score else None, flip=use_flip_test, norm_images=not use_norm_score, on_gpu=True)
+    feats = _gpu(img_feats, torch.float32, "img_feats")
+    gallery, _, gids = image2template_feature_1n(feats, templates, medias, gallery_templates, gallery_ids, **pool)
+    probe, _, pids = image2template_feature_1n(feats, templates, medias, probe_templates, probe_ids, **pool)
+    rank, pr, th, ties = _evaluate_1n(probe, gallery, gen_mask(pids, gids), tuple(fars))
+    lines = ["%s : %.5f" % (r, rank[r]) for r in rank] + ["far = %.4f  pr = %.5f" % (far, pr[far]) for far in pr]
+    return {"rank": rank, "pr": pr, "th": th, "ties": ties, "lines": lines}
 
 
 # ---- test oracle --------------------------------------------------------------------------------------------------------------

@@ -344,6 +344,21 @@ size_t fedfr_ident_workspace_bytes(int Q, int S, int K);
 int fedfr_ident_topk(const float* query, const long long* qid, int Q, const float* gallery, const long long* gid, int G, int D,
                      const long long* seg, int S, int K, double* pos, double* neg_topk, long long* neg_count, void* ws, size_t ws_bytes,
                      void* stream);
+/* IJB-C job 1:N (ijbc_all.py:367-427 evaluation): the fp64 form of the kernel above for one gallery, with ranks.  query [Q][D] and
+ * gallery [G][D] fp64, mask[Q] int64 = the gallery row of the query's identity or -1 (all device memory).  Scores are
+ * v_mfma_f64_16x16x4_f64 products accumulated over ascending k: for fp32-representable features the same fp64 numbers as
+ * fedfr_ident_topk.  Outputs: pos[Q] fp64 = score of (q, mask[q]), NaN where mask[q] == -1; neg_topk[K] fp64 = the K largest scores of
+ * the pairs (q, c != mask[q]), duplicates counted, descending, -inf past neg_count; neg_count int64; rank_gt[Q] / rank_eq[Q] int32 = the
+ * number of columns c != mask[q] whose score is greater than / equal to pos[q] (-1 where mask[q] == -1), taken on the kernel's own
+ * scores in a second sweep: query q is a top-k hit iff rank_gt[q] < k, and rank_eq[q] > 0 says that the answer depends on a tie.
+ * 1 <= K <= 4096.  The matrix is never materialised; results are exact and run-to-run identical.  The device word *status (zero it
+ * first) gets bit 1 when a score is not finite (a NaN / inf feature: the outputs are then unspecified; the reference drops NaN negatives
+ * silently, callers here must refuse) and bit 2 when a mask entry lies outside [-1, G) (the entry is treated as -1).
+ * ws: fedfr_ident_rank_workspace_bytes(Q, G, K) bytes of device memory. */
+size_t fedfr_ident_rank_workspace_bytes(int Q, int G, int K);
+int fedfr_ident_rank_topk(const double* query, int Q, const double* gallery, int G, int D, const long long* mask, int K, double* pos,
+                          double* neg_topk, long long* neg_count, int* rank_gt, int* rank_eq, void* ws, size_t ws_bytes, int* status,
+                          void* stream);
 /* IJB-C template evaluation (ijbc_all.py image2template_feature_11/_1n, verification and the TPR@FPR table).
  * fedfr_template_pool: image features feats [N][D] fp32, or [N][2D] with flip = 1 (the two halves added, test mode F1); optional
  * faceness [N] (D1: an fp32 multiply); norm_images = 1 divides every image by its fp32 L2 norm first (use_norm_score=False; needs

@@ -19,6 +19,7 @@ What is captured (reference symbol → fixture):
   eval-mode embedding sweeps, class centres and feature-based hard-negative mining → mining_r18.npz
   the train_with_public_data loop body (Branch_model + BCE + contrastive; Sequential + reweight) → client_public_{full,seq}.npz
   local_all.combine_features / evaluation (the --task 1:n client loop) → ident_1n.npz
+  ijbc_all.image2template_feature_1n / gen_mask / evaluation (job 1:N) → ijbc_1n.npz
 """
 import os
 import sys
@@ -862,9 +863,80 @@ def gen_ijbc():
          table=np.array(["%.2f" % (t * 100) for t in row]))
 
 
+# ---- 14. IJB-C job 1:N (ijbc_all.py:261-298 image2template_feature_1n, :356-427 gen_mask / evaluation) ------------------------------
+def _ijbc_1n_inputs(seed, n_img=2200, n_gal=200, n_probe=900, D=64, scale=0.75):
+    """fp16-representable image features (multiples of 1/8) around one centre per subject.  One gallery template per subject, listed in
+    two halves (G1, G2); every probe template belongs to a gallery subject.  Templates of 1 .. a few images, medias as in _ijbc_inputs."""
+    rng = np.random.default_rng(seed)
+    n_tpl = n_gal + n_probe
+    subj_of_tpl = np.concatenate([rng.permutation(n_gal), rng.integers(0, n_gal, n_probe)])
+    subj_ids = np.sort(rng.choice(np.arange(1000, 50000), n_gal, replace=False))
+    tpl_ids = rng.permutation(np.sort(rng.choice(np.arange(100, 100000), n_tpl, replace=False)))   # template ids in no order
+    templates = np.concatenate([np.arange(n_tpl), rng.integers(0, n_tpl, n_img - n_tpl)])
+    medias = np.zeros(n_img, dtype=np.int64)
+    for t in range(n_tpl):
+        rows = np.nonzero(templates == t)[0]
+        medias[rows] = 10 * tpl_ids[t] + rng.integers(0, max(1, len(rows) // 2), len(rows))       # some medias hold several frames
+    perm = rng.permutation(n_img)
+    templates, medias = templates[perm], medias[perm]
+    centers = rng.standard_normal((n_gal, D))
+    feats = scale * centers[subj_of_tpl[templates]] + rng.standard_normal((n_img, D))
+    feats = (np.clip(np.round(feats * 8), -127, 127) / 8).astype(np.float16)
+    face = rng.uniform(0.5, 1.0, n_img).astype(np.float16)
+    gal, probe = np.arange(n_gal), np.arange(n_gal, n_tpl)
+    return (feats, face, tpl_ids[templates], medias, tpl_ids[gal], subj_ids[subj_of_tpl[gal]], tpl_ids[probe],
+            subj_ids[subj_of_tpl[probe]])
+
+
+def gen_ijbc_1n():
+    import heapq
+    import math
+    sys.modules["skimage"] = types.ModuleType("skimage")
+    sys.modules["skimage.transform"] = types.ModuleType("skimage.transform")
+    sys.modules["skimage"].transform = sys.modules["skimage.transform"]
+    import ijbc_all                                            # noqa: E402  (reference)
+    kept = {}
+
+    def nlargest(n, it):                                       # evaluation prints its thresholds to 10 digits only: keep its sorted negatives
+        kept["neg"] = heapq.nlargest(n, it)
+        return kept["neg"]
+    ijbc_all.heapq = types.SimpleNamespace(nlargest=nlargest)
+    fars = [0.01, 0.1]
+    for seed in range(100):                                    # first seed with no comparison decided within 1e-9 (the rule of gen_ijbc)
+        feats, face, templates, medias, gt, gi, pt, pi = _ijbc_1n_inputs(seed)
+        x = feats.astype(np.float32) * face.astype(np.float32)[:, np.newaxis]      # test mode N1 + D1 (:523-533)
+        half = len(gt) // 2                                    # the G1 and G2 lists, concatenated as :481-484 does
+        gallery_templates, gallery_ids = np.concatenate([gt[:half], gt[half:]]), np.concatenate([gi[:half], gi[half:]])
+        with contextlib.redirect_stdout(io.StringIO()):
+            gf, gu, gids = ijbc_all.image2template_feature_1n(x, templates, medias, gallery_templates, gallery_ids)
+            pf, pu, pids = ijbc_all.image2template_feature_1n(x, templates, medias, pt, pi)
+            mask = np.array(ijbc_all.gen_mask(pids, gids), dtype=np.int64)
+            rank, pr = ijbc_all.evaluation(pf, gf, mask)
+        Q = len(mask)
+        need = [math.ceil(Q * f) for f in fars]
+        th = np.array([kept["neg"][k - 1] for k in need])
+        sim = np.dot(pf, gf.T)
+        pos = sim[np.arange(Q), mask]
+        other = np.ones(sim.shape, dtype=bool)
+        other[np.arange(Q), mask] = False
+        neg = np.sort(sim[other])[::-1]
+        assert np.array_equal(neg[:max(need)], np.array(kept["neg"]))
+        margin = min(np.min(np.abs(sim - pos[:, None])[other]), np.min(np.abs(pos[:, None] - th[None, :])),
+                     min(min(neg[k - 2] - neg[k - 1], neg[k - 1] - neg[k]) for k in need))
+        if margin > 1e-9 and 0.0 < rank["top1"] < 1.0:
+            break
+    save("ijbc_1n", img_feats=feats, faceness=face, templates=templates.astype(np.int32), medias=medias.astype(np.int32),
+         gallery_s1_templates=gt[:half].astype(np.int32), gallery_s1_ids=gi[:half].astype(np.int32),
+         gallery_s2_templates=gt[half:].astype(np.int32), gallery_s2_ids=gi[half:].astype(np.int32),
+         probe_templates=pt.astype(np.int32), probe_ids=pi.astype(np.int32), seed=seed, min_margin=margin,
+         gallery_feats=gf, gallery_unique_templates=gu, gallery_unique_ids=gids, probe_feats=pf, probe_unique_templates=pu,
+         probe_unique_ids=pids, mask=mask, fars=np.array(fars), rank=np.array([rank["top1"], rank["top5"], rank["top10"]]),
+         pr=np.array([pr[f] for f in fars]), th=th)
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["block", "r50", "r100", "heads", "bce", "sgd", "fedavg", "pfc", "client", "public", "mining", "roc", "sphnet", "sphnet64", "freeze_bn",
-                             "checkpoint", "ident_1n", "ijbc"]
+                             "checkpoint", "ident_1n", "ijbc", "ijbc_1n"]
     if "checkpoint" in which:
         gen_checkpoint()
     if "freeze_bn" in which:
@@ -899,6 +971,8 @@ if __name__ == "__main__":
         gen_ident_1n()
     if "ijbc" in which:
         gen_ijbc()
+    if "ijbc_1n" in which:
+        gen_ijbc_1n()
     if "public" in which:
         for v in ("full", "seq", "bce_rw"):
             gen_public(v)
