@@ -112,6 +112,8 @@ SIGNATURES = {
     "fedfr_roc_counts_workspace_bytes": (sz, [i64, i32]),
     "fedfr_pair_scores_roc": (i32, [vp, i32, i32, vp, i64, vp, vp, i64, vp, vp, vp, i32, vp, vp, sz, vp, vp]),
     "fedfr_roc_counts": (i32, [vp, vp, i64, vp, i32, vp, vp, sz, vp, vp]),
+    "fedfr_spreadout_workspace_bytes": (sz, [i32, i32]),
+    "fedfr_spreadout_grad": (i32, [vp, i32, i32, f32, i32, vp, vp, vp, vp, sz, vp]),
     "fedfr_contrastive": (i32, [vp, vp, vp, i32, i32, f32, vp, vp, vp]),
     "fedfr_sum_scale": (i32, [vp, i32, f32, vp, vp]),
     "fedfr_sgd_step": (i32, [vp, vp, vp, vp, sz, f32, f32, f32, i32, vp]),

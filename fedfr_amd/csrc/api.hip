@@ -648,6 +648,11 @@ int fedfr_roc_counts(const double* score, const long long* label, long long P, c
                      void* ws, size_t ws_bytes, int* status, void* stream) {
   return ijbc_roc_counts(score, label, P, genuine, G, counts, ws, ws_bytes, status, ST(stream));
 }
+size_t fedfr_spreadout_workspace_bytes(int N, int D) { return spreadout_workspace_bytes(N, D); }
+int fedfr_spreadout_grad(const float* fn, int N, int D, float margin, int mean, float* dfn, float* loss, long long* active, void* ws,
+                         size_t ws_bytes, void* stream) {
+  return spreadout_grad(fn, N, D, margin, mean, dfn, loss, active, ws, ws_bytes, ST(stream));
+}
 int fedfr_bias_prelu_bwd(const uint16_t* dy, const uint16_t* x, const float* bias, const float* alpha, int M, int C, float* partials,
                          float* coef, float* dbias, float* dalpha, const uint16_t* add, uint16_t* dx, void* stream) {
   return ew_bias_prelu_bwd(BF(dy), BF(x), bias, alpha, M, C, partials, coef, dbias, dalpha, BF(add), BFM(dx), ST(stream));

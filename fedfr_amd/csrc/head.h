@@ -59,3 +59,7 @@ int ijbc_pair_scores_roc(const double* feats, int T, int D, const int* lut, long
                          size_t ws_bytes, int* status, hipStream_t st);
 int ijbc_roc_counts(const double* score, const long long* label, long long P, const double* gv, int G, unsigned long long* counts, void* ws,
                     size_t ws_bytes, int* status, hipStream_t st);
+// spread-out regulariser of the class centres (spreadout.hip): loss and d(loss)/d(Fn) in one pass, the N x N matrix never written
+size_t spreadout_workspace_bytes(int N, int D);
+int spreadout_grad(const float* fn, int N, int D, float margin, int mean, float* dfn, float* loss, long long* active, void* ws, size_t ws_bytes,
+                   hipStream_t st);

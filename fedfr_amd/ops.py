@@ -227,6 +227,34 @@ def sgd_step(param: torch.Tensor, grad: torch.Tensor, mom: torch.Tensor, shadow:
         _C.call("fedfr_sgd_step", param.data_ptr(), grad.data_ptr(), mom.data_ptr(), sh, n, lr, mu, wd, 1 if first else 0, _C.stream())
 
 
+def _need(t: torch.Tensor, name: str, fn: str, dtype=f32) -> torch.Tensor:
+    """``require_gpu_tensor`` without the silent ``.contiguous()`` copy of ``_chk``, the error prefixed with the entry point's name."""
+    try:
+        return _C.require_gpu_tensor(t, dtype, name)
+    except RuntimeError as e:
+        raise RuntimeError("%s: %s" % (fn, e)) from None
+
+
+@torch.no_grad()
+def spreadout_loss_grad(fn: torch.Tensor, margin: float, mean: bool):
+    """Spread-out loss of row-normalised class centres ``fn`` [N, D] and its gradient (reference server.py:48-63 and its backward):
+    H = relu(fn @ fn.T - margin) off the diagonal, loss = c * sum(H ** 2), dfn = 4 c * H @ fn, c = 1 or 1 / (N (N - 1)) (``mean``).
+    One fused HIP pass (csrc/spreadout.hip): neither fn @ fn.T nor H exists in memory.  Returns (loss scalar, dfn [N, D], active =
+    int64 scalar, the number of ordered pairs above the margin), all on the device."""
+    fn = _need(fn, "fn", "spreadout_loss_grad")
+    if fn.dim() != 2:
+        raise RuntimeError("spreadout_loss_grad: fn must be [N, D]")
+    N, D = fn.shape
+    dfn = torch.empty_like(fn)
+    loss = torch.empty((), dtype=f32, device=fn.device)
+    active = torch.empty((), dtype=torch.int64, device=fn.device)
+    nbytes = _C.lib().fedfr_spreadout_workspace_bytes(N, D)
+    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=fn.device)
+    _C.call("fedfr_spreadout_grad", fn.data_ptr(), N, D, float(margin), 1 if mean else 0, dfn.data_ptr(), loss.data_ptr(), active.data_ptr(),
+            ws.data_ptr(), nbytes, _C.stream())
+    return loss, dfn, active
+
+
 # ------------------------------------------------------------------------------------------ autograd bridges
 class CosineLinearFn(torch.autograd.Function):
     """normalize(x) @ normalize(w).T  (reference FC_module.forward, client.py:69-74)."""
@@ -321,6 +349,24 @@ class ContrastiveFn(torch.autograd.Function):
     def backward(ctx, dl):
         (dx,) = ctx.saved_tensors
         return dx * dl, None, None, None
+
+
+class SpreadOutFn(torch.autograd.Function):
+    """spread-out loss of unnormalised class centres ``fc`` [N, D]: normalise -> fused loss + gradient kernel -> normalise backward, all in
+    ``forward`` (the gradient costs nothing extra there); ``backward`` scales the saved d(loss)/d(fc)."""
+
+    @staticmethod
+    def forward(ctx, fc, margin, mean):
+        x = _need(fc.detach(), "FC", "SpreadOutFn")
+        fn, inv = normalize_rows(x)
+        loss, dfn, _ = spreadout_loss_grad(fn, margin, mean)
+        ctx.save_for_backward(normalize_rows_bwd(fn, inv, dfn))
+        return loss
+
+    @staticmethod
+    def backward(ctx, dl):
+        (dfc,) = ctx.saved_tensors
+        return dfc * dl, None, None
 
 
 def contrastive_loss(feats, global_feats, last_feats, temperature=0.5):

@@ -1,6 +1,7 @@
 """Server side of the federated loop (reference server.py:25-46, :265-338): dataset-size-weighted
 averaging of client models, as HIP kernels over flat buffers (single process) or one RCCL all-reduce over
-xGMI when every client is its own rank (one client = one MI355X)."""
+xGMI when every client is its own rank (one client = one MI355X); and the spread-out step on the clients' class centres
+(reference server.py:48-63, :340-371) on one fused HIP kernel."""
 from __future__ import annotations
 
 import copy
@@ -148,6 +149,31 @@ def fedavg_all_reduce(backbone, data_size: float, total_size: float, comm=None, 
     return w
 
 
+def _spreadout_mean(mode) -> bool:
+    if mode not in ("sum", "mean"):
+        # the reference leaves the unreduced vector in `loss` for any other mode and fails later, in backward()
+        raise ValueError("SpreadOut: mode must be 'sum' or 'mean' (got %r)" % (mode,))
+    return mode == "mean"
+
+
+class SpreadOut_Module(torch.nn.Module):
+    """reference server.py:48-63: the Parameter ``FC`` [N, D] and ``forward()`` = sum ('sum') or mean ('mean') over the N (N - 1)
+    off-diagonal pairs of relu(cos(FC_i, FC_j) - margin) ** 2.  ``loss.backward()`` and ``torch.optim.SGD`` work on it as on the
+    reference's module; the loss and its gradient come from one fused HIP pass (``ops.SpreadOutFn``) that never holds the N x N cosine
+    matrix.  ``local`` is unused, as in the reference."""
+
+    def __init__(self, all_FC, margin=0.7, local=False, mode='sum'):
+        super().__init__()
+        _spreadout_mean(mode)
+        self.FC = torch.nn.Parameter(all_FC)
+        self.margin = margin
+        self.mode = mode
+
+    def forward(self):
+        from .ops import SpreadOutFn
+        return SpreadOutFn.apply(self.FC, float(self.margin), _spreadout_mean(self.mode))
+
+
 class Server(object):
     """Round driver (reference server.py:68-133, :265-338): clients are trained sequentially in one process (as the
     reference does, server.py:283) and averaged with ``FedPavg``; with ``args.add_pretrained_data`` every client trains on
@@ -288,6 +314,37 @@ class Server(object):
             self.federated_model.load_state_dict(aggr_state_dict)
         # the round / epoch counters belong to the driver, as in the reference (train.py:87-88): call step_round() after train()
         return self.avg_loss
+
+    @torch.no_grad()
+    @_C.on_device(lambda self: self.device)
+    def SpreadOut(self, sp_iter=5, mode='sum'):
+        """reference server.py:340-371: the class centres of the round's clients, stacked in ``current_client_list`` order, take ``sp_iter``
+        SGD steps (lr = 10 cfg.lr, momentum 0.9, cfg.weight_decay) on the spread-out loss at margin 0.4 and go back to the clients.
+        Per iteration: normalise -> fused loss + gradient kernel -> normalise backward -> SGD kernel, no autograd graph, one host read
+        for the logged loss (the reference's ``loss.item()``).  Every client gets an independent tensor on the device and in the dtype its
+        ``fc`` had.  The reference slices the result at ``idx * num_classes``, which is right only while all clients hold the same number
+        of classes; the slices here follow running offsets, identical in that case."""
+        from . import ops
+        from .config import config as cfg
+        assert self.current_client_list is not None
+        mean = _spreadout_mean(mode)
+        fcs = [self.clients[i].fc_module.fc.data for i in self.current_client_list]
+        FC = torch.cat([t.detach().to(device=self.device, dtype=f32) for t in fcs], dim=0).contiguous()
+        self.logger.info('=====Collect FC and cat to a big matrix=====')
+        mom = torch.empty_like(FC)
+        lr, wd = float(cfg.lr) * 10, float(cfg.weight_decay)
+        self.logger.info('=====SpreadOut Module Create=====')
+        for it in range(sp_iter):
+            fn, inv = ops.normalize_rows(FC)
+            loss, dfn, _ = ops.spreadout_loss_grad(fn, 0.4, mean)
+            self.logger.info('- SP iter %d Loss :  %.5e , Start backward' % (it, loss.item()))
+            ops.sgd_step(FC, ops.normalize_rows_bwd(fn, inv, dfn), mom, None, FC.numel(), lr, 0.9, wd, it == 0)
+        o = 0
+        for i, old in zip(self.current_client_list, fcs):
+            n = old.shape[0]
+            self.clients[i].fc_module.fc.data = FC[o:o + n].to(device=old.device, dtype=old.dtype, copy=True)
+            o += n
+        self.logger.info('=====Update FC in partial FC module=====')
 
     def step_round(self):
         """What the reference driver does after every ``server.train()`` (train.py:87-88)."""

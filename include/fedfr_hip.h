@@ -386,6 +386,17 @@ int fedfr_pair_scores_roc(const double* feats, int T, int D, const int* lut, lon
                           void* ws, size_t ws_bytes, int* status, void* stream);
 int fedfr_roc_counts(const double* score, const long long* label, long long P, const double* genuine, int G, unsigned long long* counts,
                      void* ws, size_t ws_bytes, int* status, void* stream);
+/* Spread-out regulariser of the class centres (server.py:48-63 SpreadOut_Module.forward and its autograd backward) on row-normalised
+ * fn [N][D] fp32: S = fn fn^T, H_ij = max(S_ij - margin, 0) for i != j, H_ii = 0, c = 1 (mean = 0) or 1 / (N (N - 1)) (mean = 1):
+ *   *loss = c * sum_ij H_ij^2 (summed in fp64),   dfn [N][D] = d(loss)/d(fn) = 4c * H fn   (H is symmetric: dS + dS^T = 2 dS),
+ *   *active (optional) = the number of ordered pairs i != j with S_ij > margin.
+ * d(loss)/d(FC) of the unnormalised centres is fedfr_normalize_rows_bwd of dfn.  S is an exact-fp32 MFMA product (k ascending) that is
+ * never written to memory; every dfn row has one owner that adds the column tiles in ascending order and there are no floating-point
+ * atomics, so two calls on the same input give the same bits.  N >= 2, D a multiple of 4 in [4, 1024]; fn and dfn must not overlap.
+ * ws: fedfr_spreadout_workspace_bytes(N, D) bytes of device memory (O(N); 0 for unsupported sizes). */
+size_t fedfr_spreadout_workspace_bytes(int N, int D);
+int fedfr_spreadout_grad(const float* fn, int N, int D, float margin, int mean, float* dfn, float* loss, long long* active, void* ws,
+                         size_t ws_bytes, void* stream);
 /* model-contrastive term (client.py:372-375, :415-418): row_loss[b] = CE([cos(x,g)/T, cos(x,l)/T], 0) with
  * nn.CosineSimilarity(dim=1, eps=1e-8); dx = d(mean_b row_loss)/dx (optional).  g, l: frozen global / last-round embeddings. */
 int fedfr_contrastive(const float* feats, const float* global_feats, const float* last_feats, int B, int D, float temperature,

@@ -20,6 +20,7 @@ What is captured (reference symbol → fixture):
   the train_with_public_data loop body (Branch_model + BCE + contrastive; Sequential + reweight) → client_public_{full,seq}.npz
   local_all.combine_features / evaluation (the --task 1:n client loop) → ident_1n.npz
   ijbc_all.image2template_feature_1n / gen_mask / evaluation (job 1:N) → ijbc_1n.npz
+  server.SpreadOut_Module + torch.optim.SGD driven as Server.SpreadOut does (server.py:340-371) → spreadout.npz
 """
 import os
 import sys
@@ -934,9 +935,92 @@ def gen_ijbc_1n():
          pr=np.array([pr[f] for f in fars]), th=th)
 
 
+# ---- 15. spread-out regulariser (server.py:48-63 SpreadOut_Module, the loop of Server.SpreadOut :340-371) ------------------------------
+SPREADOUT_GEN = dict(amp=0.01, a=0.371, b=0.11, c=1.7, every=3, w0=0.5, w1=0.45)
+SPREADOUT_CASES = (  # name, clients, ids per client, D, mode, iterations, cfg.lr (the loop uses 10 x), rows stored
+    # (first gradient and final FC of the 512-wide cases, first gradient of the 128-wide ones, whose final FC is stored whole: four whole
+    # 480 x 128 tensors plus the wide rows would pass the size limit of a committed file; the per-row norms cover every row)
+    ("s_mean", 6, 80, 128, "mean", 20, 0.1, 64), ("s_sum", 6, 80, 128, "sum", 5, 0.001, 64),
+    ("l_mean", 12, 100, 512, "mean", 20, 0.1, 32), ("l_sum", 12, 100, 512, "sum", 5, 0.001, 32))
+
+
+def spreadout_fc(N, D, amp, a, b, c, every, w0, w1):
+    """Closed-form class centres with planted near-duplicates (fp64 arithmetic, rounded to fp32 once): amp * sin(a i (j + 1) + b j + c i);
+    every `every`-th row r of the upper half is mixed with row r - N/2 by w = |w0 + w1 sin r|."""
+    i, j = np.arange(N, dtype=np.float64)[:, None], np.arange(D, dtype=np.float64)[None, :]
+    fc = amp * np.sin(a * i * (j + 1) + b * j + c * i)
+    base = fc.copy()
+    for r in range(N // 2, N):
+        if r % every == 0:
+            w = abs(w0 + w1 * np.sin(float(r)))
+            fc[r] = w * base[r - N // 2] + (1 - w) * base[r]
+    return torch.from_numpy(fc.astype(np.float32))
+
+
+def _spreadout_loop(fc0, mode, iters, lr, wd, margin=0.4):
+    """The body of the reference's Server.SpreadOut on `fc0` (its dtype decides the precision of the whole loop)."""
+    with _cpu_cuda_shims():
+        sp = server.SpreadOut_Module(fc0.detach().clone(), margin=margin, mode=mode)
+        opt = torch.optim.SGD(sp.parameters(), lr=lr * 10, momentum=0.9, weight_decay=wd)
+        losses_, grad0, gap, gap0, active0 = [], None, np.inf, None, None
+        for it in range(iters):
+            opt.zero_grad()
+            loss = sp()
+            losses_.append(loss.item())
+            loss.backward()
+            with torch.no_grad():
+                fn = F.normalize(sp.FC.data.double())
+                s = fn @ fn.t()
+                s.fill_diagonal_(-2.0)
+                gap = min(gap, float((s - margin).abs().min()))
+                if it == 0:
+                    grad0, active0, gap0 = sp.FC.grad.detach().clone(), int((s > margin).sum()), gap
+            opt.step()
+    return np.array(losses_, np.float64), grad0, sp.FC.data.detach().clone(), active0, (gap0, gap)
+
+
+def gen_spreadout():
+    wd = 5e-4
+    out = {"gen_" + k: v for k, v in SPREADOUT_GEN.items()}
+    out["weight_decay"], out["margin"] = wd, 0.4
+    out["cases"] = np.array([c[0] for c in SPREADOUT_CASES])
+    for name, nc, ids, D, mode, iters, lr, nrows in SPREADOUT_CASES:
+        N = nc * ids
+        fc0 = spreadout_fc(N, D, **SPREADOUT_GEN)
+        l32, g32, f32_, act, gap = _spreadout_loop(fc0, mode, iters, lr, wd)
+        l64, g64, f64_, act64, gap64 = _spreadout_loop(fc0.double(), mode, iters, lr, wd)
+        # no pair of the first iteration may sit within the fp32 dot-product error of the margin (the active count is compared exactly);
+        # `gap` is the same distance over all iterations of both loops, where a pair that crosses the margin carries a hinge of ~ 0
+        gap0, gap = min(gap[0], gap64[0]), min(gap[1], gap64[1])
+        assert act == act64 and gap0 > D * 2.0 ** -24, (name, act, act64, gap0)
+        u32, u64 = f32_.double() - fc0.double(), f64_ - fc0.double()
+        alpha, buf = 1.0, 0.0                                            # what the loop does to FC with a zero gradient: FC_t = alpha_t FC_0
+        for it in range(iters):
+            buf = wd * alpha if it == 0 else 0.9 * buf + wd * alpha
+            alpha -= lr * 10 * buf
+        wd_only = fc0.double() * (alpha - 1)
+        rows = np.unique(np.concatenate([np.arange(0, N, max(1, N // (nrows // 2)))[: nrows // 2],
+                                                                        g32.norm(dim=1).argsort(descending=True)[: nrows // 2].numpy()]))
+        out.update({name + "_shape": np.array([nc, ids, D]), name + "_mode": mode, name + "_iters": iters, name + "_cfg_lr": lr,
+                    name + "_losses": l32, name + "_losses64": l64, name + "_active": act, name + "_gap0": gap0, name + "_gap": gap,
+                    name + "_rows": rows.astype(np.int64), name + "_grad0": g32[rows], name + "_final": f32_ if D == 128 else f32_[rows],
+                    name + "_grad0_rownorm": g32.double().norm(dim=1), name + "_update_rownorm": u32.norm(dim=1),
+                    name + "_div_update": float((u32 - u64).norm() / u64.norm()),
+                    name + "_div_update_rows": float((u32 - u64)[rows].norm() / u64[rows].norm()),
+                    name + "_div_update_slices": np.array([float((u32 - u64)[k * ids:(k + 1) * ids].norm() / u64[k * ids:(k + 1) * ids].norm())
+                                                           for k in range(nc)]),
+                    name + "_div_grad0": float((g32.double() - g64).norm() / g64.norm()),
+                    name + "_div_loss": float(np.max(np.abs(l32 - l64) / np.abs(l64))),
+                    name + "_not_wd": float((u64 - wd_only).norm() / u64.norm())})
+        print("  %-7s N %4d D %3d  active %5d / %d  gap0 %.2e gap %.2e  loss %.5e -> %.5e  fp32 vs fp64: update %.2e grad %.2e loss %.2e  not-wd %.3f"
+              % (name, N, D, act, N * (N - 1), gap0, gap, l32[0], l32[-1], out[name + "_div_update"], out[name + "_div_grad0"],
+                 out[name + "_div_loss"], out[name + "_not_wd"]))
+    save("spreadout", **out)
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["block", "r50", "r100", "heads", "bce", "sgd", "fedavg", "pfc", "client", "public", "mining", "roc", "sphnet", "sphnet64", "freeze_bn",
-                             "checkpoint", "ident_1n", "ijbc", "ijbc_1n"]
+                             "checkpoint", "ident_1n", "ijbc", "ijbc_1n", "spreadout"]
     if "checkpoint" in which:
         gen_checkpoint()
     if "freeze_bn" in which:
@@ -973,6 +1057,8 @@ if __name__ == "__main__":
         gen_ijbc()
     if "ijbc_1n" in which:
         gen_ijbc_1n()
+    if "spreadout" in which:
+        gen_spreadout()
     if "public" in which:
         for v in ("full", "seq", "bce_rw"):
             gen_public(v)
