@@ -18,6 +18,7 @@ config.lr = 0.05
 config.step = [6, 14]
 config.num_epoch = 16
 config.val_targets = ["agedb_30"]
+config.val_rec = "val"          # directory of the verification sets <name>.bin (reference config.py:15-16: a path of its author's machine)
 
 
 def lr_step_func(epoch):

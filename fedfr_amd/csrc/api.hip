@@ -653,6 +653,14 @@ int fedfr_spreadout_grad(const float* fn, int N, int D, float margin, int mean, 
                          size_t ws_bytes, void* stream) {
   return spreadout_grad(fn, N, D, margin, mean, dfn, loss, active, ws, ws_bytes, ST(stream));
 }
+size_t fedfr_verif_workspace_bytes(int P, int nfolds) { return verif_workspace_bytes(P, nfolds); }
+int fedfr_verif_fold_counts(const void* emb0, const void* emb1, int fp64_input, int normalize, const unsigned char* issame, int P, int D,
+                            int nfolds, const double* thr_a, int Ta, const double* thr_b, int Tb, unsigned long long* counts_a,
+                            unsigned long long* counts_b, double* dist, double* norm_sum, int* status, void* ws, size_t ws_bytes,
+                            void* stream) {
+  return verif_fold_counts(emb0, emb1, fp64_input, normalize, issame, P, D, nfolds, thr_a, Ta, thr_b, Tb, counts_a, counts_b, dist,
+                           norm_sum, status, ws, ws_bytes, ST(stream));
+}
 int fedfr_bias_prelu_bwd(const uint16_t* dy, const uint16_t* x, const float* bias, const float* alpha, int M, int C, float* partials,
                          float* coef, float* dbias, float* dalpha, const uint16_t* add, uint16_t* dx, void* stream) {
   return ew_bias_prelu_bwd(BF(dy), BF(x), bias, alpha, M, C, partials, coef, dbias, dalpha, BF(add), BFM(dx), ST(stream));

@@ -63,3 +63,8 @@ int ijbc_roc_counts(const double* score, const long long* label, long long P, co
 size_t spreadout_workspace_bytes(int N, int D);
 int spreadout_grad(const float* fn, int N, int D, float margin, int mean, float* dfn, float* loss, long long* active, void* ws, size_t ws_bytes,
                    hipStream_t st);
+// k-fold 1:1 verification (verif.hip): normalise, pair distances, per-fold threshold histograms and the norm sum in one pass
+size_t verif_workspace_bytes(int P, int nfolds);
+int verif_fold_counts(const void* emb0, const void* emb1, int fp64_input, int normalize, const unsigned char* issame, int P, int D,
+                      int nfolds, const double* thr_a, int Ta, const double* thr_b, int Tb, unsigned long long* counts_a,
+                      unsigned long long* counts_b, double* dist, double* norm_sum, int* status, void* ws, size_t ws_bytes, hipStream_t st);

@@ -1,7 +1,8 @@
 """Server side of the federated loop (reference server.py:25-46, :265-338): dataset-size-weighted
 averaging of client models, as HIP kernels over flat buffers (single process) or one RCCL all-reduce over
-xGMI when every client is its own rank (one client = one MI355X); and the spread-out step on the clients' class centres
-(reference server.py:48-63, :340-371) on one fused HIP kernel."""
+xGMI when every client is its own rank (one client = one MI355X); the spread-out step on the clients' class centres
+(reference server.py:48-63, :340-371) on one fused HIP kernel; and the round's 1:1 verification of the global model with its
+checkpoints (reference server.py:135-148)."""
 from __future__ import annotations
 
 import copy
@@ -345,6 +346,32 @@ class Server(object):
             self.clients[i].fc_module.fc.data = FC[o:o + n].to(device=old.device, dtype=old.dtype, copy=True)
             o += n
         self.logger.info('=====Update FC in partial FC module=====')
+
+    @torch.no_grad()
+    @_C.on_device(lambda self: self.device)
+    def test(self):
+        """reference server.py:135-148: 1:1 verification of the global model on ``cfg.val_targets`` (``callbacks.CallBackVerification``:
+        fused k-fold kernel, sets resident on the GPU), in eval mode through the resident shared backbone; ``backbone.pth`` when this
+        round is the best of the last target so far and ``global_round`` > 0, ``backbone_<round>.pth`` always.  The callbacks and
+        ``output_dir`` come from ``args`` / ``cfg`` on the first call."""
+        import os
+        from .callbacks import CallBackModelCheckpoint, CallBackVerification, portable_state_dict
+        from .config import config as cfg
+        if getattr(self, "callback_verification", None) is None:
+            self.output_dir = getattr(self, "output_dir", None) or getattr(self.args, "output_dir", "./")
+            os.makedirs(self.output_dir, exist_ok=True)
+            self.callback_verification = CallBackVerification(1, 0, cfg.val_targets, cfg.val_rec, self.num_client)
+            self.callback_checkpoint = CallBackModelCheckpoint(0, self.output_dir)
+        self.federated_model.eval()
+        bb = self._eval_backbone()
+        self.callback_verification(self.global_round, bb, None, th=0)
+        bb.eval()                                   # the callback leaves its backbone in train mode, as the reference's does
+        self.federated_model.eval()
+        if self.callback_verification.highest_acc_list[-1][0] == self.global_round:
+            self.callback_checkpoint(self.global_round, self.federated_model, None)
+            self.logger.info('Save server model, epoch %d model...' % (self.global_round))
+        if self.global_round >= 0 and self.global_round % 1 == 0:
+            torch.save(portable_state_dict(self.federated_model), os.path.join(self.output_dir, "backbone_%d.pth" % self.global_round))
 
     def step_round(self):
         """What the reference driver does after every ``server.train()`` (train.py:87-88)."""

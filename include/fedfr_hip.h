@@ -397,6 +397,23 @@ int fedfr_roc_counts(const double* score, const long long* label, long long P, c
 size_t fedfr_spreadout_workspace_bytes(int N, int D);
 int fedfr_spreadout_grad(const float* fn, int N, int D, float margin, int mean, float* dfn, float* loss, long long* active, void* ws,
                          size_t ws_bytes, void* stream);
+/* k-fold 1:1 verification (eval/verification.py test / evaluate / calculate_roc / calculate_val) in one pass over the embeddings of a
+ * verification set: emb0 [2P][D], emb1 [2P][D] (the flipped images' embeddings; NULL = no flip test), both fp32 (fp64_input = 0) or
+ * fp64 (1); rows 2p and 2p + 1 form pair p, issame [P] uint8.  Per row, in fp64: s = emb0 + emb1, with normalize = 1 divided by
+ * sqrt(sum s^2) as sklearn.preprocessing.normalize does (a zero row stays zero), with normalize = 0 taken as it is; per pair
+ * dist[p] = sum (a - b)^2 (optional output).  thr_a [Ta] and thr_b [Tb] (NULL = one table) are ascending fp64 threshold tables in
+ * device memory; for each, k0 = #{k : thr[k] <= dist}, so np.less(dist, thr[k]) holds exactly for k >= k0, and
+ *   counts_a [nfolds][2][Ta + 1], counts_b [nfolds][2][Tb + 1] uint64 (overwritten) count the pairs by fold, issame and k0;
+ * folds are the contiguous ranges of KFold(n_splits = nfolds, shuffle = False) over the P pairs.  A NaN dist is counted in bin T (never
+ * accepted) and sets *status bit 1 (zero *status first).  *norm_sum = the sum of the fp64 L2 norms of all raw rows of emb0 and emb1
+ * (xnorm = norm_sum / number of rows), added in a fixed order: two calls give the same bits; the counts are integers.
+ * D a multiple of 4 in [4, 1024]; 1 <= nfolds <= P; 2 (Ta + 1) + 2 (Tb + 1) <= 16000; embeddings 16-byte aligned.
+ * ws: fedfr_verif_workspace_bytes(P, nfolds) bytes of device memory (0 for unsupported sizes). */
+size_t fedfr_verif_workspace_bytes(int P, int nfolds);
+int fedfr_verif_fold_counts(const void* emb0, const void* emb1, int fp64_input, int normalize, const unsigned char* issame, int P, int D,
+                            int nfolds, const double* thr_a, int Ta, const double* thr_b, int Tb, unsigned long long* counts_a,
+                            unsigned long long* counts_b, double* dist, double* norm_sum, int* status, void* ws, size_t ws_bytes,
+                            void* stream);
 /* model-contrastive term (client.py:372-375, :415-418): row_loss[b] = CE([cos(x,g)/T, cos(x,l)/T], 0) with
  * nn.CosineSimilarity(dim=1, eps=1e-8); dx = d(mean_b row_loss)/dx (optional).  g, l: frozen global / last-round embeddings. */
 int fedfr_contrastive(const float* feats, const float* global_feats, const float* last_feats, int B, int D, float temperature,

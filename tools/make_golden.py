@@ -21,6 +21,7 @@ What is captured (reference symbol → fixture):
   local_all.combine_features / evaluation (the --task 1:n client loop) → ident_1n.npz
   ijbc_all.image2template_feature_1n / gen_mask / evaluation (job 1:N) → ijbc_1n.npz
   server.SpreadOut_Module + torch.optim.SGD driven as Server.SpreadOut does (server.py:340-371) → spreadout.npz
+  eval.verification.calculate_roc and the per-threshold calculate_val_far tables of calculate_val → verification.npz
 """
 import os
 import sys
@@ -1018,9 +1019,42 @@ def gen_spreadout():
     save("spreadout", **out)
 
 
+# ---- 16. k-fold 1:1 verification (eval/verification.py calculate_roc, calculate_val_far per threshold) -----------------------------------
+VERIFICATION_CASES = (  # name, pairs, D, folds, label layout, seed (inputs: tools/verification_pairs.py, flip set included)
+    ("lfw", 6000, 512, 10, "blocks", 0), ("odd", 603, 128, 10, "random", 1), ("one", 200, 64, 1, "alternate", 2),
+    ("five", 257, 256, 5, "random", 3))
+
+
+def gen_verification():
+    """verification.evaluate itself cannot be captured: calculate_val's interp1d raises on the duplicate FAR values with current scipy.
+    calculate_roc and the per-threshold calculate_val_far tables of calculate_val's fold loop are."""
+    import sklearn.preprocessing
+    from eval import verification as V
+    sys.path.insert(0, os.path.join(REPO, "tools"))
+    from verification_pairs import synthetic_pairs
+    out = {"cases": np.array([c[0] for c in VERIFICATION_CASES])}
+    thr_a, thr_b = np.arange(0, 4, 0.01), np.arange(0, 4, 0.001)
+    for name, P, D, nfolds, layout, seed in VERIFICATION_CASES:
+        emb0, emb1, issame = synthetic_pairs(P, D, seed, layout)
+        emb = sklearn.preprocessing.normalize(emb0.astype(np.float64) + emb1.astype(np.float64))      # verification.test :276-277
+        e1, e2 = emb[0::2], emb[1::2]
+        tpr, fpr, acc = V.calculate_roc(thr_a, e1, e2, np.asarray(issame), nrof_folds=nfolds)
+        dist = np.sum(np.square(np.subtract(e1, e2)), 1)
+        far_train = np.zeros((nfolds, len(thr_b)))
+        for f, (train, _) in enumerate(V.LFold(n_splits=nfolds, shuffle=False).split(np.arange(P))):
+            for k, t in enumerate(thr_b):
+                far_train[f, k] = V.calculate_val_far(t, dist[train], issame[train])[1]
+        gap = min(np.abs(dist[:, None] - thr_a[None, :]).min(), np.abs(dist[:, None] - thr_b[None, :]).min())
+        assert gap > 1e-10, (name, gap)                 # no distance within summation-order error of a threshold
+        out.update({name + "_shape": np.array([P, D, nfolds, seed]), name + "_layout": layout, name + "_tpr": tpr, name + "_fpr": fpr,
+                    name + "_accuracy": acc, name + "_far_train": far_train, name + "_dist": dist, name + "_gap": gap})
+        print("  %-5s P %4d D %3d folds %2d  acc %.5f+-%.5f  gap %.2e" % (name, P, D, nfolds, acc.mean(), acc.std(), gap))
+    save("verification", **out)
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["block", "r50", "r100", "heads", "bce", "sgd", "fedavg", "pfc", "client", "public", "mining", "roc", "sphnet", "sphnet64", "freeze_bn",
-                             "checkpoint", "ident_1n", "ijbc", "ijbc_1n", "spreadout"]
+                             "checkpoint", "ident_1n", "ijbc", "ijbc_1n", "spreadout", "verification"]
     if "checkpoint" in which:
         gen_checkpoint()
     if "freeze_bn" in which:
@@ -1059,6 +1093,8 @@ if __name__ == "__main__":
         gen_ijbc_1n()
     if "spreadout" in which:
         gen_spreadout()
+    if "verification" in which:
+        gen_verification()
     if "public" in which:
         for v in ("full", "seq", "bce_rw"):
             gen_public(v)
