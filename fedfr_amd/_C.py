@@ -103,6 +103,7 @@ SIGNATURES = {
     "fedfr_pad_input_nhwc": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "fedfr_preprocess_u8": (i32, [vp, vp, vp, i32, i32, i32, vp]),
     "fedfr_roc_histogram": (i32, [vp, vp, i32, i32, i32, vp, vp]),
+    "fedfr_roc_histogram_groups": (i32, [vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, vp]),
     "fedfr_ident_workspace_bytes": (sz, [i32, i32, i32]),
     "fedfr_ident_topk": (i32, [vp, vp, i32, vp, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, sz, vp]),
     "fedfr_ident_rank_workspace_bytes": (sz, [i32, i32, i32]),

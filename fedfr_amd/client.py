@@ -758,6 +758,20 @@ class Client(object):
     def _get_backbone(self):
         return shared_backbone(self.args.network, self.device, self.dropout, getattr(self, "slot", 0))
 
+    def _local_verification(self, callback_verification, backbone, last_epoch, use_bce=False):
+        """reference client.py:478-488, :562-566: the local 1:1 test of the trained model — backbone + converter with the personalised
+        head — and the client's checkpoint under ``<output_dir>/clients/client_<cid>``."""
+        from .callbacks import portable_state_dict
+        self.logger.info("Client %d Local Testing" % (self.cid))
+        out = getattr(self, "client_output", None) or os.path.join(getattr(self.args, "output_dir", "."), "clients", "client_%d" % self.cid)
+        os.makedirs(out, exist_ok=True)
+        model = nn.Sequential(backbone, self.bce_module.converter) if use_bce else backbone
+        backbone.mark_weights_dirty()           # the eval forward rebuilds its 16-bit weight copies from the trained fp32 parameters
+        callback_verification.veri_test(model, last_epoch, self.target_ID, self.cid)
+        torch.save(portable_state_dict(backbone), os.path.join(out, "backbone.pth"))
+        if use_bce:
+            torch.save(portable_state_dict(self.bce_module), os.path.join(out, "bce_module.pth"))
+
     @_C.on_device(lambda self: self.device)
     def train(self, start_epoch=0, callback_verification=None):
         """reference client.py:511-571."""
@@ -766,6 +780,9 @@ class Client(object):
         backbone.train()
         self.fc_module.to(self.device)
         self.fc_module.train()
+        if callback_verification is not None and start_epoch == 0:             # client.py:523-525
+            self.logger.info('Pretrain Local testing')
+            callback_verification.veri_test(backbone, -1, self.target_ID, self.cid)
         trainer = FusedTrainer(backbone, self.fc_module.fc.data, self.loss_name, 30.0, 0.4,
                                lr=cfg.lr_func(start_epoch) * cfg.lr, momentum=cfg.momentum, weight_decay=cfg.weight_decay,
                                aux_slot=getattr(self, "slot", 0))
@@ -787,6 +804,8 @@ class Client(object):
             loss_meter.update(l.item(), 1)
         trainer.finish()
         self.loss_meter = loss_meter
+        if callback_verification is not None:                                   # client.py:562-566
+            self._local_verification(callback_verification, backbone, start_epoch + self.local_epoch - 1)
         self.backbone_state_dict = flat_state_dict(backbone)
         self.fc_module.cpu()
 
@@ -881,6 +900,9 @@ class Client(object):
             import copy
             global_model = copy.deepcopy(backbone).eval()                          # frozen copy of the incoming global model
             self.last_model = self.last_model.to(self.device).eval()
+        if callback_verification is not None and start_epoch == 0:             # client.py:331-333
+            self.logger.info('Pretrain Local testing')
+            callback_verification.veri_test(backbone, -1, self.target_ID, self.cid)
         trainer = FusedHeadTrainer(backbone, head_params, lr=cfg.lr, momentum=cfg.momentum, weight_decay=cfg.weight_decay,
                                    aux_slot=getattr(self, "slot", 0))
         margin, fc_module = self.margin_softmax, self.fc_module
@@ -931,6 +953,8 @@ class Client(object):
         trainer.finish()
         self.cos_meter, self.con_meter, self.bce_meter = cos_meter, con_meter, bce_meter
         self.loss_meter = loss_meter
+        if callback_verification is not None:                                   # client.py:478-488
+            self._local_verification(callback_verification, backbone, start_epoch + self.local_epoch - 1, use_bce)
         self.backbone_state_dict = flat_state_dict(backbone)
         self.fc_module.cpu()
         if use_bce:

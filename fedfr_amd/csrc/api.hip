@@ -619,6 +619,10 @@ int fedfr_class_accumulate(const float* feats, const long long* label, int B, in
 int fedfr_roc_histogram(const float* feats, const long long* label, int N, int D, int T, unsigned long long* hist, void* stream) {
   return head_roc_histogram(feats, label, N, D, T, hist, ST(stream));
 }
+int fedfr_roc_histogram_groups(const float* feats, const long long* label, int N, int D, const int* row_index, const int* tile_group,
+                               int n_tiles, int G, int* tile_group_dev, unsigned long long* hist, void* stream) {
+  return head_roc_histogram_groups(feats, label, N, D, row_index, tile_group, n_tiles, G, tile_group_dev, hist, ST(stream));
+}
 size_t fedfr_ident_workspace_bytes(int Q, int S, int K) { return ident_workspace_bytes(Q, S, K); }
 int fedfr_ident_topk(const float* query, const long long* qid, int Q, const float* gallery, const long long* gid, int G, int D,
                      const long long* seg, int S, int K, double* pos, double* neg_topk, long long* neg_count, void* ws, size_t ws_bytes,

@@ -38,6 +38,9 @@ int head_sgemm_colflag(const float* A, const float* B, int M, int N, int K, long
                        long long sbn, float alpha, float thr, unsigned char* flags, hipStream_t st);
 int head_class_accumulate(const float* x, const long long* label, int B, int D, int C, float* sums, float* counts, hipStream_t st);
 int head_roc_histogram(const float* feat, const long long* label, int N, int D, int T, unsigned long long* hist, hipStream_t st);
+// grouped pair histogram (roc_groups.hip): G disjoint target sets in one pass over the unordered pairs; tile_group is HOST memory
+int head_roc_histogram_groups(const float* feat, const long long* label, int N, int D, const int* row_index, const int* tile_group,
+                              int n_tiles, int G, int* tile_group_dev, unsigned long long* hist, hipStream_t st);
 // 1:N identification (ident.hip): positive score per query + exact top-K negatives per column segment
 size_t ident_workspace_bytes(int Q, int S, int K);
 int ident_topk(const float* query, const long long* qid, int Q, const float* gallery, const long long* gid, int G, int D,

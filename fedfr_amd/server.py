@@ -201,6 +201,18 @@ class Server(object):
         self.pretrained_feats = None                 # [N_public, 512] normalised embeddings (hard-negative mining)
         self.pretrained_fc = None                    # [n_public, 512] class centres of the public identities (server.py:182-240)
         self.pretrain_fc = None                      # where the reference stores the FedAvg'd public centres (server.py:325, see train())
+        self.callback_local_veri = None              # local 1:1 verification (server.py:105-108): see enable_local_verification()
+        self.local_candidates = []
+
+    def enable_local_verification(self, callback, candidates=None):
+        """reference server.py:105-108: ``callback`` (``eval_local.CallBack_LocalVerifi``) is handed to the clients whose ``cid`` is a
+        "local candidate" — by default up to ten, ``sorted(np.random.permutation(num_client)[:10])``, drawn here and not in
+        ``__init__`` so that a server without local verification consumes no random numbers for it."""
+        self.callback_local_veri = callback
+        if candidates is None:
+            candidates = sorted(list(np.random.permutation(self.num_client)[:10]))
+        self.local_candidates = [int(c) for c in candidates]
+        self.logger.info('Local Veri Candidates %s' % (self.local_candidates,))
 
     # ---- public-set inference sweeps (SURVEY §8f N1; reference server.py:182-263)
     def _eval_backbone(self):
@@ -248,14 +260,17 @@ class Server(object):
             c.slot = slot
             c.backbone_state_dict = flat_state_dict(self.federated_model)       # "server sends backbone"
             c.local_epoch = self.local_epoch
+            veri = {}                                                           # server.py:291-298: candidates train with the local test
+            if self.callback_local_veri is not None and c.cid in self.local_candidates:
+                veri = {"callback_verification": self.callback_local_veri}
             if public:
                 if self.pretrained_fc is None:
                     raise RuntimeError("Server.train: add_pretrained_data needs server.pretrained_fc ([n_public, 512] class centres)")
                 c.train_with_public_data(self.global_epoch, public_train_loader=self.public_train_loader,
                                          pretrained_fc=self.pretrained_fc, choose_hard_negative=mine,
-                                         pretrained_label=self.pretrained_label, pretrained_feats=self.pretrained_feats)
+                                         pretrained_label=self.pretrained_label, pretrained_feats=self.pretrained_feats, **veri)
             else:
-                c.train(self.global_epoch)
+                c.train(self.global_epoch, **veri)
 
         par = max(1, int(getattr(self.args, "parallel_clients", 1)))
         order = list(self.current_client_list)

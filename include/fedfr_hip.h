@@ -333,6 +333,15 @@ int fedfr_preprocess_u8(const unsigned char* src_hwc, const unsigned char* flip,
  * bin = int((<feats[a], feats[b]> + 1) * 1000) in fp64; hist[2*bin] += same label, hist[2*bin+1] += different label.
  * hist: 4002 uint64 counters, accumulated (zero them first). */
 int fedfr_roc_histogram(const float* feats, const long long* label, int N, int D, int T, unsigned long long* hist, void* stream);
+/* grouped pairwise ROC histogram (local_all.py:303-335: roc_cuda.py once per client on one feature matrix) in one pass: G disjoint
+ * target sets.  row_index[n_tiles * 64] (device int32): feature rows in slot order, every group's rows starting at a multiple of 64,
+ * -1 = padding, every row of feats at most once (rows that are nobody's target in tiles of group -1, or left out).  tile_group[n_tiles]
+ * (HOST int32): group in [-1, G) of each 64-slot tile; it is copied to tile_group_dev[n_tiles] (device) on the stream.  For every
+ * unordered pair of indexed rows {a, b} the bin of fedfr_roc_histogram is counted in hist[g(a)] if g(a) >= 0 and in hist[g(b)] if
+ * g(b) >= 0 and g(b) != g(a): hist[c] equals fedfr_roc_histogram's result with group c's rows first.
+ * hist: [G][4002] uint64 counters, accumulated (zero them first). */
+int fedfr_roc_histogram_groups(const float* feats, const long long* label, int N, int D, const int* row_index, const int* tile_group,
+                               int n_tiles, int G, int* tile_group_dev, unsigned long long* hist, void* stream);
 /* 1:N identification (local_all.py:142-176 evaluation, one launch for all clients of :274-297): query [Q][D] fp32 with per-query id
  * qid[Q] (-1: not enrolled), gallery [G][D] fp32 with per-column id gid[G] (distinct among the ids >= 0), columns split into S client
  * segments by seg[S+1] (HOST memory, 0 = seg[0] < seg[1] < ... < seg[S] = G).  Scores are fp64 dot products of the fp32 features.
