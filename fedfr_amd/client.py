@@ -430,17 +430,17 @@ class FusedTrainer(_BackboneTrainer):
             # the two GEMMs on the path are latency chains (16 / 32 dependent k-steps on 32 / 16 workgroups): split-K slabs that
             # the consumer adds in order, and margin -> softmax -> gradient as one launch
             ks, kd = _split_for(D_), _split_for(C_)
-            prob_t, g = ops.softmax_ce_fused(ops.sgemm(fn, wn, trans_b=True, splits=ks), labels, self.s, self.m, self.arc, 1.0 / B)
+            _, g, nll_t = ops.softmax_ce_fused(ops.sgemm(fn, wn, trans_b=True, splits=ks), labels, self.s, self.m, self.arc, 1.0 / B, nll=True)
             dfeats = ops.normalize_rows_bwd_slabs(fn, finv, ops.sgemm(g, wn, splits=kd))
         else:
             cos = ops.sgemm(fn, wn, trans_b=True)
-            prob_t, g = ops.softmax_ce_grad(cos, labels, self.s, self.m, self.arc, 1.0 / B)
+            _, g, nll_t = ops.softmax_ce_grad(cos, labels, self.s, self.m, self.arc, 1.0 / B, nll=True)
             dfn = ops.sgemm(g, wn)
             dfeats = ops.normalize_rows_bwd(fn, finv, dfn)
 
         def off_path():
             # what the backbone's backward pass does not wait for: the loss value, d(loss)/d(class weights), the step counters
-            loss = ops.nll_mean(prob_t, 0.0)
+            loss = ops.nll_rows_mean(nll_t)                 # log domain: finite where the target's probability underflows fp32
             dwn = ops.sgemm(g, fn, trans_a=True)
             _C.call("fedfr_normalize_rows_bwd", wn.data_ptr(), winv.data_ptr(), dwn.data_ptr(), self.fc_grad.data_ptr(),
                     wn.shape[0], wn.shape[1], 0.0, _C.stream())
@@ -459,7 +459,7 @@ class FusedTrainer(_BackboneTrainer):
             with torch.cuda.stream(self.aux_stream):
                 loss = off_path()
         finally:
-            # the join is unconditional: prob_t / g / fn / wn live in the main stream's pool, and a raise inside off_path must not leave the
+            # the join is unconditional: nll_t / g / fn / wn live in the main stream's pool, and a raise inside off_path must not leave the
             # main stream free to reuse them while the aux stream still reads
             main.wait_stream(self.aux_stream)
         loss.record_stream(main)

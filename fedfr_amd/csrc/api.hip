@@ -55,7 +55,7 @@ int fedfr_check_launch(const char* what) {
 
 extern "C" {
 
-int fedfr_version(void) { return 100; }
+int fedfr_version(void) { return 101; }
 int fedfr_storage_dtype(void) { return FEDFR_FP16 ? 1 : 0; }
 const char* fedfr_last_error_string(void) { return g_err; }
 // ---- process-global switches (tuning / validation).  ONE table: name, variable, clamp (the default is the variable's initialiser, read before the first change), so that fedfr_set_option, fedfr_get_option and
@@ -567,8 +567,8 @@ int fedfr_sgemm_splitk(const float* A, const float* B, float* C, int M, int N, i
   return head_sgemm_splitk(A, B, C, M, N, K, sam, sak, sbk, sbn, ldc, alpha, splits, slab_stride, ST(stream));
 }
 int fedfr_softmax_ce_fused(float* z, const long long* label, int R, int C, int ldz, float s, float m, int arcface, float inv_batch, float* prob_t,
-                           int nslab, long long slab_stride, void* stream) {
-  return head_softmax_ce_fused(z, label, R, C, ldz, s, m, arcface, inv_batch, prob_t, nslab, slab_stride, ST(stream));
+                           int nslab, long long slab_stride, float* nll_t, void* stream) {
+  return head_softmax_ce_fused(z, label, R, C, ldz, s, m, arcface, inv_batch, prob_t, nslab, slab_stride, nll_t, ST(stream));
 }
 int fedfr_normalize_rows_bwd_slabs(const float* xn, const float* inv_norm, const float* dxn, int nslab, long long slab_stride, float* dx, int R,
                                    int D, float beta, void* stream) {
@@ -579,15 +579,15 @@ int fedfr_sgemm(const float* A, const float* B, float* C, int M, int N, int K, l
   return head_sgemm(A, B, C, M, N, K, sam, sak, sbk, sbn, ldc, alpha, beta, bias, ST(stream));
 }
 int fedfr_margin_rowmax(float* z, const long long* label, int R, int C, int ldz, float s, float m, int arc, float* row_max,
-                        float* dmul, void* stream) {
-  return head_margin_rowmax(z, label, R, C, ldz, s, m, arc, row_max, dmul, ST(stream));
+                        float* dmul, float* z_t, void* stream) {
+  return head_margin_rowmax(z, label, R, C, ldz, s, m, arc, row_max, dmul, z_t, ST(stream));
 }
 int fedfr_exp_rowsum(float* z, int R, int C, int ldz, const float* row_max, float* row_sum, void* stream) {
   return head_exp_rowsum(z, R, C, ldz, row_max, row_sum, ST(stream));
 }
 int fedfr_softmax_grad(float* z, const long long* label, int R, int C, int ldz, const float* row_sum, const float* dmul, float s,
-                       float inv_batch, float* prob_t, void* stream) {
-  return head_softmax_grad(z, label, R, C, ldz, row_sum, dmul, s, inv_batch, prob_t, ST(stream));
+                       float inv_batch, float* prob_t, const float* row_max, const float* z_t, float* nll_t, void* stream) {
+  return head_softmax_grad(z, label, R, C, ldz, row_sum, dmul, s, inv_batch, prob_t, row_max, z_t, nll_t, ST(stream));
 }
 int fedfr_margin_bwd(const float* dlogits, const long long* label, const float* dmul, float s, int R, int C, float* dcos, void* stream) {
   return head_margin_bwd(dlogits, label, dmul, s, R, C, dcos, ST(stream));

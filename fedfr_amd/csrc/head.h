@@ -12,15 +12,15 @@ int head_normalize_rows_bwd_slabs(const float* xn, const float* inv, const float
 int head_sgemm_splitk(const float* A, const float* B, float* C, int M, int N, int K, long long sam, long long sak, long long sbk, long long sbn,
                       int ldc, float alpha, int splits, long long slab_stride, hipStream_t st);
 int head_softmax_ce_fused(float* z, const long long* label, int R, int C, int ldz, float s, float m, int arc, float inv_batch, float* prob_t,
-                          int nslab, long long slab_stride, hipStream_t st);
+                          int nslab, long long slab_stride, float* nll_t, hipStream_t st);
 // same, products accumulated in fp64 (fp32 validation path of the backbone)
 int head_sgemm_f64acc(const float* A, const float* B, float* C, int M, int N, int K, long long sam, long long sak, long long sbk, long long sbn,
                       int ldc, float alpha, float beta, const float* bias, hipStream_t st);
 int head_margin_rowmax(float* z, const long long* label, int R, int C, int ldz, float s, float m, int arc, float* row_max,
-                       float* dmul, hipStream_t st);
+                       float* dmul, float* z_t, hipStream_t st);
 int head_exp_rowsum(float* z, int R, int C, int ldz, const float* row_max, float* row_sum, hipStream_t st);
 int head_softmax_grad(float* z, const long long* label, int R, int C, int ldz, const float* row_sum, const float* dmul, float s,
-                      float inv_batch, float* prob_t, hipStream_t st);
+                      float inv_batch, float* prob_t, const float* row_max, const float* z_t, float* nll_t, hipStream_t st);
 int head_margin_bwd(const float* dlogits, const long long* label, const float* dmul, float s, int R, int C, float* dcos,
                     hipStream_t st);
 int head_nll_mean(const float* prob_t, int R, float floor_, float* loss, hipStream_t st);

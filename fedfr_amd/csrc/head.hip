@@ -408,10 +408,11 @@ __device__ __forceinline__ float block_sum(float v, float* sh) {
   return r;
 }
 
-// step 1: logits = margin(cos) * s in place; row_max; dmul[row] = d logit_target / d cos_target
+// step 1: logits = margin(cos) * s in place; row_max; dmul[row] = d logit_target / d cos_target; z_t[row] = the target's logit (-inf when
+// the label is outside [0, C)): what the log-domain loss of step 3 needs once step 2 has overwritten the logits
 __global__ __launch_bounds__(256) void margin_rowmax_kernel(float* __restrict__ z, const long long* __restrict__ label, int C,
                                                             int ldz, float s, float m, int arc, float* __restrict__ row_max,
-                                                            float* __restrict__ dmul) {
+                                                            float* __restrict__ dmul, float* __restrict__ z_t) {
   __shared__ float sh[4];
   const int row = blockIdx.x;
   float* zr = z + (size_t)row * ldz;
@@ -435,12 +436,14 @@ __global__ __launch_bounds__(256) void margin_rowmax_kernel(float* __restrict__ 
       v = x * s;
     }
     zr[c] = v;
+    if (z_t && c == y) z_t[row] = v;
     mx = fmaxf(mx, v);
   }
   mx = block_max(mx, sh);
   if (threadIdx.x == 0) {
     row_max[row] = mx;
     if (dmul && (y < 0 || y >= C)) dmul[row] = s;
+    if (z_t && (y < 0 || y >= C)) z_t[row] = -INFINITY;
   }
 }
 
@@ -496,14 +499,19 @@ __global__ __launch_bounds__(256) void nll_mean_ratio_kernel(const float* __rest
 
 // step 3: p = z / sum; prob_t[row] = p[label] (0 when label == -1); grad wrt cos in place:
 //   g[c] = (p[c] - [c == y]) * inv_batch * (c == y ? dmul[row] : s)
+// nll_t (optional, with row_max and z_t of step 1): -log p[label] in the log domain, (row_max - z_t) + log(row_sum): finite where p[label]
+// itself underflows (a target more than ~104 below the row maximum, s = 64 on a badly mislabelled sample), as F.cross_entropy's
 __global__ __launch_bounds__(256) void softmax_grad_kernel(float* __restrict__ z, const long long* __restrict__ label, int C, int ldz,
                                                            const float* __restrict__ row_sum, const float* __restrict__ dmul,
-                                                           float s, float inv_batch, float* __restrict__ prob_t) {
+                                                           float s, float inv_batch, float* __restrict__ prob_t,
+                                                           const float* __restrict__ row_max, const float* __restrict__ z_t,
+                                                           float* __restrict__ nll_t) {
   const int row = blockIdx.x;
   float* zr = z + (size_t)row * ldz;
   const float inv = 1.f / row_sum[row];
   const long long y = label[row];
   if (threadIdx.x == 0 && (y < 0 || y >= C)) prob_t[row] = 0.f;
+  if (threadIdx.x == 0 && nll_t) nll_t[row] = (row_max[row] - z_t[row]) + logf(row_sum[row]);
   for (int c = threadIdx.x; c < C; c += 256) {
     const float pr = zr[c] * inv;
     float g = pr;
@@ -523,13 +531,13 @@ __global__ __launch_bounds__(256) void softmax_grad_kernel(float* __restrict__ z
 template <int NPT>
 __global__ __launch_bounds__(256) void softmax_ce_fused_kernel(float* __restrict__ z, const long long* __restrict__ label, int C, int ldz, float s,
                                                                float m, int arc, float inv_batch, float* __restrict__ prob_t, int nslab,
-                                                               long long slab_stride) {
+                                                               long long slab_stride, float* __restrict__ nll_t) {
   __shared__ float sh[4];
   const int row = blockIdx.x;
   float* zr = z + (size_t)row * ldz;
   const long long y = label[row];
   float v[NPT];
-  float mx = -INFINITY, dm = s;
+  float mx = -INFINITY, dm = s, zt = -INFINITY;
 #pragma unroll
   for (int k = 0; k < NPT; ++k) {
     const int c = threadIdx.x + 256 * k;
@@ -551,6 +559,7 @@ __global__ __launch_bounds__(256) void softmax_ce_fused_kernel(float* __restrict
         t = x * s;
       }
       v[k] = t;
+      if (c == y) zt = t;
       mx = fmaxf(mx, t);
     }
   }
@@ -567,7 +576,10 @@ __global__ __launch_bounds__(256) void softmax_ce_fused_kernel(float* __restrict
   __syncthreads();                                       // sh is reused
   sum = block_sum(sum, sh);
   const float inv = 1.f / sum;
-  if (threadIdx.x == 0 && (y < 0 || y >= C)) prob_t[row] = 0.f;
+  if (threadIdx.x == 0 && (y < 0 || y >= C)) {
+    prob_t[row] = 0.f;
+    if (nll_t) nll_t[row] = (mx - zt) + logf(sum);
+  }
 #pragma unroll
   for (int k = 0; k < NPT; ++k) {
     const int c = threadIdx.x + 256 * k;
@@ -576,6 +588,7 @@ __global__ __launch_bounds__(256) void softmax_ce_fused_kernel(float* __restrict
       float g = pr, mul = s;
       if (c == y) {
         prob_t[row] = pr;
+        if (nll_t) nll_t[row] = (mx - zt) + logf(sum);
         g -= 1.f;
         mul = dm;
       }
@@ -584,17 +597,17 @@ __global__ __launch_bounds__(256) void softmax_ce_fused_kernel(float* __restrict
   }
 }
 int head_softmax_ce_fused(float* z, const long long* label, int R, int C, int ldz, float s, float m, int arc, float inv_batch, float* prob_t,
-                          int nslab, long long slab_stride, hipStream_t st) {
+                          int nslab, long long slab_stride, float* nll_t, hipStream_t st) {
   FEDFR_REQUIRE(z && label && prob_t && R > 0 && C > 0 && C <= 16384 && ldz >= C && nslab >= 1 && (nslab == 1 || slab_stride >= (long long)R * ldz),
                 "softmax_ce_fused: bad args (rows of at most 16384 classes)");
-  if (C <= 1024) hipLaunchKernelGGL(softmax_ce_fused_kernel<4>, dim3(R), dim3(256), 0, st, z, label, C, ldz, s, m, arc, inv_batch, prob_t, nslab, slab_stride);
-  else if (C <= 4096) hipLaunchKernelGGL(softmax_ce_fused_kernel<16>, dim3(R), dim3(256), 0, st, z, label, C, ldz, s, m, arc, inv_batch, prob_t, nslab, slab_stride);
-  else hipLaunchKernelGGL(softmax_ce_fused_kernel<64>, dim3(R), dim3(256), 0, st, z, label, C, ldz, s, m, arc, inv_batch, prob_t, nslab, slab_stride);      // (round 5: the sampled PartialFC head, 8 500 classes)
+  if (C <= 1024) hipLaunchKernelGGL(softmax_ce_fused_kernel<4>, dim3(R), dim3(256), 0, st, z, label, C, ldz, s, m, arc, inv_batch, prob_t, nslab, slab_stride, nll_t);
+  else if (C <= 4096) hipLaunchKernelGGL(softmax_ce_fused_kernel<16>, dim3(R), dim3(256), 0, st, z, label, C, ldz, s, m, arc, inv_batch, prob_t, nslab, slab_stride, nll_t);
+  else hipLaunchKernelGGL(softmax_ce_fused_kernel<64>, dim3(R), dim3(256), 0, st, z, label, C, ldz, s, m, arc, inv_batch, prob_t, nslab, slab_stride, nll_t);      // (round 5: the sampled PartialFC head, 8 500 classes)
   FEDFR_LAUNCH_CHECK("softmax_ce_fused");
   return FEDFR_OK;
 }
 
-// loss = -mean_r log(max(prob_t[r], floor))   (floor = 1e-30 for PartialFC, 0 for F.cross_entropy)
+// loss = -mean_r log(max(prob_t[r], floor))   (floor = 1e-30: PartialFC; the dense heads average nll_t of step 3 with sum_scale instead)
 __global__ __launch_bounds__(256) void nll_mean_kernel(const float* __restrict__ prob_t, int R, float floor_, float* __restrict__ loss) {
   __shared__ float sh[4];
   float s = 0.f;
@@ -604,20 +617,20 @@ __global__ __launch_bounds__(256) void nll_mean_kernel(const float* __restrict__
 }
 
 int head_margin_rowmax(float* z, const long long* label, int R, int C, int ldz, float s, float m, int arc, float* row_max,
-                       float* dmul, hipStream_t st) {
+                       float* dmul, float* z_t, hipStream_t st) {
   FEDFR_REQUIRE(z && label && row_max && R > 0 && C > 0 && ldz >= C, "margin_rowmax: bad args");
-  hipLaunchKernelGGL(margin_rowmax_kernel, dim3(R), dim3(256), 0, st, z, label, C, ldz, s, m, arc, row_max, dmul);
+  hipLaunchKernelGGL(margin_rowmax_kernel, dim3(R), dim3(256), 0, st, z, label, C, ldz, s, m, arc, row_max, dmul, z_t);
   FEDFR_LAUNCH_CHECK("margin_rowmax");
   return FEDFR_OK;
 }
 int head_exp_rowsum(float* z, int R, int C, int ldz, const float* row_max, float* row_sum, hipStream_t st) {
-  FEDFR_REQUIRE(z && row_max && row_sum && R > 0 && C > 0, "exp_rowsum: bad args");
+  FEDFR_REQUIRE(z && row_max && row_sum && R > 0 && C > 0 && ldz >= C, "exp_rowsum: bad args");
   hipLaunchKernelGGL(exp_rowsum_kernel, dim3(R), dim3(256), 0, st, z, C, ldz, row_max, row_sum);
   FEDFR_LAUNCH_CHECK("exp_rowsum");
   return FEDFR_OK;
 }
 int head_exp_rowsum_target(float* z, const long long* label, int R, int C, int ldz, const float* row_max, float* sums2, hipStream_t st) {
-  FEDFR_REQUIRE(z && label && row_max && sums2 && R > 0 && C > 0, "exp_rowsum_target: bad args");
+  FEDFR_REQUIRE(z && label && row_max && sums2 && R > 0 && C > 0 && ldz >= C, "exp_rowsum_target: bad args");
   hipLaunchKernelGGL(exp_rowsum_target_kernel, dim3(R), dim3(256), 0, st, z, label, R, C, ldz, row_max, sums2);
   FEDFR_LAUNCH_CHECK("exp_rowsum_target");
   return FEDFR_OK;
@@ -629,9 +642,9 @@ int head_nll_mean_ratio(const float* num, const float* den, int R, float floor_,
   return FEDFR_OK;
 }
 int head_softmax_grad(float* z, const long long* label, int R, int C, int ldz, const float* row_sum, const float* dmul, float s,
-                      float inv_batch, float* prob_t, hipStream_t st) {
-  FEDFR_REQUIRE(z && label && row_sum && dmul && prob_t && R > 0 && C > 0, "softmax_grad: bad args");
-  hipLaunchKernelGGL(softmax_grad_kernel, dim3(R), dim3(256), 0, st, z, label, C, ldz, row_sum, dmul, s, inv_batch, prob_t);
+                      float inv_batch, float* prob_t, const float* row_max, const float* z_t, float* nll_t, hipStream_t st) {
+  FEDFR_REQUIRE(z && label && row_sum && dmul && prob_t && R > 0 && C > 0 && ldz >= C && (!nll_t || (row_max && z_t)), "softmax_grad: bad args");
+  hipLaunchKernelGGL(softmax_grad_kernel, dim3(R), dim3(256), 0, st, z, label, C, ldz, row_sum, dmul, s, inv_batch, prob_t, row_max, z_t, nll_t);
   FEDFR_LAUNCH_CHECK("softmax_grad");
   return FEDFR_OK;
 }

@@ -49,16 +49,18 @@ def normalize_rows_bwd_slabs(xn: torch.Tensor, inv: torch.Tensor, dxn_slabs: tor
     return dx
 
 
-def softmax_ce_fused(cos_slabs: torch.Tensor, label: torch.Tensor, s: float, m: float, arcface: bool, inv_batch: float):
+def softmax_ce_fused(cos_slabs: torch.Tensor, label: torch.Tensor, s: float, m: float, arcface: bool, inv_batch: float, nll: bool = False):
     """``softmax_ce_grad`` (no collectives) as ONE launch; ``cos_slabs`` [S, R, C] (C <= 16384) are split-K slabs of the cosine matrix.
-    Returns (prob_target [R], grad = cos_slabs[0], overwritten)."""
+    Returns (prob_target [R], grad = cos_slabs[0], overwritten), and with ``nll`` also the per-row loss -log p_target [R] taken in the
+    log domain (see ``nll_rows_mean``)."""
     cos_slabs = _chk(cos_slabs, "cosine slabs")
     label = _chk(label, "label", torch.int64)
     S, R, Cc = cos_slabs.shape
     prob_t = torch.empty(R, dtype=f32, device=cos_slabs.device)
+    nll_t = torch.empty(R, dtype=f32, device=cos_slabs.device) if nll else None
     _C.call("fedfr_softmax_ce_fused", cos_slabs.data_ptr(), label.data_ptr(), R, Cc, Cc, s, m, 1 if arcface else 0, inv_batch,
-            prob_t.data_ptr(), S, R * Cc, _C.stream())
-    return prob_t, cos_slabs[0]
+            prob_t.data_ptr(), S, R * Cc, _C.ptr(nll_t), _C.stream())
+    return (prob_t, cos_slabs[0], nll_t) if nll else (prob_t, cos_slabs[0])
 
 
 def _auto_splits(M: int, N: int, K: int) -> int:
@@ -113,10 +115,13 @@ def sgemm(a: torch.Tensor, b: torch.Tensor, trans_a: bool = False, trans_b: bool
 
 
 def softmax_ce_grad(cosine: torch.Tensor, label: torch.Tensor, s: float, m: float, arcface: bool,
-                    inv_batch: float, all_reduce=None):
+                    inv_batch: float, all_reduce=None, nll: bool = False):
     """In place on ``cosine`` [R,C]: margin -> softmax -> gradient wrt the cosine matrix.
     Returns (prob_target [R], grad == cosine storage).  ``all_reduce(t, op)`` (op in {"max","sum"}) is
-    applied to the row max / row sum / target prob between the three kernels (PartialFC C3-C5)."""
+    applied to the row max / row sum / target prob between the three kernels (PartialFC C3-C5).
+    ``nll`` (dense rows only: no ``all_reduce``): also return the per-row loss -log p_target [R], taken in the log domain."""
+    if nll and all_reduce is not None:
+        raise RuntimeError("softmax_ce_grad: the log-domain row loss is for unsharded rows (the sharded form keeps PartialFC's floor)")
     cosine = _chk(cosine, "cosine")
     label = _chk(label, "label", torch.int64)
     R, Cc = cosine.shape
@@ -125,19 +130,21 @@ def softmax_ce_grad(cosine: torch.Tensor, label: torch.Tensor, s: float, m: floa
     row_sum = torch.empty(R, dtype=f32, device=dev)
     dmul = torch.empty(R, dtype=f32, device=dev)
     prob_t = torch.empty(R, dtype=f32, device=dev)
+    z_t = torch.empty(R, dtype=f32, device=dev) if nll else None
+    nll_t = torch.empty(R, dtype=f32, device=dev) if nll else None
     st = _C.stream()
     _C.call("fedfr_margin_rowmax", cosine.data_ptr(), label.data_ptr(), R, Cc, Cc, s, m, 1 if arcface else 0,
-            row_max.data_ptr(), dmul.data_ptr(), st)
+            row_max.data_ptr(), dmul.data_ptr(), _C.ptr(z_t), st)
     if all_reduce is not None:
         all_reduce(row_max, "max")
     _C.call("fedfr_exp_rowsum", cosine.data_ptr(), R, Cc, Cc, row_max.data_ptr(), row_sum.data_ptr(), st)
     if all_reduce is not None:
         all_reduce(row_sum, "sum")
     _C.call("fedfr_softmax_grad", cosine.data_ptr(), label.data_ptr(), R, Cc, Cc, row_sum.data_ptr(), dmul.data_ptr(), s,
-            inv_batch, prob_t.data_ptr(), st)
+            inv_batch, prob_t.data_ptr(), row_max.data_ptr() if nll else None, _C.ptr(z_t), _C.ptr(nll_t), st)
     if all_reduce is not None:
         all_reduce(prob_t, "sum")
-    return prob_t, cosine
+    return (prob_t, cosine, nll_t) if nll else (prob_t, cosine)
 
 
 def sharded_softmax_ce_grad(cosine: torch.Tensor, label: torch.Tensor, s: float, m: float, arcface: bool, inv_batch: float,
@@ -157,12 +164,12 @@ def sharded_softmax_ce_grad(cosine: torch.Tensor, label: torch.Tensor, s: float,
     loss = torch.empty((), dtype=f32, device=dev)
     st = _C.stream()
     _C.call("fedfr_margin_rowmax", cosine.data_ptr(), label.data_ptr(), R, Cc, Cc, s, m, 1 if arcface else 0,
-            row_max.data_ptr(), dmul.data_ptr(), st)
+            row_max.data_ptr(), dmul.data_ptr(), None, st)
     all_reduce(row_max, "max")                                                                     # partial_fc.py:142
     _C.call("fedfr_exp_rowsum_target", cosine.data_ptr(), label.data_ptr(), R, Cc, Cc, row_max.data_ptr(), sums2.data_ptr(), st)
     all_reduce(sums2, "sum")                                                                       # partial_fc.py:147 + :161
     _C.call("fedfr_softmax_grad", cosine.data_ptr(), label.data_ptr(), R, Cc, Cc, sums2.data_ptr(), dmul.data_ptr(), s,
-            inv_batch, prob_t.data_ptr(), st)
+            inv_batch, prob_t.data_ptr(), None, None, None, st)
     _C.call("fedfr_nll_mean_ratio", sums2[1].data_ptr(), sums2[0].data_ptr(), R, floor, loss.data_ptr(), st)
     return loss, cosine
 
@@ -201,6 +208,15 @@ def axpy_(dst: torch.Tensor, src: torch.Tensor, w: float) -> torch.Tensor:
 def nll_mean(prob_t: torch.Tensor, floor: float = 0.0) -> torch.Tensor:
     loss = torch.empty((), dtype=f32, device=prob_t.device)
     _C.call("fedfr_nll_mean", prob_t.data_ptr(), prob_t.numel(), floor, loss.data_ptr(), _C.stream())
+    return loss
+
+
+def nll_rows_mean(nll_t: torch.Tensor) -> torch.Tensor:
+    """Mean of the per-row losses ``softmax_ce_fused`` / ``softmax_ce_grad`` return with ``nll=True``: F.cross_entropy's value.  Those are
+    (row max - target logit) + log(row sum), so a target whose probability underflows fp32 (more than ~104 below the row maximum: s = 64
+    on a badly mislabelled sample) still gives the finite gap, where -log(max(prob_target, 0)) gave inf."""
+    loss = torch.empty((), dtype=f32, device=nll_t.device)
+    _C.call("fedfr_sum_scale", nll_t.data_ptr(), nll_t.numel(), 1.0 / nll_t.numel(), loss.data_ptr(), _C.stream())
     return loss
 
 
@@ -293,7 +309,7 @@ class MarginFn(torch.autograd.Function):
         row_max = torch.empty(R, dtype=f32, device=z.device)
         dmul = torch.empty(R, dtype=f32, device=z.device)
         _C.call("fedfr_margin_rowmax", z.data_ptr(), label.data_ptr(), R, Cc, Cc, s, m, 1 if arcface else 0, row_max.data_ptr(),
-                dmul.data_ptr(), _C.stream())
+                dmul.data_ptr(), None, _C.stream())
         ctx.save_for_backward(label, dmul)
         ctx.s = s
         return z
@@ -315,9 +331,9 @@ class CrossEntropyFn(torch.autograd.Function):
     def forward(ctx, logits, label):
         z = _chk(logits.detach().clone(), "logits")
         label = _chk(label, "label", torch.int64)
-        prob_t, grad = softmax_ce_grad(z, label, 1.0, 0.0, False, 1.0 / z.shape[0])
+        _, grad, nll_t = softmax_ce_grad(z, label, 1.0, 0.0, False, 1.0 / z.shape[0], nll=True)
         ctx.save_for_backward(grad)
-        return nll_mean(prob_t, 0.0)
+        return nll_rows_mean(nll_t)
 
     @staticmethod
     def backward(ctx, dl):

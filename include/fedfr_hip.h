@@ -285,18 +285,22 @@ int fedfr_sgemm(const float* A, const float* B, float* C, int M, int N, int K, l
  * split-K slabs C + z * slab_stride (k range z of ceil(K / splits) rounded up to 32; no bias / beta), whose consumers add the slabs in
  * order: fedfr_softmax_ce_fused = fedfr_margin_rowmax + fedfr_exp_rowsum + fedfr_softmax_grad in ONE launch for rows of <= 16384 classes
  * (bit-identical to the three; cosines summed over nslab slabs, gradient written over slab 0), fedfr_normalize_rows_bwd_slabs =
- * fedfr_normalize_rows_bwd on a dxn given as slabs. */
+ * fedfr_normalize_rows_bwd on a dxn given as slabs.
+ * The dense cross-entropy loss is taken in the log domain: nll_t[row] = (row_max - z_t) + log(row_sum) with z_t the target's logit
+ * (fedfr_margin_rowmax writes it; -inf, hence nll_t = +inf, for a label outside [0, C)), finite where prob_t = exp(-nll_t) underflows
+ * to 0 — F.cross_entropy's value; mean over rows = fedfr_sum_scale(nll_t, R, 1 / R).  z_t and nll_t (with row_max, z_t) may be NULL. */
 int fedfr_sgemm_splitk(const float* A, const float* B, float* C, int M, int N, int K, long long sam, long long sak, long long sbk,
                        long long sbn, int ldc, float alpha, int splits, long long slab_stride, void* stream);
 int fedfr_softmax_ce_fused(float* z, const long long* label, int R, int C, int ldz, float s, float m, int arcface, float inv_batch,
-                           float* prob_t, int nslab, long long slab_stride, void* stream);
+                           float* prob_t, int nslab, long long slab_stride, float* nll_t, void* stream);
 int fedfr_normalize_rows_bwd_slabs(const float* xn, const float* inv_norm, const float* dxn, int nslab, long long slab_stride, float* dx,
                                    int R, int D, float beta, void* stream);
 int fedfr_margin_rowmax(float* z, const long long* label, int R, int C, int ldz, float s, float m, int arcface,
-                        float* row_max, float* dmul, void* stream);
+                        float* row_max, float* dmul, float* z_t, void* stream);
 int fedfr_exp_rowsum(float* z, int R, int C, int ldz, const float* row_max, float* row_sum, void* stream);
 int fedfr_softmax_grad(float* z, const long long* label, int R, int C, int ldz, const float* row_sum,
-                       const float* dmul, float s, float inv_batch, float* prob_t, void* stream);
+                       const float* dmul, float s, float inv_batch, float* prob_t, const float* row_max, const float* z_t,
+                       float* nll_t, void* stream);
 int fedfr_margin_bwd(const float* dlogits, const long long* label, const float* dmul, float s, int R, int C, float* dcos,
                      void* stream);
 int fedfr_nll_mean(const float* prob_t, int R, float floor_, float* loss, void* stream);

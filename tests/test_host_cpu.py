@@ -401,3 +401,23 @@ def test_loss_scale_guard_backs_off_and_warns():
         t2.check_overflow()
     assert t2.loss_scale == 256.0 == st.initial
     _C._LOSS_SCALE_STATES.pop(str(dev), None)
+
+
+def test_head_cases_are_conditioned_for_fp32():
+    """Every case of tests/head_cases.py (the inputs of tests/test_head_kernels_gpu.py), evaluated by the same plain formula in fp32 and in
+    fp64 on the CPU: the fp32 result is within ONE QUARTER of the tolerance the GPU test applies to that quantity, under the same per-row
+    error measure.  So a correct fp32 kernel passes the GPU test with room to spare (the inputs are well conditioned), and the tolerances
+    are not what lets it pass.  A case that fails here gets other inputs, not another tolerance."""
+    import head_cases as hc
+    n, worst = 0, {}
+    for case in hc.all_cases():
+        r64, r32 = case.ref(torch.float64), case.ref(torch.float32)
+        assert r64.keys() == r32.keys()
+        for k, q in r64.items():
+            figs = []
+            hc.check(r32[k].value, q, case.name + ":" + k, frac=0.25, out=figs)
+            n += 1
+            for _, kind, e in figs:
+                worst[kind] = max(worst.get(kind, 0.0), e)
+    print("head cases: %d quantities, worst fp32 error per kind %s" % (n, worst))
+    assert n > 2000 and set(worst) == {"fwd", "grad", "loss"}
