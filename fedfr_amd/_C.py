@@ -115,6 +115,9 @@ SIGNATURES = {
     "fedfr_roc_counts": (i32, [vp, vp, i64, vp, i32, vp, vp, sz, vp, vp]),
     "fedfr_spreadout_workspace_bytes": (sz, [i32, i32]),
     "fedfr_spreadout_grad": (i32, [vp, i32, i32, f32, i32, vp, vp, vp, vp, sz, vp]),
+    "fedfr_bottle_workspace_bytes": (sz, [i32, i32]),
+    "fedfr_bottle_forward": (i32, [vp, vp, i32, i32, vp, vp, vp, vp]),
+    "fedfr_bottle_backward": (i32, [vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, sz, vp]),
     "fedfr_verif_workspace_bytes": (sz, [i32, i32]),
     "fedfr_verif_fold_counts": (i32, [vp, vp, i32, i32, vp, i32, i32, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
     "fedfr_contrastive": (i32, [vp, vp, vp, i32, i32, f32, vp, vp, vp]),

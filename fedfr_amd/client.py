@@ -19,6 +19,7 @@ import torch
 from torch import nn
 
 from . import _C, backbones, losses, ops
+from .backbones import BottleBlock
 from .config import config as cfg
 
 f32 = torch.float32
@@ -126,13 +127,15 @@ class _Converter(nn.Module):
 
 
 class BCE_module(nn.Module):
-    """Personalised transform head (reference client.py:25-60), converter_layer == 1 only (config.py:31)."""
+    """Personalised transform head (reference client.py:25-60): the converter is one identity-initialised Linear (converter_layer == 1,
+    config.py:31) or a BottleBlock(hidden, 4) (any other value)."""
 
     def __init__(self, hidden, n_class, converter_layer=1, m=0.4, r=30.0, t=3):
         super().__init__()
-        if converter_layer != 1:
-            raise NotImplementedError("fedfr_amd: BottleBlock converter (converter_layer != 1) is out of scope (SURVEY §2.1)")
-        self.converter = nn.Sequential(_Converter(hidden))      # keeps the reference key 'converter.0.weight'
+        if converter_layer == 1:
+            self.converter = nn.Sequential(_Converter(hidden))      # keeps the reference key 'converter.0.weight'
+        else:
+            self.converter = BottleBlock(hidden, 4)
         self.weight = nn.Parameter(torch.normal(0, 0.01, (n_class, hidden)))
         self.bias = nn.Parameter(torch.zeros(n_class))
         self.n_class, self.hidden, self.m, self.r, self.t = n_class, hidden, m, r, t

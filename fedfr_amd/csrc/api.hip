@@ -657,6 +657,14 @@ int fedfr_spreadout_grad(const float* fn, int N, int D, float margin, int mean, 
                          size_t ws_bytes, void* stream) {
   return spreadout_grad(fn, N, D, margin, mean, dfn, loss, active, ws, ws_bytes, ST(stream));
 }
+size_t fedfr_bottle_workspace_bytes(int B, int D) { return bottle_workspace_bytes(B, D); }
+int fedfr_bottle_forward(const float* x, const float* const* params, int B, int D, float* h1, float* h2, float* y, void* stream) {
+  return bottle_forward(x, params, B, D, h1, h2, y, ST(stream));
+}
+int fedfr_bottle_backward(const float* x, const float* const* params, const float* h1, const float* h2, const float* dy, int B, int D,
+                          float* dx, float* const* grads, void* ws, size_t ws_bytes, void* stream) {
+  return bottle_backward(x, params, h1, h2, dy, B, D, dx, grads, ws, ws_bytes, ST(stream));
+}
 size_t fedfr_verif_workspace_bytes(int P, int nfolds) { return verif_workspace_bytes(P, nfolds); }
 int fedfr_verif_fold_counts(const void* emb0, const void* emb1, int fp64_input, int normalize, const unsigned char* issame, int P, int D,
                             int nfolds, const double* thr_a, int Ta, const double* thr_b, int Tb, unsigned long long* counts_a,

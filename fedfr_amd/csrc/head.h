@@ -71,3 +71,9 @@ size_t verif_workspace_bytes(int P, int nfolds);
 int verif_fold_counts(const void* emb0, const void* emb1, int fp64_input, int normalize, const unsigned char* issame, int P, int D,
                       int nfolds, const double* thr_a, int Ta, const double* thr_b, int Tb, unsigned long long* counts_a,
                       unsigned long long* counts_b, double* dist, double* norm_sum, int* status, void* ws, size_t ws_bytes, hipStream_t st);
+// BottleBlock converter (bottle.hip): four-branch bottleneck MLP with a residual, forward in 2 launches, backward in 2; params / grads are HOST
+// arrays of 18 device pointers: br1..br4 x (first weight, first bias, second weight, second bias), then concat_fc weight and bias
+size_t bottle_workspace_bytes(int B, int D);
+int bottle_forward(const float* x, const float* const* params, int B, int D, float* h1, float* h2, float* y, hipStream_t st);
+int bottle_backward(const float* x, const float* const* params, const float* h1, const float* h2, const float* dy, int B, int D, float* dx,
+                    float* const* grads, void* ws, size_t ws_bytes, hipStream_t st);

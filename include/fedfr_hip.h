@@ -410,6 +410,20 @@ int fedfr_roc_counts(const double* score, const long long* label, long long P, c
 size_t fedfr_spreadout_workspace_bytes(int N, int D);
 int fedfr_spreadout_grad(const float* fn, int N, int D, float margin, int mean, float* dfn, float* loss, long long* active, void* ws,
                          size_t ws_bytes, void* stream);
+/* BottleBlock converter of the personalised head (backbones/bottle.py; client.py:25-36 with converter_layer != 1), fp32, x [B][D], H = D / 4,
+ * branch g = 0..3, LeakyReLU slope 0.01:
+ *   h1_g = leaky(x W1_g^T + b1_g), h2_g = leaky(h1_g W2_g^T + b2_g), y = x + [h2_0|h2_1|h2_2|h2_3] W3^T + b3.
+ * params / grads: HOST arrays of 18 DEVICE pointers in the order br1..br4 x (first weight [H][D], first bias [H], second weight [H][H],
+ * second bias [H]), then concat_fc weight [D][D] and bias [D].  h1, h2 [B][D] (branch g in columns g H .. (g + 1) H) are written by the
+ * forward and read by the backward; the pre-activations are never stored: leaky' is taken from the sign of the stored activation (0.01 at
+ * exactly 0, as torch).  The backward writes all 18 gradients (overwriting) and dx = d y (residual) + the branch term; dx == NULL skips the
+ * input gradient.  Exact-fp32 MFMA products, k ascending; every batch sum has one owner and a fixed order, no floating-point atomics: two
+ * calls on the same input give the same bits.  Forward 2 launches, backward 2.  D a multiple of 64 in [64, 512], B >= 1 (bottle_rate 4).
+ * ws: fedfr_bottle_workspace_bytes(B, D) bytes of device memory (0 for unsupported sizes). */
+size_t fedfr_bottle_workspace_bytes(int B, int D);
+int fedfr_bottle_forward(const float* x, const float* const* params, int B, int D, float* h1, float* h2, float* y, void* stream);
+int fedfr_bottle_backward(const float* x, const float* const* params, const float* h1, const float* h2, const float* dy, int B, int D,
+                          float* dx, float* const* grads, void* ws, size_t ws_bytes, void* stream);
 /* k-fold 1:1 verification (eval/verification.py test / evaluate / calculate_roc / calculate_val) in one pass over the embeddings of a
  * verification set: emb0 [2P][D], emb1 [2P][D] (the flipped images' embeddings; NULL = no flip test), both fp32 (fp64_input = 0) or
  * fp64 (1); rows 2p and 2p + 1 form pair p, issame [P] uint8.  Per row, in fp64: s = emb0 + emb1, with normalize = 1 divided by

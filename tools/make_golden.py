@@ -22,6 +22,7 @@ What is captured (reference symbol → fixture):
   ijbc_all.image2template_feature_1n / gen_mask / evaluation (job 1:N) → ijbc_1n.npz
   server.SpreadOut_Module + torch.optim.SGD driven as Server.SpreadOut does (server.py:340-371) → spreadout.npz
   eval.verification.calculate_roc and the per-threshold calculate_val_far tables of calculate_val → verification.npz
+  client.BCE_module(converter_layer=2) = backbones.BottleBlock(512, 4) → bce_bottle.npz / client_public_bce_bottle.npz / bottle_init.npz
 """
 import os
 import sys
@@ -214,6 +215,66 @@ def gen_bce():
          d_weight=mod.weight.grad, d_bias=mod.bias.grad,
          d_conv_w_slice=mod.converter[0].weight.grad[:8, :64], d_conv_b=mod.converter[0].bias.grad,
          conv_w_norm=mod.converter[0].weight.grad.norm())
+
+
+def _bottle_cases():
+    """tests/bottle_cases.py: the closed-form BottleBlock parameters the tests rebuild (no RNG)"""
+    import importlib.util
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    spec = importlib.util.spec_from_file_location("bottle_cases", os.path.join(REPO, "tests", "bottle_cases.py"))
+    bc = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bc)
+    return bc
+
+
+def _load_bottle(converter):
+    bc = _bottle_cases()
+    sd = dict(zip(bc.PARAM_KEYS, bc.golden_params(512)))
+    assert list(converter.state_dict().keys()) == bc.PARAM_KEYS, "tests/bottle_cases.PARAM_KEYS differs from the reference's key order"
+    converter.load_state_dict(sd)
+
+
+BOTTLE_SLICES = ("br1.0.weight", "br3.2.weight", "concat_fc.weight")
+
+
+def gen_bce_bottle():
+    """gen_bce with converter_layer = 2, in double precision; the converter's output and the gradient arriving at it are kept too, so that a test can pin a
+    stand-alone formula of the block to the reference"""
+    B, C = 12, 10
+    x = R.closed_form((B, 512), 0.113, 0.2, 1.0).requires_grad_(True)
+    mod = client.BCE_module(512, C, 2)
+    mod.weight.data = R.closed_form((C, 512), 0.071, 1.1, 0.05)
+    mod.bias.data = R.closed_form((C,), 0.5, 0.1, 0.1)
+    _load_bottle(mod.converter)
+    mod.double()                                                  # the reference module evaluated in fp64 on the fp32 closed-form values:
+    x = x.detach().double().requires_grad_(True)                  # tests pin an fp64 formula to this fixture at 1e-6
+    lab = torch.tensor([0, 3, 9, 12, 5, 5, 25, 1, 2, 7, 10, 4])   # >= C => all-negative rows
+    kept = []
+
+    def keep(module, inputs, output):
+        output.retain_grad()
+        kept.append(output)
+    hook = mod.converter.register_forward_hook(keep)
+    z, gt = mod(x, lab)
+    hook.remove()
+    loss = losses.BCE_loss()(z.clone(), gt)
+    loss.backward()
+    conv = dict(mod.converter.named_parameters())
+    out = dict(B=B, C=C, labels=lab, z=z, gt=gt, loss=loss, dx=x.grad, d_weight=mod.weight.grad, d_bias=mod.bias.grad,
+               conv_out=kept[0], d_conv_out=kept[0].grad, keys=np.array(list(mod.state_dict().keys())))
+    for k in BOTTLE_SLICES:
+        out["d_" + k + "_slice"] = conv[k].grad[:8, :64]
+    for k, p in conv.items():
+        out["norm_d_" + k] = p.grad.norm()
+        if k.endswith("bias"):
+            out["d_" + k] = p.grad
+    save("bce_bottle", **out)
+
+
+def gen_bottle_init():
+    torch.manual_seed(100)
+    blk = backbones.BottleBlock(512, 4)
+    save("bottle_init", **{k: (v[:8, :8] if v.dim() == 2 else v[:8]) for k, v in blk.state_dict().items()})
 
 
 # ---- 4. SGD ------------------------------------------------------------------------------------------
@@ -481,11 +542,16 @@ def gen_public(variant):
     margin = losses.CosFace(s=30, m=0.4)
     out = dict(cfgp)
     out["variant"] = np.array(variant)
+    bottle = variant == "bce_bottle"                                  # 'full' with converter_layer = 2 (BottleBlock converter)
+    if bottle:
+        variant = "full"
     has_bce, has_con, has_rw = variant in ("full", "bce_rw"), variant == "full", variant == "bce_rw"
     num_client, num_classes = 4, nl
     if has_bce:
-        bcem = client.BCE_module(512, nl, 1)
+        bcem = client.BCE_module(512, nl, 2 if bottle else 1)
         bcem.weight.data = R.head_fc(nl, seed=13)
+        if bottle:
+            _load_bottle(bcem.converter)
         bcem.train()
         bce_crit = losses.BCE_loss()
         model = client.Branch_model(backbone, fcm, bcem)
@@ -550,6 +616,14 @@ def gen_public(variant):
     if has_bce:
         out["bce_weight"] = bcem.weight.data
         out["bce_bias"] = bcem.bias.data
+    if bottle:
+        conv = bcem.converter.state_dict()
+        for k in BOTTLE_SLICES:
+            out["bce_conv_" + k + "_slice"] = conv[k][:8, :64]
+        out["variant"] = np.array("bce_bottle")
+        save("client_public_bce_bottle", **out)
+        return
+    if has_bce:
         out["bce_conv_w_diag"] = torch.diagonal(bcem.converter[0].weight.data).clone()
         out["bce_conv_w_slice"] = bcem.converter[0].weight.data[:8, :64]
         out["bce_conv_b"] = bcem.converter[0].bias.data
@@ -1054,7 +1128,7 @@ def gen_verification():
 
 if __name__ == "__main__":
     which = sys.argv[1:] or ["block", "r50", "r100", "heads", "bce", "sgd", "fedavg", "pfc", "client", "public", "mining", "roc", "sphnet", "sphnet64", "freeze_bn",
-                             "checkpoint", "ident_1n", "ijbc", "ijbc_1n", "spreadout", "verification"]
+                             "checkpoint", "ident_1n", "ijbc", "ijbc_1n", "spreadout", "verification", "bottle"]
     if "checkpoint" in which:
         gen_checkpoint()
     if "freeze_bn" in which:
@@ -1098,3 +1172,7 @@ if __name__ == "__main__":
     if "public" in which:
         for v in ("full", "seq", "bce_rw"):
             gen_public(v)
+    if "bottle" in which:
+        gen_bce_bottle()
+        gen_bottle_init()
+        gen_public("bce_bottle")

@@ -2,7 +2,7 @@
 """Step time of the reference's MAIN training loop, Client.train_with_public_data (client.py:287-508), at its own sizes: combined batch 256
 (config.com_batch_size), a cosine head over [local | public] identities (100 + 6 000), the personalised BCE branch over the 100 local identities
 (weight 10) and the model-contrastive term against two frozen eval-mode backbones (weight config.mu) — through client.FusedHeadTrainer exactly as
-Client.train_with_public_data drives it.  usage: python tools/public_data_bench.py [arch] [steps] [variant: full|bce|seq] [lr]
+Client.train_with_public_data drives it.  usage: python tools/public_data_bench.py [arch] [steps] [variant: full|bce|seq] [lr] [converter_layer]
 Prints one JSON line (ms per step, images/s) — a diagnostic, not the headline bench."""
 import json
 import os
@@ -18,6 +18,8 @@ arch = sys.argv[1] if len(sys.argv) > 1 else "iresnet100"
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 10
 variant = sys.argv[3] if len(sys.argv) > 3 else "full"
 lr = float(sys.argv[4]) if len(sys.argv) > 4 else 1e-3       # (random-init weights and two fixed random batches: the reference's 0.05 diverges)
+if len(sys.argv) > 5:
+    cfg.converter_layer = int(sys.argv[5])                    # != 1: the BottleBlock converter
 dev = torch.device("cuda:0")
 B, NL, NP = cfg.com_batch_size, 100, 6000
 torch.manual_seed(100)
