@@ -118,6 +118,12 @@ SIGNATURES = {
     "fedfr_bottle_workspace_bytes": (sz, [i32, i32]),
     "fedfr_bottle_forward": (i32, [vp, vp, i32, i32, vp, vp, vp, vp]),
     "fedfr_bottle_backward": (i32, [vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, sz, vp]),
+    "fedfr_bce_fused_workspace_bytes": (sz, [i32, i32]),
+    "fedfr_bce_fused": (i32, [vp, vp, vp, i32, i32, f32, f32, f32, f32, f32, vp, vp, vp, vp, sz, vp]),
+    "fedfr_branch_dfeats": (i32, [vp, vp, vp, i32, i64, vp, vp, f32, vp, i32, i32, vp]),
+    "fedfr_branch_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32, i32]),
+    "fedfr_branch_head": (i32, [vp, vp, i32, i32, vp, i32, i32, f32, f32, i32, vp, vp, vp, i32, f32, f32, f32, f32, f32, vp, vp, f32, f32, i32,
+                                vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     "fedfr_verif_workspace_bytes": (sz, [i32, i32]),
     "fedfr_verif_fold_counts": (i32, [vp, vp, i32, i32, vp, i32, i32, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
     "fedfr_contrastive": (i32, [vp, vp, vp, i32, i32, f32, vp, vp, vp]),

@@ -5,6 +5,15 @@
 The hot loop (reference client.py:536-551: zero_grad → fwd → margin → CE → bwd → SGD step) runs through
 ``FusedTrainer``: one ``fedfr_net_forward``, the fp32 head kernels, one ``fedfr_net_backward`` and the flat
 ``fedfr_sgd_step`` — no per-layer Python, no PyTorch autograd on the hot path.
+
+Which paths are autograd-free:
+
+* ``Client.train`` (``FusedTrainer``) and ``Client.train_with_public_data`` (``FusedBranchTrainer``: the whole head — CosFace over
+  [local | public] centres, the personalised BCE branch with its converter, the model-contrastive term — is ONE ``fedfr_branch_head``
+  call) create no ``requires_grad`` tensor and enter no autograd graph.
+* ``train_with_public_data`` under ``args.reweight_cosface`` or ``FEDFR_FUSED_BRANCH=0``, ``ShardedHeadTrainer``'s private BCE branch
+  and every caller that composes ``FC_module`` / ``BCE_module`` / the margin modules itself go through ``FusedHeadTrainer``: the
+  backbone step is the same, the head is a Python closure of HIP-backed ``autograd.Function``s evaluated under ``torch.enable_grad()``.
 """
 from __future__ import annotations
 
@@ -537,6 +546,126 @@ class FusedHeadTrainer(_BackboneTrainer):
         return loss.detach()
 
 
+def public_head_loss(margin, fc_module, bce_module=None, bce_loss=None, detach=False, reweight=None, state=None, temperature=0.5,
+                     mu=0.0, bce_weight=10):
+    """The head of ``train_with_public_data`` as the closure ``FusedHeadTrainer.step`` evaluates under autograd: ``head_loss(feats, labels)
+    -> (loss, cos_loss, con_loss | None, bce_loss | None)``.  ``bce_module`` None: no BCE term; ``state`` None: no contrastive term, else
+    the dict whose ``global_feats`` / ``last_feats`` the caller refreshes every step; ``reweight``: ``Client.reweight_cosface``.  What
+    ``FusedBranchTrainer`` computes without autograd (``reweight`` excepted); tools/branch_step_bench.py times the two against each other."""
+    def head_loss(feats, labels):
+        cos_logits = margin(fc_module(feats), labels)
+        if reweight is not None:
+            cos_logits = reweight(cos_logits, labels)
+        cos_loss = ops.cross_entropy(cos_logits, labels)
+        loss = cos_loss
+        bce = con = None
+        if bce_module is not None:
+            bce_logits, bce_gts = bce_module(feats.detach() if detach else feats, labels)
+            bce = bce_loss(bce_logits, bce_gts)
+            loss = loss + bce_weight * bce
+        if state is not None:
+            con = ops.contrastive_loss(feats, state["global_feats"], state["last_feats"], temperature)
+            loss = loss + mu * con
+        return loss, cos_loss, con, bce
+    return head_loss
+
+
+class FusedBranchTrainer(_BackboneTrainer):
+    """The training body of ``train_with_public_data`` (reference client.py:354-441) without autograd: ``_forward``, ONE ``fedfr_branch_head``
+    call (csrc/branch.hip: losses, d(loss)/d(features) and the gradient of every head parameter), the backbone's backward pass and the SGD
+    updates.  loss = CE(margin(fc_module(f))) + bce_weight * BCE(bce_module(f or f.detach())) + mu * contrastive(f, f_global, f_last);
+    the BCE term needs ``bce_module``, the contrastive term the two extra embeddings in ``step``.  Head parameters get torch.optim.SGD
+    semantics exactly as in ``FusedHeadTrainer`` (momentum buffer created on first use, coupled weight decay)."""
+
+    def __init__(self, backbone: "backbones.IResNet", fc_module: FC_module, bce_module: Optional[BCE_module] = None,
+                 loss_name: str = "CosFace", s: float = 30.0, m: float = 0.4, detach: bool = False, mu: float = 0.0,
+                 temperature: float = 0.5, bce_weight: float = 10.0, bce_r: float = 30.0, bce_lambda: float = 0.7, lr: float = 0.1,
+                 momentum: float = 0.9, weight_decay: float = 5e-4, aux_slot: int = 0):
+        if loss_name not in ("CosFace", "ArcFace"):
+            raise ValueError("loss must be CosFace or ArcFace")
+        self.arc, self.s, self.m = loss_name == "ArcFace", float(s), float(m)
+        self.fc_module, self.bce_module = fc_module, bce_module
+        self.detach, self.con_mu, self.temperature = bool(detach), float(mu), float(temperature)
+        self.bce_weight, self.bce_r, self.bce_lambda = float(bce_weight), float(bce_r), float(bce_lambda)
+        self.conv_kind, self.conv_params = 0, []
+        if bce_module is not None:
+            if float(bce_module.r) != self.bce_r:               # one r scales the logits and the loss (client.py:33, losses.py:5): the kernel takes one
+                raise ValueError("FusedBranchTrainer: BCE_module.r (%g) and the BCE loss's r (%g) differ" % (bce_module.r, self.bce_r))
+            conv = bce_module.converter
+            self.conv_kind = 2 if isinstance(conv, BottleBlock) else 1
+            self.conv_params = list(conv.parameters())          # Linear: weight, bias; BottleBlock: the 18 tensors in the C ABI's order
+            if len(self.conv_params) != (18 if self.conv_kind == 2 else 2):
+                raise RuntimeError("FusedBranchTrainer: unexpected converter (%d parameters)" % len(self.conv_params))
+        # opt.step() order of the closure path: fc_module's parameters, then bce_module's
+        self.head_params = list(fc_module.parameters()) + (list(bce_module.parameters()) if bce_module is not None else [])
+        for hp in self.head_params:
+            _C.require_gpu_tensor(hp.data, f32, "head parameter")
+        self.head_grads = {}
+        self.head_mom = {}
+        self._ws = None
+        super().__init__(backbone, lr, momentum, weight_decay, aux_slot)
+
+    def _grad(self, p):
+        g = self.head_grads.get(p)
+        if g is None or g.shape != p.data.shape:
+            g = self.head_grads[p] = torch.empty_like(p.data)
+        return g
+
+    @torch.no_grad()
+    def head(self, feats, labels, global_feats=None, last_feats=None):
+        """The head alone on embeddings ``feats`` [B, D]: -> (losses [4] = total, cos, contrastive, bce on the device, dfeats [B, D]); the
+        parameter gradients land in ``self.head_grads``."""
+        feats = _C.require_gpu_tensor(feats, f32, "features")
+        B, D = feats.shape
+        fc = _C.require_gpu_tensor(self.fc_module.fc.data, f32, "fc weight")
+        C = fc.shape[0]
+        con = global_feats is not None
+        if con:
+            global_feats = ops._chk(global_feats, "global_feats")
+            last_feats = ops._chk(last_feats, "last_feats")
+            if global_feats.shape != feats.shape or last_feats.shape != feats.shape:
+                raise RuntimeError("FusedBranchTrainer: feats / global_feats / last_feats must have the same [B, D] shape")
+        bm = self.bce_module
+        n_class = bm.n_class if bm is not None else 0
+        cp = cg = None
+        if bm is not None:
+            n = len(self.conv_params)
+            cp = (ctypes.c_void_p * n)(*[_C.require_gpu_tensor(p.data, f32, "converter parameter").data_ptr() for p in self.conv_params])
+            cg = (ctypes.c_void_p * n)(*[self._grad(p).data_ptr() for p in self.conv_params])
+            _C.require_gpu_tensor(bm.weight.data, f32, "bce weight")
+            _C.require_gpu_tensor(bm.bias.data, f32, "bce bias")
+        nbytes = _C.lib().fedfr_branch_workspace_bytes(B, D, C, n_class, self.conv_kind, 1 if self.detach else 0, 1 if con else 0)
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=feats.device)
+        losses = torch.empty(4, dtype=f32, device=feats.device)
+        dfeats = torch.empty_like(feats)
+        _C.call("fedfr_branch_head", feats.data_ptr(), labels.data_ptr(), B, D, fc.data_ptr(), C, 1 if self.arc else 0, self.s, self.m,
+                self.conv_kind, cp, _C.ptr(bm.weight.data) if bm is not None else None, _C.ptr(bm.bias.data) if bm is not None else None,
+                n_class, float(bm.m) if bm is not None else 0.0, float(bm.r) if bm is not None else 1.0, float(bm.t) if bm is not None else 1.0,
+                self.bce_lambda, self.bce_weight, _C.ptr(global_feats) if con else None, _C.ptr(last_feats) if con else None,
+                self.temperature, self.con_mu, 1 if self.detach else 0, losses.data_ptr(), dfeats.data_ptr(),
+                self._grad(self.fc_module.fc).data_ptr(), cg, self._grad(bm.weight).data_ptr() if bm is not None else None,
+                self._grad(bm.bias).data_ptr() if bm is not None else None, self._ws.data_ptr(), nbytes, _C.stream())
+        return losses, dfeats
+
+    @_C.on_device(lambda self: self.bb.device)
+    @torch.no_grad()
+    def step(self, imgs: torch.Tensor, labels: torch.Tensor, global_feats=None, last_feats=None):
+        """-> (loss, cos_loss, con_loss or None, bce_loss or None), detached device scalars."""
+        plan, feats, labels = self._forward(imgs, labels)
+        losses, dfeats = self.head(feats, labels, global_feats, last_feats)
+        self._backward(plan, imgs, dfeats, self.fuse_sgd, unscale=False)
+        self._update_backbone()
+        for hp in self.head_params:
+            buf = self.head_mom.get(hp)
+            first = buf is None
+            if first:
+                buf = self.head_mom[hp] = torch.empty_like(hp.data)
+            ops.sgd_step(hp.data, self.head_grads[hp], buf, None, hp.numel(), self.lr, self.mu, self.wd, first, overflow=self._sgd_overflow)
+        self._end_step()
+        return losses[0], losses[1], losses[2] if global_feats is not None else None, losses[3] if self.bce_module is not None else None
+
+
 class ShardedHeadTrainer(FusedHeadTrainer):
     """BASELINE config 5 — "iresnet100 + CosFace + personalized transform head, 8 clients = 8 MI355X, PartialFC class-sharded across
     GPUs".  The reference never runs this combination (its clients own private dense heads, client.py:149; its PartialFC is dead
@@ -906,26 +1035,21 @@ class Client(object):
         if callback_verification is not None and start_epoch == 0:             # client.py:331-333
             self.logger.info('Pretrain Local testing')
             callback_verification.veri_test(backbone, -1, self.target_ID, self.cid)
-        trainer = FusedHeadTrainer(backbone, head_params, lr=cfg.lr, momentum=cfg.momentum, weight_decay=cfg.weight_decay,
-                                   aux_slot=getattr(self, "slot", 0))
-        margin, fc_module = self.margin_softmax, self.fc_module
+        # the whole head as one fused call, unless the reference's re-weighting quirk detaches the cos branch or FEDFR_FUSED_BRANCH=0
+        fused = not reweight and os.environ.get("FEDFR_FUSED_BRANCH", "1") != "0"
+        if fused:
+            trainer = FusedBranchTrainer(backbone, self.fc_module, self.bce_module if use_bce else None, self.loss_name,
+                                         self.margin_softmax.s, self.margin_softmax.m, detach=detach, mu=cfg.mu if use_con else 0.0,
+                                         temperature=self.temperature if use_con else 0.5, bce_weight=10.0, bce_r=self.bce_loss.r if use_bce else 30.0,
+                                         bce_lambda=self.bce_loss.lambda_ if use_bce else 0.7, lr=cfg.lr, momentum=cfg.momentum,
+                                         weight_decay=cfg.weight_decay, aux_slot=getattr(self, "slot", 0))
+        else:
+            trainer = FusedHeadTrainer(backbone, head_params, lr=cfg.lr, momentum=cfg.momentum, weight_decay=cfg.weight_decay,
+                                       aux_slot=getattr(self, "slot", 0))
         state = {}
-
-        def head_loss(feats, labels):
-            cos_logits = margin(fc_module(feats), labels)
-            if reweight:
-                cos_logits = self.reweight_cosface(cos_logits, labels)
-            cos_loss = ops.cross_entropy(cos_logits, labels)
-            loss = cos_loss
-            bce = con = None
-            if use_bce:
-                bce_logits, bce_gts = self.bce_module(feats.detach() if detach else feats, labels)
-                bce = self.bce_loss(bce_logits, bce_gts)
-                loss = loss + 10 * bce
-            if use_con:
-                con = ops.contrastive_loss(feats, state["global_feats"], state["last_feats"], self.temperature)
-                loss = loss + cfg.mu * con
-            return loss, cos_loss, con, bce
+        head_loss = public_head_loss(self.margin_softmax, self.fc_module, self.bce_module if use_bce else None,
+                                     self.bce_loss if use_bce else None, detach, self.reweight_cosface if reweight else None,
+                                     state if use_con else None, self.temperature if use_con else 0.5, cfg.mu)
 
         loss_meter, cos_meter, con_meter, bce_meter = AverageMeter(), AverageMeter(), AverageMeter(), AverageMeter()
         pending = []
@@ -949,7 +1073,10 @@ class Client(object):
                     with torch.no_grad():
                         state["global_feats"] = global_model(imgs)
                         state["last_feats"] = self.last_model(imgs)
-                pending.append(trainer.step(imgs, labels, head_loss))
+                if fused:
+                    pending.append(trainer.step(imgs, labels, state.get("global_feats"), state.get("last_feats")))
+                else:
+                    pending.append(trainer.step(imgs, labels, head_loss))
                 if len(pending) >= self.sync_every:
                     drain()
         drain()

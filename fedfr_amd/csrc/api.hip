@@ -665,6 +665,27 @@ int fedfr_bottle_backward(const float* x, const float* const* params, const floa
                           float* dx, float* const* grads, void* ws, size_t ws_bytes, void* stream) {
   return bottle_backward(x, params, h1, h2, dy, B, D, dx, grads, ws, ws_bytes, ST(stream));
 }
+size_t fedfr_bce_fused_workspace_bytes(int B, int C) { return branch_bce_workspace_bytes(B, C); }
+int fedfr_bce_fused(const float* cosv, const long long* label, const float* bias, int B, int C, float m, float r, float t, float lam,
+                    float loss_scale, float* row_loss, float* dcos, float* dbias, void* ws, size_t ws_bytes, void* stream) {
+  return branch_bce_fused(cosv, label, bias, B, C, m, r, t, lam, loss_scale, row_loss, dcos, dbias, ws, ws_bytes, ST(stream));
+}
+int fedfr_branch_dfeats(const float* xn, const float* inv_norm, const float* dxn, int nslab, long long slab_stride, const float* dbce,
+                        const float* dcon, float mu, float* dfeats, int B, int D, void* stream) {
+  return branch_dfeats(xn, inv_norm, dxn, nslab, slab_stride, dbce, dcon, mu, dfeats, B, D, ST(stream));
+}
+size_t fedfr_branch_workspace_bytes(int B, int D, int C, int n_class, int converter, int detach, int contrastive) {
+  return branch_workspace_bytes(B, D, C, n_class, converter, detach, contrastive);
+}
+int fedfr_branch_head(const float* feats, const long long* labels, int B, int D, const float* fc, int C, int arcface, float s, float m,
+                      int converter, const float* const* converter_params, const float* bce_weight, const float* bce_bias, int n_class,
+                      float bce_m, float bce_r, float bce_t, float bce_lambda, float bce_scale, const float* global_feats,
+                      const float* last_feats, float temperature, float mu, int detach, float* losses, float* dfeats, float* dfc,
+                      float* const* converter_grads, float* dbce_weight, float* dbce_bias, void* ws, size_t ws_bytes, void* stream) {
+  return branch_head(feats, labels, B, D, fc, C, arcface, s, m, converter, converter_params, bce_weight, bce_bias, n_class, bce_m, bce_r, bce_t,
+                     bce_lambda, bce_scale, global_feats, last_feats, temperature, mu, detach, losses, dfeats, dfc, converter_grads, dbce_weight,
+                     dbce_bias, ws, ws_bytes, ST(stream));
+}
 size_t fedfr_verif_workspace_bytes(int P, int nfolds) { return verif_workspace_bytes(P, nfolds); }
 int fedfr_verif_fold_counts(const void* emb0, const void* emb1, int fp64_input, int normalize, const unsigned char* issame, int P, int D,
                             int nfolds, const double* thr_a, int Ta, const double* thr_b, int Tb, unsigned long long* counts_a,

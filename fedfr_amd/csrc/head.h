@@ -77,3 +77,14 @@ size_t bottle_workspace_bytes(int B, int D);
 int bottle_forward(const float* x, const float* const* params, int B, int D, float* h1, float* h2, float* y, hipStream_t st);
 int bottle_backward(const float* x, const float* const* params, const float* h1, const float* h2, const float* dy, int B, int D, float* dx,
                     float* const* grads, void* ws, size_t ws_bytes, hipStream_t st);
+// fused head of train_with_public_data (branch.hip): BCE in one pass, the embedding gradient of all branches in one pass, the whole head as one call
+size_t branch_bce_workspace_bytes(int B, int C);
+int branch_bce_fused(const float* cosv, const long long* label, const float* bias, int B, int C, float m, float r, float t, float lam,
+                     float loss_scale, float* row_loss, float* dcos, float* dbias, void* ws, size_t ws_bytes, hipStream_t st);
+int branch_dfeats(const float* xn, const float* inv, const float* dxn, int nslab, long long slab_stride, const float* dbce, const float* dcon,
+                  float mu, float* dfeats, int B, int D, hipStream_t st);
+size_t branch_workspace_bytes(int B, int D, int C, int n_class, int conv, int detach, int contrastive);
+int branch_head(const float* feats, const long long* labels, int B, int D, const float* fc, int C, int arc, float s, float m, int conv,
+                const float* const* conv_params, const float* bce_w, const float* bce_b, int n_class, float bce_m, float bce_r, float bce_t,
+                float bce_lam, float bce_scale, const float* gfeats, const float* lfeats, float temperature, float mu, int detach, float* losses,
+                float* dfeats, float* dfc, float* const* conv_grads, float* dbce_w, float* dbce_b, void* ws, size_t ws_bytes, hipStream_t st);

@@ -424,6 +424,35 @@ size_t fedfr_bottle_workspace_bytes(int B, int D);
 int fedfr_bottle_forward(const float* x, const float* const* params, int B, int D, float* h1, float* h2, float* y, void* stream);
 int fedfr_bottle_backward(const float* x, const float* const* params, const float* h1, const float* h2, const float* dy, int B, int D,
                           float* dx, float* const* grads, void* ws, size_t ws_bytes, void* stream);
+/* Fused head of train_with_public_data (client.py:354-441; csrc/branch.hip), fp32, deterministic: no floating-point atomics anywhere.
+ * fedfr_bce_fused: the personalised head's elementwise part in ONE pass over cos [B][C] (definitions: fedfr_bce_logits / fedfr_bce_loss above):
+ *   row_loss[b] = sum_c bce(z[b][c], label[b] == c), dcos = d(loss_scale * mean_b row_loss)/dcos, dbias[c] = sum_b dz[b][c]; z, gt and dz/dcos are
+ *   never stored.  A label outside [0, C) is an all-negative row.  dbias: one partial row per workgroup of 16 rows, added in ascending order by a
+ *   second launch.  dcos must not alias cos.  ws: fedfr_bce_fused_workspace_bytes(B, C) bytes of device memory (0 for unsupported sizes). */
+size_t fedfr_bce_fused_workspace_bytes(int B, int C);
+int fedfr_bce_fused(const float* cosv, const long long* label, const float* bias, int B, int C, float m, float r, float t, float lam,
+                    float loss_scale, float* row_loss, float* dcos, float* dbias, void* ws, size_t ws_bytes, void* stream);
+/* dfeats = fedfr_normalize_rows_bwd_slabs(xn, inv_norm, dxn slabs) + dbce + mu * dcon in one pass over [B][D]; dbce (the BCE branch's gradient
+ * wrt the converter input) and dcon (the contrastive gradient) may each be NULL. */
+int fedfr_branch_dfeats(const float* xn, const float* inv_norm, const float* dxn, int nslab, long long slab_stride, const float* dbce,
+                        const float* dcon, float mu, float* dfeats, int B, int D, void* stream);
+/* The whole head as one call on the caller's stream:
+ *   loss = CE(s * margin(cos(feats, fc)), labels) + bce_scale * BCE(cos(converter(feats), bce_weight); bce_bias) + mu * contrastive(feats, ...)
+ * feats [B][D], labels [B] in [0, C), fc [C][D] (the first n_class rows are the local identities), arcface 0 = CosFace / 1 = ArcFace with s, m.
+ * converter: 0 = no BCE branch (every bce / converter argument is ignored), 1 = Linear (converter_params = HOST array {weight [D][D], bias [D]}),
+ * 2 = BottleBlock (HOST array of 18 device pointers as fedfr_bottle_forward takes them; D a multiple of 64 in [64, 512]); converter_grads: the
+ * same layout, written.  bce_weight [n_class][D], bce_bias [n_class]; labels >= n_class (public identities) are all-negative BCE rows.
+ * global_feats / last_feats [B][D]: both NULL = no contrastive term.  detach != 0: the BCE branch gives the embedding no gradient (BCE_detach).
+ * Outputs (all overwritten): losses[4] = total, cos, contrastive, bce (an absent term is 0); dfeats [B][D]; dfc [C][D]; converter_grads;
+ * dbce_weight [n_class][D]; dbce_bias [n_class].  The two identity-branch GEMMs run split-K when 256 <= C <= 4096 and D >= 256; beyond that the
+ * d(f_hat) GEMM alone does once C >= 1024 (a long reduction over few tiles); the slabs are added in order by their consumers.  Every argument is checked before the first launch.
+ * ws: fedfr_branch_workspace_bytes(...) bytes of device memory (0 for unsupported sizes); contrastive != 0 when global_feats is given. */
+size_t fedfr_branch_workspace_bytes(int B, int D, int C, int n_class, int converter, int detach, int contrastive);
+int fedfr_branch_head(const float* feats, const long long* labels, int B, int D, const float* fc, int C, int arcface, float s, float m,
+                      int converter, const float* const* converter_params, const float* bce_weight, const float* bce_bias, int n_class,
+                      float bce_m, float bce_r, float bce_t, float bce_lambda, float bce_scale, const float* global_feats,
+                      const float* last_feats, float temperature, float mu, int detach, float* losses, float* dfeats, float* dfc,
+                      float* const* converter_grads, float* dbce_weight, float* dbce_bias, void* ws, size_t ws_bytes, void* stream);
 /* k-fold 1:1 verification (eval/verification.py test / evaluate / calculate_roc / calculate_val) in one pass over the embeddings of a
  * verification set: emb0 [2P][D], emb1 [2P][D] (the flipped images' embeddings; NULL = no flip test), both fp32 (fp64_input = 0) or
  * fp64 (1); rows 2p and 2p + 1 form pair p, issame [P] uint8.  Per row, in fp64: s = emb0 + emb1, with normalize = 1 divided by
