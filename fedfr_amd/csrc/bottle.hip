@@ -5,8 +5,8 @@
 // h1 and h2 are stored [B][D] with branch g in columns g H .. (g + 1) H (the concatenation W3 consumes); the pre-activations never are:
 // slope 0.01 > 0, so h > 0 exactly when z > 0 and the backward takes leaky' from the sign of the stored activation (0.01 at 0, as torch).
 //
-// Two launches forward, two backward.  Every kernel is built from ONE masked 64x64 tile GEMM on v_mfma_f32_16x16x4_f32 (the k-ordered exact
-// fp32 FMA chain of head.hip's sgemm, same LDS layout); the block is launch-bound (1.18 MFLOP per row), so what matters is the launch count:
+// Two launches forward, two backward.  Every kernel is built from ONE masked 64x64 tile GEMM: the tile of tile64.h with fp32 accumulation (the
+// k-ordered exact fp32 FMA chain of head.hip's sgemm); the block is launch-bound (1.18 MFLOP per row), so what matters is the launch count:
 //   fwd 1  grid (row tiles, 4 branches): h1_g tile, barrier, h2_g tile from the block's own h1_g rows
 //   fwd 2  grid (D / 64, row tiles):     y
 //   bwd 1  grid (row tiles, 4 branches): dz2_g = (dy W3[:, g]) * leaky'(h2_g), barrier, dz1_g = (dz2_g W2_g) * leaky'(h1_g) -> workspace
@@ -14,10 +14,13 @@
 //          workgroup sum, no atomics; the tile of column block 0 also sums its bias gradient in a fixed order) and of dx = dy + dz1 W1
 // Parameters and gradients stay the 18 separate tensors: br1..br4 x (W1, b1, W2, b2), then W3, b3.
 #include "head.h"
+#include "tile64.h"
 
 namespace {
-constexpr int BK = 32, LD = 80, NL = BK / 4;      // 64x64 tile, 4 waves (2x2) of 32x32; k-major LDS rows, see sgemm_kernel (head.hip)
+constexpr int BK = 32;
 constexpr float SLOPE = 0.01f;                    // nn.LeakyReLU()
+using Smem = tile64::Lds<BK>;
+using tile64::zero;
 
 struct BottleP {
   const float* x;
@@ -33,89 +36,29 @@ struct BottleP {
   int B, D, H;
 };
 
-struct Smem {
-  float a[2][BK][LD], b[2][BK][LD];
-};
-
-__device__ __forceinline__ void zero(f32x4_t (&acc)[2][2]) {
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-}
-
 // acc[m][n] += sum_{k < K} A[m * sam + k * sak] * B[k * sbk + n * sbn] for m < min(64, mrem), n < min(64, nrem); rows and columns past the
 // limits read as 0.  Every thread of the block calls it; on return all waves are past the last read of the LDS tiles.
 __device__ __forceinline__ void tile_gemm(Smem& s, f32x4_t (&acc)[2][2], const float* A, long long sam, long long sak, int mrem, const float* B,
                                           long long sbk, long long sbn, int nrem, int K) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  float ra[NL], rb[NL];
+  const bool akf = sak == 1, bkf = sbn != 1;      // which operand is k-fastest in memory (uniform)
+  float ra[BK / 4], rb[BK / 4];
   auto load = [&](int k0) {
-#pragma unroll
-    for (int i = 0; i < NL; ++i) {
-      const int e = tid + 256 * i;
-      int m, k;
-      if (sak == 1) { k = e & (BK - 1); m = e / BK; } else { m = e & 63; k = e >> 6; }
-      ra[i] = (m < mrem && k0 + k < K) ? A[m * sam + (k0 + k) * sak] : 0.f;
-      int n, kb;
-      if (sbn == 1) { n = e & 63; kb = e >> 6; } else { kb = e & (BK - 1); n = e / BK; }
-      rb[i] = (n < nrem && k0 + kb < K) ? B[(k0 + kb) * sbk + n * sbn] : 0.f;
-    }
+    tile64::load<BK>(ra, akf, [&](int m, int k, int) { return (m < mrem && k0 + k < K) ? A[m * sam + (k0 + k) * sak] : 0.f; });
+    tile64::load<BK>(rb, bkf, [&](int n, int k, int) { return (n < nrem && k0 + k < K) ? B[(k0 + k) * sbk + n * sbn] : 0.f; });
   };
   auto store = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < NL; ++i) {
-      const int e = tid + 256 * i;
-      int m, k;
-      if (sak == 1) { k = e & (BK - 1); m = e / BK; } else { m = e & 63; k = e >> 6; }
-      s.a[buf][k][m ^ ((k >> 1) << 1)] = ra[i];
-      int n, kb;
-      if (sbn == 1) { n = e & 63; kb = e >> 6; } else { kb = e & (BK - 1); n = e / BK; }
-      s.b[buf][kb][n ^ ((kb >> 1) << 1)] = rb[i];
-    }
+    tile64::store(s, 0, buf, akf, ra);
+    tile64::store(s, 1, buf, bkf, rb);
   };
-  const int nk = ceil_div(K, BK);
-  load(0);
-  store(0);
-  __syncthreads();
-  const int l15 = lane & 15, lg = lane >> 4;
-  for (int kt = 0; kt < nk; ++kt) {
-    const int buf = kt & 1;
-    if (kt + 1 < nk) load((kt + 1) * BK);
-#pragma unroll
-    for (int k4 = 0; k4 < BK; k4 += 4) {
-      float fa[2], fb[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int kk = k4 + lg, sw = (kk >> 1) << 1;
-        fa[i] = s.a[buf][kk][(wm * 32 + i * 16 + l15) ^ sw];
-        fb[i] = s.b[buf][kk][(wn * 32 + i * 16 + l15) ^ sw];
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i], fb[j], acc[i][j], 0, 0, 0);
-    }
-    if (kt + 1 < nk) store(buf ^ 1);
-    __syncthreads();
-  }
+  tile64::k_loop<BK>(s, acc, 0, K, load, store);
 }
 
-// f(m, n, v) for every accumulator element of the tile inside the limits: m = wm*32 + i*16 + lg*4 + q, n = wn*32 + j*16 + l15
+// f(m, n, v) for every accumulator element of the tile inside the limits
 template <class F>
 __device__ __forceinline__ void for_each(const f32x4_t (&acc)[2][2], int mrem, int nrem, F f) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int wm = wave >> 1, wn = wave & 1, l15 = lane & 15, lg = lane >> 4;
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int m = wm * 32 + i * 16 + lg * 4 + q, n = wn * 32 + j * 16 + l15;
-        if (m < mrem && n < nrem) f(m, n, acc[i][j][q]);
-      }
+  tile64::for_each(acc, [&](int m, int n, float v) {
+    if (m < mrem && n < nrem) f(m, n, v);
+  });
 }
 
 __device__ __forceinline__ float leaky(float z) { return z > 0.f ? z : SLOPE * z; }
@@ -200,9 +143,9 @@ __device__ __forceinline__ void wgrad_tile(Smem& s, const BottleP& p, const floa
   float sum = 0.f;
   if (mo + c < M)
     for (int b = q; b < p.B; b += 4) sum += dO[(size_t)b * D + mo + c];
-  s.a[0][q][c] = sum;                                          // tile_gemm has returned: the LDS tiles are free
+  s.t[0][0][q][c] = sum;                                       // tile_gemm has returned: the LDS tiles are free
   __syncthreads();
-  if (q == 0 && mo + c < M) db[mo + c] = ((s.a[0][0][c] + s.a[0][1][c]) + s.a[0][2][c]) + s.a[0][3][c];
+  if (q == 0 && mo + c < M) db[mo + c] = ((s.t[0][0][0][c] + s.t[0][0][1][c]) + s.t[0][0][2][c]) + s.t[0][0][3][c];
 }
 
 __global__ __launch_bounds__(256) void bottle_bwd_tiles_kernel(BottleP p) {

@@ -22,6 +22,7 @@ typedef __attribute__((ext_vector_type(8))) _Float16 bf16x8_t;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 #endif
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
+typedef __attribute__((ext_vector_type(4))) double f64x4_t;
 typedef __attribute__((ext_vector_type(4))) short s16x4_t;
 typedef __attribute__((ext_vector_type(8))) short s16x8_t;
 

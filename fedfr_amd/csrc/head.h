@@ -37,6 +37,14 @@ int head_contrastive(const float* x, const float* g, const float* l, int B, int 
 int head_sgemm_colflag(const float* A, const float* B, int M, int N, int K, long long sam, long long sak, long long sbk,
                        long long sbn, float alpha, float thr, unsigned char* flags, hipStream_t st);
 int head_class_accumulate(const float* x, const long long* label, int B, int D, int C, float* sums, float* counts, hipStream_t st);
+// the ROC histogram slot of a pair score s (reference roc_cuda.py:14-30): bin = int((s + 1) * 1000), truncation as int() there, clamped to
+// [0, 2000] (the reference would write out of bounds instead); slot 2 * bin counts same-label pairs, 2 * bin + 1 different-label pairs
+constexpr int ROC_NBIN = 4002;
+__device__ __forceinline__ int roc_slot(double s, bool same) {
+  int bin = (int)((s + 1.0) * 1000.0);
+  bin = bin < 0 ? 0 : (bin > 2000 ? 2000 : bin);
+  return 2 * bin + (same ? 0 : 1);
+}
 int head_roc_histogram(const float* feat, const long long* label, int N, int D, int T, unsigned long long* hist, hipStream_t st);
 // grouped pair histogram (roc_groups.hip): G disjoint target sets in one pass over the unordered pairs; tile_group is HOST memory
 int head_roc_histogram_groups(const float* feat, const long long* label, int N, int D, const int* row_index, const int* tile_group,

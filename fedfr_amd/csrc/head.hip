@@ -3,6 +3,7 @@
 // (reference: client.py:69-74, losses.py:17-45, partial_fc.py:130-176), BCE personalised head elementwise part
 // (client.py:45-58, losses.py:4-15).  The head stays fp32: s=30..64 amplifies cosine error.
 #include "head.h"
+#include "tile64.h"
 
 // ---------------------------------------------------------------------------------------------------------
 // normalisation: one wave per row
@@ -101,7 +102,7 @@ int head_normalize_rows_bwd(const float* xn, const float* inv, const float* dxn,
 
 // ---------------------------------------------------------------------------------------------------------
 // strided fp32 GEMM  C[m][n] = alpha * sum_k A[m*sam + k*sak] * B[k*sbk + n*sbn] (+ bias[n]) (+ beta*C)
-// block tile 64x64, 4 waves (2x2) of 32x32, BK = 16, v_mfma_f32_16x16x4_f32
+// one 64x64 tile of tile64.h per workgroup, v_mfma_f32_16x16x4_f32
 // ---------------------------------------------------------------------------------------------------------
 #ifndef SGEMM_COLFLAG_BK
 #define SGEMM_COLFLAG_BK 16      // k depth of the hard-negative-mining GEMM (throughput-bound: measured per value below)
@@ -119,195 +120,87 @@ struct SgemmP {
   long long slab_stride;
 };
 
-template <int BK>      // k depth of a stage: 16, or 32 (half as many global-load round trips on the K loop: the head's 128 x 1000 x 512 GEMMs are a latency chain)
-__global__ __launch_bounds__(256) void sgemm_kernel(SgemmP p) {
-  constexpr int BM = 64, BN = 64, LD = 80, NL = BK / 4;   // k-major LDS rows; LD%32==16 + column XOR (k>>1)<<1: reads and writes conflict-free
-  __shared__ float sA[2][BK][LD], sB[2][BK][LD];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
-  float ra[NL], rb[NL];
+// One 64x64 tile of tile64.h per workgroup; Acc = f32x4_t: the exact fp32 FMA chain over k ascending, with the colflag and split-K forms;
+// Acc = f64x4_t: the same products accumulated in fp64 and rounded once (beta, bias and alpha applied in fp64).
+template <int BK, class Acc>      // BK: k depth of a stage: 16, or 32 (half as many global-load round trips on the K loop: the head's 128 x 1000 x 512 GEMMs are a latency chain)
+__device__ __forceinline__ void sgemm_tile(tile64::Lds<BK>& s, SgemmP& p) {
+  constexpr bool F64 = sizeof(Acc) == sizeof(f64x4_t);
+  const int m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
+  const bool akf = p.sak == 1, bkf = p.sbn != 1;            // which operand is k-fastest in memory (uniform)
+  float ra[BK / 4], rb[BK / 4];
   auto load = [&](int k0) {
-#pragma unroll
-    for (int i = 0; i < NL; ++i) {
-      const int e = tid + 256 * i;
-      int m, k;
-      if (p.sak == 1) { k = e & (BK - 1); m = e / BK; } else { m = e & 63; k = e >> 6; }
+    tile64::load<BK>(ra, akf, [&](int m, int k, int) {
       const int gm = m0 + m, gk = k0 + k;
-      ra[i] = (gm < p.M && gk < p.K) ? p.A[(long long)gm * p.sam + (long long)gk * p.sak] : 0.f;
-      int n, kb;
-      if (p.sbn == 1) { n = e & 63; kb = e >> 6; } else { kb = e & (BK - 1); n = e / BK; }
-      const int gn = n0 + n, gkb = k0 + kb;
-      rb[i] = (gn < p.N && gkb < p.K) ? p.B[(long long)gkb * p.sbk + (long long)gn * p.sbn] : 0.f;
-    }
+      return (gm < p.M && gk < p.K) ? p.A[(long long)gm * p.sam + (long long)gk * p.sak] : 0.f;
+    });
+    tile64::load<BK>(rb, bkf, [&](int n, int k, int) {
+      const int gn = n0 + n, gk = k0 + k;
+      return (gn < p.N && gk < p.K) ? p.B[(long long)gk * p.sbk + (long long)gn * p.sbn] : 0.f;
+    });
   };
   auto store = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < NL; ++i) {
-      const int e = tid + 256 * i;
-      int m, k;
-      if (p.sak == 1) { k = e & (BK - 1); m = e / BK; } else { m = e & 63; k = e >> 6; }
-      sA[buf][k][m ^ ((k >> 1) << 1)] = ra[i];
-      int n, kb;
-      if (p.sbn == 1) { n = e & 63; kb = e >> 6; } else { kb = e & (BK - 1); n = e / BK; }
-      sB[buf][kb][n ^ ((kb >> 1) << 1)] = rb[i];
-    }
+    tile64::store(s, 0, buf, akf, ra);
+    tile64::store(s, 1, buf, bkf, rb);
   };
-  f32x4_t acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) acc[a][b] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+  Acc acc[2][2];
+  tile64::zero(acc);
   // split-K: this block's k range (the loads mask k >= p.K, so the range end is made the problem's K for them)
-  const int kbeg = gridDim.z > 1 ? (int)blockIdx.z * p.kchunk : 0;
-  if (gridDim.z > 1) {
-    p.K = min(p.K, kbeg + p.kchunk);
-    p.C += (size_t)blockIdx.z * p.slab_stride;
-  }
-  const int nk = ceil_div(p.K - kbeg, BK);
-  load(kbeg);
-  store(0);
-  __syncthreads();
-  const int l15 = lane & 15, lg = lane >> 4;
-  for (int kt = 0; kt < nk; ++kt) {
-    const int buf = kt & 1;
-    if (kt + 1 < nk) load(kbeg + (kt + 1) * BK);
-#pragma unroll
-    for (int k4 = 0; k4 < BK; k4 += 4) {
-      float fa[2], fb[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int kk = k4 + lg, sw = (kk >> 1) << 1;
-        fa[i] = sA[buf][kk][(wm * 32 + i * 16 + l15) ^ sw];
-        fb[i] = sB[buf][kk][(wn * 32 + i * 16 + l15) ^ sw];
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i], fb[j], acc[i][j], 0, 0, 0);
+  int kbeg = 0;
+  if constexpr (!F64)
+    if (gridDim.z > 1) {
+      kbeg = (int)blockIdx.z * p.kchunk;
+      p.K = min(p.K, kbeg + p.kchunk);
+      p.C += (size_t)blockIdx.z * p.slab_stride;
     }
-    if (kt + 1 < nk) store(buf ^ 1);
-    __syncthreads();
-  }
-  // D[row = m][col = n]: m = wm*32 + i*16 + lg*4 + reg, n = wn*32 + j*16 + l15
-  if (p.colflag) {            // threshold + column-OR epilogue (hard-negative mining): every hit stores the same 1 -> order-free
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int n = n0 + wn * 32 + j * 16 + l15;
-      bool hit = false;
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int m = m0 + wm * 32 + i * 16 + lg * 4 + q;
-          hit |= m < p.M && p.alpha * acc[i][j][q] > p.thr;
-        }
-      if (hit && n < p.N) p.colflag[n] = 1;
-    }
-    return;
-  }
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int m = m0 + wm * 32 + i * 16 + lg * 4 + q, n = n0 + wn * 32 + j * 16 + l15;
-        if (m < p.M && n < p.N) {
-          float v = p.alpha * acc[i][j][q];
-          if (p.bias) v += p.bias[n];
-          float* c = p.C + (size_t)m * p.ldc + n;
-          if (p.beta != 0.f) v += p.beta * *c;
-          *c = v;
-        }
+  tile64::k_loop<BK>(s, acc, kbeg, p.K, load, store);
+  if constexpr (F64) {
+    tile64::for_each(acc, [&](int m, int n, double a) {
+      m += m0, n += n0;
+      if (m < p.M && n < p.N) {
+        double v = (double)p.alpha * a;
+        if (p.bias) v += (double)p.bias[n];
+        float* c = p.C + (size_t)m * p.ldc + n;
+        if (p.beta != 0.f) v += (double)p.beta * (double)*c;
+        *c = (float)v;
       }
+    });
+  } else {
+    if (p.colflag) {            // threshold + column-OR epilogue (hard-negative mining): every hit stores the same 1 -> order-free
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int n = n0 + tile64::col(j);
+        bool hit = false;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) hit |= m0 + tile64::row_f32(i, q) < p.M && p.alpha * acc[i][j][q] > p.thr;
+        if (hit && n < p.N) p.colflag[n] = 1;
+      }
+      return;
+    }
+    tile64::for_each(acc, [&](int m, int n, float a) {
+      m += m0, n += n0;
+      if (m < p.M && n < p.N) {
+        float v = p.alpha * a;
+        if (p.bias) v += p.bias[n];
+        float* c = p.C + (size_t)m * p.ldc + n;
+        if (p.beta != 0.f) v += p.beta * *c;
+        *c = v;
+      }
+    });
+  }
 }
-
-// Same GEMM with the products accumulated in fp64 (v_mfma_f64_16x16x4_f64 on the fp32 operands widened exactly): the result is the
-// correctly rounded fp32 value of the exact sum for all practical purposes.  Used by the fp32 validation path of the backbone (net_f32.hip),
-// whose weight-gradient GEMMs sum over up to 10^5 positions: a sequential fp32 accumulation of that length put it 3x further from the fp64
-// evaluation of a training step than the fp32 reference is.
+template <int BK>
+__global__ __launch_bounds__(256) void sgemm_kernel(SgemmP p) {
+  __shared__ tile64::Lds<BK> s;
+  sgemm_tile<BK, f32x4_t>(s, p);
+}
+// Used by the fp32 validation path of the backbone (net_f32.hip), whose weight-gradient GEMMs sum over up to 10^5 positions: a sequential
+// fp32 accumulation of that length put it 3x further from the fp64 evaluation of a training step than the fp32 reference is.
 template <int BK>
 __global__ __launch_bounds__(256) void sgemm_f64acc_kernel(SgemmP p) {
-  constexpr int BM = 64, BN = 64, LD = 80, NL = BK / 4;   // k-major LDS rows; LD%32==16 + column XOR (k>>1)<<1: reads and writes conflict-free
-  __shared__ float sA[2][BK][LD], sB[2][BK][LD];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
-  float ra[NL], rb[NL];
-  auto load = [&](int k0) {
-#pragma unroll
-    for (int i = 0; i < NL; ++i) {
-      const int e = tid + 256 * i;
-      int m, k;
-      if (p.sak == 1) { k = e & (BK - 1); m = e / BK; } else { m = e & 63; k = e >> 6; }
-      const int gm = m0 + m, gk = k0 + k;
-      ra[i] = (gm < p.M && gk < p.K) ? p.A[(long long)gm * p.sam + (long long)gk * p.sak] : 0.f;
-      int n, kb;
-      if (p.sbn == 1) { n = e & 63; kb = e >> 6; } else { kb = e & (BK - 1); n = e / BK; }
-      const int gn = n0 + n, gkb = k0 + kb;
-      rb[i] = (gn < p.N && gkb < p.K) ? p.B[(long long)gkb * p.sbk + (long long)gn * p.sbn] : 0.f;
-    }
-  };
-  auto store = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < NL; ++i) {
-      const int e = tid + 256 * i;
-      int m, k;
-      if (p.sak == 1) { k = e & (BK - 1); m = e / BK; } else { m = e & 63; k = e >> 6; }
-      sA[buf][k][m ^ ((k >> 1) << 1)] = ra[i];
-      int n, kb;
-      if (p.sbn == 1) { n = e & 63; kb = e >> 6; } else { kb = e & (BK - 1); n = e / BK; }
-      sB[buf][kb][n ^ ((kb >> 1) << 1)] = rb[i];
-    }
-  };
-  typedef __attribute__((ext_vector_type(4))) double f64x4_acc_t;
-  f64x4_acc_t acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) acc[a][b] = (f64x4_acc_t){0.0, 0.0, 0.0, 0.0};
-  const int nk = ceil_div(p.K, BK);
-  load(0);
-  store(0);
-  __syncthreads();
-  const int l15 = lane & 15, lg = lane >> 4;
-  for (int kt = 0; kt < nk; ++kt) {
-    const int buf = kt & 1;
-    if (kt + 1 < nk) load((kt + 1) * BK);
-#pragma unroll
-    for (int k4 = 0; k4 < BK; k4 += 4) {
-      float fa[2], fb[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int kk = k4 + lg, sw = (kk >> 1) << 1;
-        fa[i] = sA[buf][kk][(wm * 32 + i * 16 + l15) ^ sw];
-        fb[i] = sB[buf][kk][(wn * 32 + i * 16 + l15) ^ sw];
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)fa[i], (double)fb[j], acc[i][j], 0, 0, 0);
-    }
-    if (kt + 1 < nk) store(buf ^ 1);
-    __syncthreads();
-  }
-  // f64 16x16x4 accumulator layout (differs from the f32 form): register q of lane l holds D[row = 4 q + (l >> 4)][col = l & 15]
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int m = m0 + wm * 32 + i * 16 + 4 * q + lg, n = n0 + wn * 32 + j * 16 + l15;
-        if (m < p.M && n < p.N) {
-          double v = (double)p.alpha * acc[i][j][q];
-          if (p.bias) v += (double)p.bias[n];
-          float* c = p.C + (size_t)m * p.ldc + n;
-          if (p.beta != 0.f) v += (double)p.beta * (double)*c;
-          *c = (float)v;
-        }
-      }
+  __shared__ tile64::Lds<BK> s;
+  sgemm_tile<BK, f64x4_t>(s, p);
 }
 
 int head_sgemm(const float* A, const float* B, float* C, int M, int N, int K, long long sam, long long sak,
@@ -818,84 +711,36 @@ int head_contrastive(const float* x, const float* g, const float* l, int B, int 
 // integer atomics (order-free -> deterministic).  Pairs (a, b): a < b, a < T (the T target rows come first), b < N.
 // hist[2 * bin] counts same-label pairs, hist[2 * bin + 1] different-label pairs.
 // ---------------------------------------------------------------------------------------------------------
-typedef __attribute__((ext_vector_type(4))) double f64x4_t;
 __global__ __launch_bounds__(256) void roc_hist_kernel(const float* __restrict__ feat, const long long* __restrict__ label, int N, int D,
                                                        int T, unsigned long long* __restrict__ hist) {
-  constexpr int BK = 16, LD = 80, NBIN = 4002;
-  __shared__ float sA[2][BK][LD], sB[2][BK][LD];
-  __shared__ unsigned lh[NBIN];
+  constexpr int BK = 16;
+  __shared__ tile64::Lds<BK> s;
+  __shared__ unsigned lh[ROC_NBIN];
   const int a0 = blockIdx.y * 64, b0 = blockIdx.x * 64;
   if (b0 + 63 <= a0) return;                                  // tile entirely on / below the diagonal: no pair with a < b
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  for (int i = tid; i < NBIN; i += 256) lh[i] = 0u;
+  const int tid = threadIdx.x;
+  for (int i = tid; i < ROC_NBIN; i += 256) lh[i] = 0u;
   float ra[4], rb[4];
+  auto row = [&](int g, int lim, int gk) { return (g < lim && gk < D) ? feat[(size_t)g * D + gk] : 0.f; };   // features are row-major: k fastest
   auto load = [&](int k0) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int e = tid + 256 * i, k = e & 15, m = e >> 4;   // features are row-major: k fastest
-      const int ga = a0 + m, gb = b0 + m, gk = k0 + k;
-      ra[i] = (ga < T && gk < D) ? feat[(size_t)ga * D + gk] : 0.f;
-      rb[i] = (gb < N && gk < D) ? feat[(size_t)gb * D + gk] : 0.f;
-    }
+    tile64::load<BK>(ra, true, [&](int m, int k, int) { return row(a0 + m, T, k0 + k); });
+    tile64::load<BK>(rb, true, [&](int m, int k, int) { return row(b0 + m, N, k0 + k); });
   };
   auto store = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int e = tid + 256 * i, k = e & 15, m = e >> 4;
-      sA[buf][k][m ^ ((k >> 1) << 1)] = ra[i];
-      sB[buf][k][m ^ ((k >> 1) << 1)] = rb[i];
-    }
+    tile64::store(s, 0, buf, true, ra);
+    tile64::store(s, 1, buf, true, rb);
   };
   f64x4_t acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) acc[a][b] = (f64x4_t){0.0, 0.0, 0.0, 0.0};
-  const int nk = ceil_div(D, BK);
-  load(0);
-  store(0);
+  tile64::zero(acc);
+  tile64::k_loop<BK>(s, acc, 0, D, load, store);
+  tile64::for_each(
+      acc, [&](int n) { return b0 + n < N ? label[b0 + n] : 0; },
+      [&](int m, int n, double v, long long lb) {
+        const int a = a0 + m, b = b0 + n;
+        if (a < b && a < T && b < N) atomicAdd(&lh[roc_slot(v, label[a] == lb)], 1u);
+      });
   __syncthreads();
-  const int l15 = lane & 15, lg = lane >> 4;
-  for (int kt = 0; kt < nk; ++kt) {
-    const int buf = kt & 1;
-    if (kt + 1 < nk) load((kt + 1) * BK);
-#pragma unroll
-    for (int k4 = 0; k4 < BK; k4 += 4) {
-      double fa[2], fb[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int kk = k4 + lg, sw = (kk >> 1) << 1;
-        fa[i] = (double)sA[buf][kk][(wm * 32 + i * 16 + l15) ^ sw];
-        fb[i] = (double)sB[buf][kk][(wn * 32 + i * 16 + l15) ^ sw];
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[i], fb[j], acc[i][j], 0, 0, 0);
-    }
-    if (kt + 1 < nk) store(buf ^ 1);
-    __syncthreads();
-  }
-  // f64 16x16x4 accumulator layout (differs from the f32 form): register q of lane l holds D[row = 4 q + (l >> 4)][col = l & 15]
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int b = b0 + wn * 32 + j * 16 + l15;
-    const long long lb = b < N ? label[b] : 0;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int a = a0 + wm * 32 + i * 16 + q * 4 + lg;
-        if (a < b && a < T && b < N) {
-          int bin = (int)((acc[i][j][q] + 1.0) * 1000.0);           // truncation, as int() in the reference
-          bin = bin < 0 ? 0 : (bin > 2000 ? 2000 : bin);             // (the reference would write out of bounds instead)
-          atomicAdd(&lh[2 * bin + (label[a] == lb ? 0 : 1)], 1u);
-        }
-      }
-  }
-  __syncthreads();
-  for (int i = tid; i < NBIN; i += 256)
+  for (int i = tid; i < ROC_NBIN; i += 256)
     if (lh[i]) atomicAdd(&hist[i], (unsigned long long)lh[i]);
 }
 int head_roc_histogram(const float* feat, const long long* label, int N, int D, int T, unsigned long long* hist, hipStream_t st) {

@@ -3,11 +3,11 @@
 // over all queries the exact top-K (K <= 4096) of the negative scores; the query x gallery matrix is never written to memory.
 //
 // ident64_tile_kernel<CAP>, CAP > 0 (sweep 1): a work item is a 64-row query tile x a group of 8 column chunks; workgroup x takes items
-// x, x + X, ...  A chunk is one 64 x 64 tile of v_mfma_f64_16x16x4_f64 on fp64 operand tiles, the K loop of ident_tile_kernel: k ascending
-// in steps of 4, zero-padded to a multiple of 16, so a score is the same fp64 number whichever workgroup computes it and, on
-// fp32-representable features, the number ident.hip computes.  Epilogue as there: column mask[q] writes pos[q], every other score that
-// beats the workgroup's running K-th bound goes to an LDS candidate buffer of CAP entries, cut back to K by a descending bitonic sort when
-// it fills.  ident64_merge_kernel<CAP> runs the same buffer over the X sorted slabs.  CAP = 4096 for K <= 1024, 8192 (64 KiB) above.
+// x, x + X, ...  A chunk is one 64 x 64 tile of v_mfma_f64_16x16x4_f64 on fp64 operand tiles (its own LDS layout, below) under the pipeline,
+// the MFMA step and the accumulator walk of tile64.h: k ascending in steps of 4, zero-padded to a multiple of 16, so a score is the same fp64
+// number whichever workgroup computes it and, on fp32-representable features, the number ident.hip computes.  Epilogue as there: column
+// mask[q] writes pos[q], every other score that beats the workgroup's running K-th bound goes to the LDS candidate buffer of topk_cand.h at
+// CAP entries.  ident64_merge_kernel<CAP> runs the same buffer over the X sorted slabs.  CAP = 4096 for K <= 1024, 8192 (64 KiB) above.
 // ident64_tile_kernel<0> (sweep 2) recomputes the tiles and counts each row's scores against the pos of sweep 1: 8 rows x 2 counters per
 // lane, summed per item in LDS and added to rank_gt / rank_eq with integer atomics.  pos[q] is not known when sweep 1 meets the first
 // columns of row q; keeping a per-row list of "maybe above" scores instead would need Q x (unbounded) storage for hard probes, so the
@@ -19,6 +19,8 @@
 // at CAP 4096 (2 workgroups per CU), 100 KiB at CAP 8192 (1 per CU); sweep 2 adds 512 B of counters (its 180 VGPRs allow 2 per CU).
 #include <algorithm>
 #include "head.h"
+#include "tile64.h"
+#include "topk_cand.h"
 
 namespace {
 
@@ -27,81 +29,12 @@ constexpr int kChunks = 8;            // 64-column chunks per work item
 constexpr int BK = 16, LDK = BK + 2;  // K step and LDS row pitch in doubles
 constexpr int kTileBytes = 2 * 2 * 64 * LDK * (int)sizeof(double);
 constexpr int kRankWgs = 1024;        // sweep 2: 256 CUs x 2 resident x 2 rounds
-typedef __attribute__((ext_vector_type(4))) double f64x4_t;
 
-struct CandHdr {
-  double thr;                         // a value <= thr cannot enter the top-K (K values >= thr are held)
-  unsigned long long negs;
-  int n;                              // candidates written (may run past CAP while a chunk overflows)
-  int pad;
-};
 static_assert(sizeof(CandHdr) <= 32, "the candidates start 32 bytes after the header");
 
 constexpr int cand_bytes(int cap) { return 32 + cap * (int)sizeof(double); }
 constexpr int cap_for(int K) { return K <= 1024 ? 4096 : 8192; }                 // capacity well above K: a cut always leaves room
 inline int topk_wgs(int K) { return K <= 1024 ? 512 : 256; }                     // sweep 1: 256 CUs x resident workgroups
-
-__device__ __forceinline__ void cand_init(CandHdr& h) {
-  if (threadIdx.x == 0) {
-    h.n = 0;
-    h.thr = -INFINITY;
-    h.negs = 0ull;
-  }
-}
-
-// Sort v[0, n) descending (padded with -inf to a power of two >= 64), keep min(n, K) of it and raise thr to the K-th value.  Called by
-// the whole workgroup after a barrier that follows the last write to the buffer.
-template <int CAP>
-__device__ void cand_cut(CandHdr& h, double* v, int K) {
-  const int tid = threadIdx.x;
-  const int n = min(h.n, CAP);
-  int n2 = 64;
-  while (n2 < n) n2 <<= 1;
-  for (int i = n + tid; i < n2; i += 256) v[i] = -INFINITY;
-  __syncthreads();
-  for (int k = 2; k <= n2; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < (n2 >> 1); i += 256) {
-        const int lo = ((i & ~(j - 1)) << 1) | (i & (j - 1)), hi = lo + j;
-        const double a = v[lo], b = v[hi];
-        if ((lo & k) == 0 ? a < b : a > b) {
-          v[lo] = b;
-          v[hi] = a;
-        }
-      }
-      __syncthreads();
-    }
-  if (tid == 0) {
-    const int m = min(n, K);
-    h.n = m;
-    if (m == K) h.thr = v[K - 1];
-  }
-  __syncthreads();
-}
-
-// Offer this thread's values x[i] (bit i of pend set) to the buffer; every thread of the workgroup calls it (it holds barriers).  Values
-// that find the buffer full stay pending across a cut.
-template <int CAP, int NV>
-__device__ __forceinline__ void cand_offer(CandHdr& h, double* v, const double (&x)[NV], unsigned pend, int K) {
-  for (;;) {
-    const double thr = h.thr;
-#pragma unroll
-    for (int i = 0; i < NV; ++i)
-      if ((pend >> i) & 1u) {
-        if (x[i] > thr) {
-          const int s = atomicAdd(&h.n, 1);
-          if (s < CAP) {
-            v[s] = x[i];
-            pend &= ~(1u << i);
-          }
-        } else {
-          pend &= ~(1u << i);
-        }
-      }
-    if (!__syncthreads_or(pend != 0u)) return;
-    cand_cut<CAP>(h, v, K);
-  }
-}
 
 // status bits: 1 = a non-finite score, 2 = a mask entry outside [-1, G)
 __global__ __launch_bounds__(256) void ident64_init_kernel(const long long* __restrict__ mask, int Q, int G, double* __restrict__ pos,
@@ -128,8 +61,7 @@ __global__ __launch_bounds__(256) void ident64_tile_kernel(const double* __restr
   CandHdr& h = *reinterpret_cast<CandHdr*>(smem + kTileBytes);
   double* cv = reinterpret_cast<double*>(smem + kTileBytes + 32);
   int* sCnt = reinterpret_cast<int*>(smem + kTileBytes);      // [64][2] (sweep 2)
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1, l15 = lane & 15, lg = lane >> 4;
+  const int tid = threadIdx.x, wm = tile64::wm(), wn = tile64::wn(), l15 = tile64::l15(), lg = tile64::lg();
   if (RANK) {
     if (tid < 128) sCnt[tid] = 0;
   } else {
@@ -138,17 +70,17 @@ __global__ __launch_bounds__(256) void ident64_tile_kernel(const double* __restr
   __syncthreads();
   unsigned long long negs = 0ull;
   bool bad = false;
-  const int ntile = ceil_div(Q, 64), ncg = ceil_div(G, 64 * kChunks), nk = ceil_div(D, BK);
+  const int ntile = ceil_div(Q, 64), ncg = ceil_div(G, 64 * kChunks);
   const long long items = (long long)ntile * ncg;
   for (long long w = blockIdx.x; w < items; w += gridDim.x) {
     const int a0 = (int)(w / ncg) * 64, c_beg = (int)(w % ncg) * 64 * kChunks, c_end = min(G, c_beg + 64 * kChunks);
-    // this lane's 8 rows: a0 + wm * 32 + i * 16 + q * 4 + lg, kept at index i * 4 + q
+    // this lane's 8 rows a0 + row_f64(i, q), kept at index i * 4 + q
     int ma[8];
     double pa[8];
     int gt[8], eq[8];
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
-      const int a = a0 + wm * 32 + (r >> 2) * 16 + (r & 3) * 4 + lg;
+      const int a = a0 + tile64::row_f64(r >> 2, r & 3);
       const long long m = a < Q ? mask[a] : -1;
       ma[r] = (m >= 0 && m < G) ? (int)m : -1;
       if (RANK) {
@@ -176,16 +108,9 @@ __global__ __launch_bounds__(256) void ident64_tile_kernel(const double* __restr
         }
       };
       f64x4_t acc[2][2];
-#pragma unroll
-      for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) acc[a][b] = (f64x4_t){0.0, 0.0, 0.0, 0.0};
-      load(0);
-      store(0);                       // the previous chunk's K loop ended on a barrier after its last LDS read
-      __syncthreads();
-      for (int kt = 0; kt < nk; ++kt) {
-        const int buf = kt & 1;
-        if (kt + 1 < nk) load((kt + 1) * BK);
+      tile64::zero(acc);
+      // the previous chunk's K loop ended on a barrier after its last LDS read
+      tile64::pipeline<BK>(0, D, load, store, [&](int buf) {
 #pragma unroll
         for (int k4 = 0; k4 < BK; k4 += 4) {
           double fa[2], fb[2];
@@ -194,51 +119,40 @@ __global__ __launch_bounds__(256) void ident64_tile_kernel(const double* __restr
             fa[i] = sA[(buf * 64 + wm * 32 + i * 16 + l15) * LDK + k4 + lg];
             fb[i] = sB[(buf * 64 + wn * 32 + i * 16 + l15) * LDK + k4 + lg];
           }
-#pragma unroll
-          for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[i], fb[j], acc[i][j], 0, 0, 0);
+          tile64::mma(fa, fb, acc);
         }
-        if (kt + 1 < nk) store(buf ^ 1);
-        __syncthreads();
-      }
-      // f64 16x16x4 accumulator layout: register q of lane l holds D[row = 4 q + (l >> 4)][col = l & 15]
+      });
       double v[16];
       unsigned pend = 0u;
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int b = b0 + wn * 32 + j * 16 + l15;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int a = a0 + wm * 32 + i * 16 + q * 4 + lg, r = (j * 2 + i) * 4 + q, r8 = i * 4 + q;
-            v[r] = acc[i][j][q];
-            if (a < Q && b < c_end) {
-              if (RANK) {
-                if (ma[r8] >= 0 && ma[r8] != b) {
-                  gt[r8] += v[r] > pa[r8] ? 1 : 0;
-                  eq[r8] += v[r] == pa[r8] ? 1 : 0;
-                }
-              } else {
-                if (!isfinite(v[r])) bad = true;
-                if (ma[r8] == b) {
-                  pos[a] = v[r];
-                } else {
-                  ++negs;
-                  pend |= 1u << r;
-                }
-              }
+      int r = 0;                      // position in the walk (order j, i, q): a constant once the walk is unrolled; r & 7 = i * 4 + q
+      tile64::for_each(acc, [&](int m, int n, double x) {
+        const int a = a0 + m, b = b0 + n, r8 = r & 7;
+        v[r] = x;
+        if (a < Q && b < c_end) {
+          if (RANK) {
+            if (ma[r8] >= 0 && ma[r8] != b) {
+              gt[r8] += x > pa[r8] ? 1 : 0;
+              eq[r8] += x == pa[r8] ? 1 : 0;
+            }
+          } else {
+            if (!isfinite(x)) bad = true;
+            if (ma[r8] == b) {
+              pos[a] = x;
+            } else {
+              ++negs;
+              pend |= 1u << r;
             }
           }
-      }
+        }
+        ++r;
+      });
       if constexpr (!RANK) cand_offer<CAP>(h, cv, v, pend, K);
     }
     if (RANK) {
       // the item's counts: LDS sum over the 32 lanes that share a row, then one integer atomic per row and counter
 #pragma unroll
       for (int r = 0; r < 8; ++r) {
-        const int row = wm * 32 + (r >> 2) * 16 + (r & 3) * 4 + lg;
+        const int row = tile64::row_f64(r >> 2, r & 3);
         if (gt[r]) atomicAdd(&sCnt[row * 2], gt[r]);
         if (eq[r]) atomicAdd(&sCnt[row * 2 + 1], eq[r]);
       }

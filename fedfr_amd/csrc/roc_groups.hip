@@ -13,20 +13,20 @@
 // one LDS-private 4002-counter histogram per workgroup is enough, flushed with 64-bit integer atomics to one or two global histograms
 // (order-free: deterministic).  The grid is 1-D over the tile pairs (ta <= tb) with ta a grouped tile: tiles below the diagonal and
 // tiles between two ungrouped sides are never launched.  No workgroup waits for another.
-// Tile arithmetic (64 x 64, 2 x 2 waves of 32 x 32, v_mfma_f64_16x16x4_f64, BK = 16, double-buffered k-major LDS rows with the XOR
-// swizzle) and the accumulator layout are roc_hist_kernel's: every dot product is the same fp64 number there and here.
+// The tile (tile64.h, fp64 accumulation, BK = 16) and the histogram slot (roc_slot, head.h) are roc_hist_kernel's: every dot product is the
+// same fp64 number there and here.
 #include "head.h"
+#include "tile64.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) double f64x4_t;
-constexpr int BK = 16, LD = 80, NBIN = 4002;
+constexpr int BK = 16;
 
 __global__ __launch_bounds__(256) void roc_hist_groups_kernel(const float* __restrict__ feat, const long long* __restrict__ label,
                                                               const int* __restrict__ row_index, const int* __restrict__ tile_group, int N,
                                                               int D, int n_tiles, int G, unsigned long long* __restrict__ hist) {
-  __shared__ float sA[2][BK][LD], sB[2][BK][LD];
-  __shared__ unsigned lh[NBIN];
+  __shared__ tile64::Lds<BK> s;
+  __shared__ unsigned lh[ROC_NBIN];
   __shared__ int sRow[2][64];                                  // feature row of every slot of the two sides, -1 = padding
   __shared__ long long sLab[2][64];
   // linear index -> (ta, tb), ta <= tb < n_tiles: row ta of the triangle starts at S(ta) = ta * n - ta (ta - 1) / 2
@@ -43,95 +43,49 @@ __global__ __launch_bounds__(256) void roc_hist_groups_kernel(const float* __res
   gb = (gb >= 0 && gb < G) ? gb : -1;
   if (ga < 0 && gb < 0) return;                                // workgroup-uniform: no pair of this tile has a target row
   const int h0 = ga >= 0 ? ga : gb, h1 = (ga >= 0 && gb >= 0 && gb != ga) ? gb : -1;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  for (int i = tid; i < NBIN; i += 256) lh[i] = 0u;
+  const int tid = threadIdx.x;
+  for (int i = tid; i < ROC_NBIN; i += 256) lh[i] = 0u;
   if (tid < 128) {
-    const int side = tid >> 6, s = tid & 63;
-    int r = row_index[(size_t)(side ? tb : ta) * 64 + s];
+    const int side = tid >> 6, sl = tid & 63;
+    int r = row_index[(size_t)(side ? tb : ta) * 64 + sl];
     r = (r >= 0 && r < N) ? r : -1;
-    sRow[side][s] = r;
-    sLab[side][s] = r >= 0 ? label[r] : 0;
+    sRow[side][sl] = r;
+    sLab[side][sl] = r >= 0 ? label[r] : 0;
   }
   int rowa[4], rowb[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {                                // this thread's four rows of either side (the same for every k-step)
-    const int m = (tid + 256 * i) >> 4;
+    int m, k;
+    tile64::elem<BK>(true, i, m, k);
     int r = row_index[(size_t)ta * 64 + m];
     rowa[i] = (r >= 0 && r < N) ? r : -1;
     r = row_index[(size_t)tb * 64 + m];
     rowb[i] = (r >= 0 && r < N) ? r : -1;
   }
   float ra[4], rb[4];
+  auto row = [&](int r, int gk) { return (r >= 0 && gk < D) ? feat[(size_t)r * D + gk] : 0.f; };   // features are row-major: k fastest
   auto load = [&](int k0) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int gk = k0 + ((tid + 256 * i) & 15);              // features are row-major: k fastest
-      ra[i] = (rowa[i] >= 0 && gk < D) ? feat[(size_t)rowa[i] * D + gk] : 0.f;
-      rb[i] = (rowb[i] >= 0 && gk < D) ? feat[(size_t)rowb[i] * D + gk] : 0.f;
-    }
+    tile64::load<BK>(ra, true, [&](int, int k, int i) { return row(rowa[i], k0 + k); });
+    tile64::load<BK>(rb, true, [&](int, int k, int i) { return row(rowb[i], k0 + k); });
   };
   auto store = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int e = tid + 256 * i, k = e & 15, m = e >> 4;
-      sA[buf][k][m ^ ((k >> 1) << 1)] = ra[i];
-      sB[buf][k][m ^ ((k >> 1) << 1)] = rb[i];
-    }
+    tile64::store(s, 0, buf, true, ra);
+    tile64::store(s, 1, buf, true, rb);
   };
   f64x4_t acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) acc[a][b] = (f64x4_t){0.0, 0.0, 0.0, 0.0};
-  const int nk = ceil_div(D, BK);
-  load(0);
-  store(0);
-  __syncthreads();
-  const int l15 = lane & 15, lg = lane >> 4;
-  for (int kt = 0; kt < nk; ++kt) {
-    const int buf = kt & 1;
-    if (kt + 1 < nk) load((kt + 1) * BK);
-#pragma unroll
-    for (int k4 = 0; k4 < BK; k4 += 4) {
-      double fa[2], fb[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int kk = k4 + lg, sw = (kk >> 1) << 1;
-        fa[i] = (double)sA[buf][kk][(wm * 32 + i * 16 + l15) ^ sw];
-        fb[i] = (double)sB[buf][kk][(wn * 32 + i * 16 + l15) ^ sw];
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[i], fb[j], acc[i][j], 0, 0, 0);
-    }
-    if (kt + 1 < nk) store(buf ^ 1);
-    __syncthreads();
-  }
-  // f64 16x16x4 accumulator layout: register q of lane l holds D[row = 4 q + (l >> 4)][col = l & 15]
+  tile64::zero(acc);
+  tile64::k_loop<BK>(s, acc, 0, D, load, store);
   const bool diag = ta == tb;                                  // within a diagonal tile every pair shows up twice: keep slot a < slot b
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int sb = wn * 32 + j * 16 + l15;
-    const bool vb = sRow[1][sb] >= 0;
-    const long long lb = sLab[1][sb];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int sa = wm * 32 + i * 16 + q * 4 + lg;
-        if (vb && sRow[0][sa] >= 0 && (!diag || sa < sb)) {
-          int bin = (int)((acc[i][j][q] + 1.0) * 1000.0);           // truncation, as int() in the reference
-          bin = bin < 0 ? 0 : (bin > 2000 ? 2000 : bin);             // (the reference would write out of bounds instead)
-          atomicAdd(&lh[2 * bin + (sLab[0][sa] == lb ? 0 : 1)], 1u);
-        }
-      }
-  }
+  struct Col { bool valid; long long label; };
+  tile64::for_each(
+      acc, [&](int sb) { return Col{sRow[1][sb] >= 0, sLab[1][sb]}; },
+      [&](int sa, int sb, double v, const Col& c) {
+        if (c.valid && sRow[0][sa] >= 0 && (!diag || sa < sb)) atomicAdd(&lh[roc_slot(v, sLab[0][sa] == c.label)], 1u);
+      });
   __syncthreads();
-  unsigned long long* const o0 = hist + (size_t)h0 * NBIN;
-  unsigned long long* const o1 = h1 >= 0 ? hist + (size_t)h1 * NBIN : nullptr;
-  for (int i = tid; i < NBIN; i += 256)
+  unsigned long long* const o0 = hist + (size_t)h0 * ROC_NBIN;
+  unsigned long long* const o1 = h1 >= 0 ? hist + (size_t)h1 * ROC_NBIN : nullptr;
+  for (int i = tid; i < ROC_NBIN; i += 256)
     if (lh[i]) {
       atomicAdd(&o0[i], (unsigned long long)lh[i]);
       if (o1) atomicAdd(&o1[i], (unsigned long long)lh[i]);

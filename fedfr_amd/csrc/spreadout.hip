@@ -3,8 +3,8 @@
 // on row-normalised Fn [N][D] fp32, c = 1 ('sum') or 1 / (N (N - 1)) ('mean').  S and H are never written to memory: N = 85 000 would be 29 GB.
 //
 // spreadout_tile_kernel: workgroup b owns rows [64 b, 64 b + 64) of dFn and walks the 64-column tiles of S in ascending order.
-//   First product: the 64 x 64 x D tile of head.hip's sgemm (2 x 2 waves of 32 x 32, v_mfma_f32_16x16x4_f32 = an exact fp32 FMA chain over k
-//   ascending, BK = 16, double-buffered k-major LDS rows with the same XOR swizzle), both operands read from Fn with 16-byte loads.
+//   First product: the 64 x 64 x D tile of tile64.h with fp32 accumulation (sgemm's exact fp32 FMA chain over k ascending, BK = 16), both
+//   operands read from Fn with 16-byte loads and this kernel's own thread-to-element map.
 //   Epilogue on the accumulators: hinge, diagonal and out-of-range entries zeroed by global index, sum h^2 (fp64 per lane) and the count of
 //   S_ij > margin.  A tile with no active element (workgroup-uniform: __syncthreads_or) ends there: at margin 0.4 that is almost every tile.
 //   Second product, active tiles only: the hinge tile goes to LDS (pitch 66: the A-fragment read of 16 rows x 2 k lands on 32 banks) with a
@@ -17,26 +17,26 @@
 // spreadout_reduce_kernel: one workgroup adds the per-row-block fp64 loss partials and counts in a fixed order.
 // No floating-point atomics; every dFn element is accumulated by one owner over ascending column tiles: two launches are bit-identical.
 #include "head.h"
+#include "tile64.h"
 
 namespace {
 
-constexpr int BM = 64, BN = 64, BK = 16, LD = 80;      // LD % 32 == 16 + column XOR ((k >> 1) << 1): LDS reads and writes conflict-free (head.hip)
+constexpr int BM = 64, BN = 64, BK = 16;
 constexpr int HP = 66;                                 // pitch of the hinge tile in floats
 constexpr int kMaxD = 1024;
 
 __global__ __launch_bounds__(256) void spreadout_tile_kernel(const float* __restrict__ fn, int N, int D, float margin, float scale,
                                                              float* dfn, double* __restrict__ part_loss,
                                                              long long* __restrict__ part_active) {
-  __shared__ float sA[2][BK][LD], sB[2][BK][LD];
+  __shared__ tile64::Lds<BK> t;
   __shared__ float sH[BM * HP];
   __shared__ unsigned sMask[2];                        // [0]: 16-row groups, [1]: 4-column groups of the hinge tile with an active element
   __shared__ double sLoss[4];
   __shared__ long long sCnt[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1, l15 = lane & 15, lg = lane >> 4;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = tile64::l15(), lg = tile64::lg();
   const int i0 = blockIdx.x * BM;
   const int lm = tid >> 2, lk = (tid & 3) * 4;         // this thread's 16-byte piece of a 64 x 16 operand tile: row lm, k lk .. lk + 3
-  const int nk = ceil_div(D, BK), nchunk = ceil_div(D, 16);
+  const int nchunk = ceil_div(D, 16);
   if (tid < 2) sMask[tid] = 0u;
   double loss = 0.0;
   long long cnt = 0;
@@ -52,72 +52,38 @@ __global__ __launch_bounds__(256) void spreadout_tile_kernel(const float* __rest
     auto store = [&](int buf) {
       const float va[4] = {ra.x, ra.y, ra.z, ra.w}, vb[4] = {rb.x, rb.y, rb.z, rb.w};
 #pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const int k = lk + t, c = lm ^ ((k >> 1) << 1);
-        sA[buf][k][c] = va[t];
-        sB[buf][k][c] = vb[t];
+      for (int e = 0; e < 4; ++e) {
+        t.put(0, buf, lk + e, lm, va[e]);
+        t.put(1, buf, lk + e, lm, vb[e]);
       }
     };
     f32x4_t acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int b = 0; b < 2; ++b) acc[a][b] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-    load(0);
-    store(0);                                          // the previous tile ended on a barrier after its last LDS read
-    __syncthreads();
-    for (int kt = 0; kt < nk; ++kt) {
-      const int buf = kt & 1;
-      if (kt + 1 < nk) load((kt + 1) * BK);
-#pragma unroll
-      for (int k4 = 0; k4 < BK; k4 += 4) {
-        float fa[2], fb[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          const int kk = k4 + lg, sw = (kk >> 1) << 1;
-          fa[i] = sA[buf][kk][(wm * 32 + i * 16 + l15) ^ sw];
-          fb[i] = sB[buf][kk][(wn * 32 + i * 16 + l15) ^ sw];
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i], fb[j], acc[i][j], 0, 0, 0);
-      }
-      if (kt + 1 < nk) store(buf ^ 1);
-      __syncthreads();
-    }
-    // S[row m][col n]: m = wm * 32 + i * 16 + lg * 4 + q, n = wn * 32 + j * 16 + l15.  The hinge replaces S in the accumulators.
+    tile64::zero(acc);
+    tile64::k_loop<BK>(t, acc, 0, D, load, store);     // the previous tile ended on a barrier after its last LDS read
+    auto hinge = [&](int m, int n, float sv, bool& on) {   // H of element (m, n) of the tile; diagonal and out-of-range entries by global index
+      on = i0 + m < N && j0 + n < N && i0 + m != j0 + n && sv > margin;
+      return on ? sv - margin : 0.f;
+    };
     unsigned rmask = 0u, kmask = 0u;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int m = wm * 32 + i * 16 + lg * 4 + q, n = wn * 32 + j * 16 + l15;
-          const float s = acc[i][j][q];
-          const bool on = i0 + m < N && j0 + n < N && i0 + m != j0 + n && s > margin;
-          const float h = on ? s - margin : 0.f;
-          acc[i][j][q] = h;
-          if (on) {
-            loss += (double)h * (double)h;
-            ++cnt;
-            rmask |= 1u << (m >> 4);
-            kmask |= 1u << (n >> 2);
-          }
-        }
+    tile64::for_each(acc, [&](int m, int n, float sv) {
+      bool on;
+      const float h = hinge(m, n, sv, on);
+      if (on) {
+        loss += (double)h * (double)h;
+        ++cnt;
+        rmask |= 1u << (m >> 4);
+        kmask |= 1u << (n >> 2);
+      }
+    });
     if (!__syncthreads_or(rmask != 0u)) continue;
     if (rmask) {
       atomicOr(&sMask[0], rmask);
       atomicOr(&sMask[1], kmask);
     }
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          sH[(wm * 32 + i * 16 + lg * 4 + q) * HP + wn * 32 + j * 16 + l15] = acc[i][j][q];
+    tile64::for_each(acc, [&](int m, int n, float sv) {
+      bool on;
+      sH[m * HP + n] = hinge(m, n, sv, on);
+    });
     __syncthreads();
     const unsigned rows = sMask[0], ks = sMask[1];
     for (int c = wave; c < nchunk; c += 4) {
