@@ -69,11 +69,14 @@ SIGNATURES = {
     "fedfr_stem_fwd": (i32, [vp, vp, vp, vp, i32, i32, vp]),
     "fedfr_stem_wgrad_ws_bytes": (sz, [i32, i32]),
     "fedfr_stem_wgrad": (i32, [vp, vp, vp, vp, i32, i32, vp]),
+    "fedfr_stem_wgrad_fused": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]),
     "fedfr_bn_finalize": (i32, [vp, i32, i32, f64, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp]),
     "fedfr_bn_apply_stat_rows": (i32, [i32, i32]),
     "fedfr_bn_apply": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]),
     "fedfr_bn_bwd_rows": (i32, [i32, i32]),
     "fedfr_bn_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp]),
+    "fedfr_bn_bwd_apply_rows": (i32, [i32, i32]),
+    "fedfr_bn_bwd_rowslab": (i32, [vp] * 9 + [i32, i32, f64, vp, i32, i32] + [vp] * 6 + [i32] + [vp] * 9),
     "fedfr_bn_sliced_rows": (i32, [i32, i32, i32]),
     "fedfr_bn_sliced_ok": (i32, [i32, i32, i32, i32]),
     "fedfr_conv2d_fwd_moments": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, C.POINTER(i32), vp]),

@@ -475,6 +475,11 @@ size_t fedfr_stem_wgrad_ws_bytes(int batch, int hw) { return (size_t)ew_stem_wgr
 int fedfr_stem_wgrad(const float* x, const uint16_t* dy, float* dw, void* ws, int batch, int hw, void* stream) {
   return ew_stem_wgrad(x, BF(dy), dw, (float*)ws, batch, hw, hw, ST(stream));
 }
+int fedfr_stem_wgrad_fused(const float* x, const uint16_t* dy_act, const uint16_t* x0, const float* coef, const float* sc, const float* sh,
+                           const float* alpha, float* dw, void* ws, int batch, int hw, void* stream) {
+  FEDFR_REQUIRE(x0, "stem_wgrad_fused: the conv output x0 is required (fedfr_stem_wgrad is the plain form)");
+  return ew_stem_wgrad(x, BF(dy_act), dw, (float*)ws, batch, hw, hw, ST(stream), BF(x0), coef, sc, sh, alpha);
+}
 
 // ---- streams -------------------------------------------------------------------------------------------------
 // A HIP stream of the LOWEST priority the device offers, for the weight-gradient stream of fedfr_net_backward2: workgroups of the
@@ -524,6 +529,25 @@ int fedfr_bn_bwd(const uint16_t* dy, const uint16_t* x, const float* mean, const
   p.partials = partials; p.coef = coef; p.add = BF(add); p.add_up = BF(add_up); p.H = H; p.W = H; p.dx = BFM(dx);
   FEDFR_TRY(ew_bn_bwd_reduce(p, ST(stream)));
   FEDFR_TRY(ew_bn_bwd_finalize(partials, ew_bn_bwd_grid(M, C), C, (double)M, gamma, mean, rstd, dgamma, dbeta, dalpha, coef, ST(stream)));
+  return ew_bn_bwd_apply(p, ST(stream));
+}
+int fedfr_bn_bwd_apply_rows(int M, int C) { return ew_bn_bwd_apply_grid(M, C); }
+// the row-slab branch of net.hip's bn_bwd, argument for argument
+int fedfr_bn_bwd_rowslab(const uint16_t* dy, const uint16_t* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                         const float* alpha, const float* sc, const float* sh, int M, int C, double count, float* partials, int rows_in,
+                         int coef_only, float* coef, float* dgamma, float* dbeta, float* dalpha, const uint16_t* add,
+                         const uint16_t* add_up, int H, uint16_t* dx, const uint16_t* nx, const float* nmean, const float* nrstd,
+                         float* npart, const float* nsc, const float* nsh, const float* nalpha, void* stream) {
+  FEDFR_REQUIRE(partials && coef, "bn_bwd_rowslab: partials and coef are required");
+  FEDFR_REQUIRE(!(dalpha && !alpha), "bn_bwd_rowslab: dalpha without alpha");
+  BnBwd p{};
+  p.nx = BF(nx); p.nmean = nmean; p.nrstd = nrstd; p.npart = npart; p.nsc = nsc; p.nsh = nsh; p.nalpha = nalpha;
+  p.dy = BF(dy); p.x = BF(x); p.mean = mean; p.rstd = rstd; p.gamma = gamma; p.beta = beta; p.alpha = alpha; p.sc = sc; p.sh = sh;
+  p.M = M; p.C = C; p.partials = partials; p.coef = coef; p.add = BF(add); p.add_up = BF(add_up); p.H = H; p.W = H; p.dx = BFM(dx);
+  if (rows_in <= 0) FEDFR_TRY(ew_bn_bwd_reduce(p, ST(stream)));      // else: the producing pass already wrote the partials
+  FEDFR_TRY(ew_bn_bwd_finalize(partials, rows_in > 0 ? rows_in : ew_bn_bwd_grid(M, C), C, count, gamma, mean, rstd, dgamma, dbeta, dalpha, coef,
+                               ST(stream)));
+  if (coef_only) return FEDFR_OK;
   return ew_bn_bwd_apply(p, ST(stream));
 }
 

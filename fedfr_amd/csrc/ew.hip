@@ -1505,6 +1505,10 @@ __global__ __launch_bounds__(256) void stem_wgrad_mfma_kernel(const float* __res
           const float z = x0[j] * G[j] + Hs[j];
           if (z <= 0.f) dz = d[j] * al[j];
           o[j] = ca[j] * dz + (cA[j] * x0[j] + cB[j]);
+          // the fp32 result is kept as such and THEN rounded to 16 bits, as bn_bwd_apply does (v_pk_fma_f32 + v_cvt_pk_f16_f32): left alone, hipcc
+          // folds the conversion of the fp16 build into v_fma_mixlo_f16, which rounds the exact sum once — another last bit in a few elements per
+          // million, and the weight gradient no longer equals the two-kernel form's bit for bit (tests/test_stem_chain_gpu.py)
+          asm("" : "+v"(o[j]));
         }
         dv[i] = mc + px < mend ? pack8(o) : make_uint4(0, 0, 0, 0);      // rows beyond this workgroup's range read as zeros, and B is not zero
       }

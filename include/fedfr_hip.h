@@ -212,6 +212,11 @@ int fedfr_stem_stat_rows(int batch, int hw);
 int fedfr_stem_fwd(const float* x, const float* w_krsc, uint16_t* y, float* stats, int batch, int hw, void* stream);
 size_t fedfr_stem_wgrad_ws_bytes(int batch, int hw);
 int fedfr_stem_wgrad(const float* x, const uint16_t* dy, float* dw, void* ws, int batch, int hw, void* stream);
+/* the same weight gradient from the gradient wrt the stem's ACTIVATION: the BatchNorm + PReLU backward (coef [3][64] of fedfr_bn_bwd_rowslab
+ * with coef_only, the forward's scale / shift, the slopes) is applied to dy_act and the conv output x0 on their way in (what
+ * fedfr_net_backward runs under option "stem_fuse_wgrad") */
+int fedfr_stem_wgrad_fused(const float* x, const uint16_t* dy_act, const uint16_t* x0, const float* coef, const float* sc, const float* sh,
+                           const float* alpha, float* dw, void* ws, int batch, int hw, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * BatchNorm2d (train) + PReLU + residual — replace nn.BatchNorm2d / nn.PReLU / `out += identity`
@@ -230,6 +235,21 @@ int fedfr_bn_bwd(const uint16_t* dy, const uint16_t* x, const float* mean, const
                  const float* beta, const float* alpha, int M, int C, float* partials, float* coef, float* dgamma,
                  float* dbeta, float* dalpha, const uint16_t* add, const uint16_t* add_up, int H, uint16_t* dx,
                  void* stream);
+/* The row-slab chain exactly as fedfr_net_backward drives it on the large maps (every argument of the apply pass is reachable):
+ *   sc / sh: this BatchNorm's forward (scale, shift) — with alpha the PReLU mask is then sign(x sc + sh), the forward's own expression (NULL:
+ *   derived from mean / rstd / gamma / beta, as fedfr_bn_bwd does);  count: elements per channel, HUGE_VAL for a frozen BatchNorm (dx = gamma
+ *   rstd dz, the parameter-gradient sums unchanged);  rows_in > 0: `partials` already holds that many rows [3][C] left by a producing pass and
+ *   the reduce pass is skipped;  coef_only: stop after the finalize (dgamma / dbeta / dalpha / coef written, dx untouched) — the consumer
+ *   applies coef itself (fedfr_stem_wgrad_fused);  nx: dx is also reduced as the dy of the BatchNorm over nx (nmean / nrstd) into npart,
+ *   fedfr_bn_bwd_apply_rows rows [3][C] = (sum dz, sum dz xhat, 0); with nalpha that BatchNorm has a PReLU behind it (nsc / nsh: its forward
+ *   scale / shift) and the rows carry (sum dz, sum dz xhat, sum dx z over z <= 0) — served without alpha / add only.  npart may be `partials`
+ *   (the finalize has read them before the apply pass writes). */
+int fedfr_bn_bwd_apply_rows(int M, int C);
+int fedfr_bn_bwd_rowslab(const uint16_t* dy, const uint16_t* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                         const float* alpha, const float* sc, const float* sh, int M, int C, double count, float* partials, int rows_in,
+                         int coef_only, float* coef, float* dgamma, float* dbeta, float* dalpha, const uint16_t* add,
+                         const uint16_t* add_up, int H, uint16_t* dx, const uint16_t* nx, const float* nmean, const float* nrstd,
+                         float* npart, const float* nsc, const float* nsh, const float* nalpha, void* stream);
 
 /* Channel-sliced train-mode BatchNorm passes that reduce the partial rows themselves (no finalize launch; csrc/bn_sliced.hip) — what
  * fedfr_net_forward / _backward run on the 28x28 and smaller maps.  Partial rows: [row][statistic][C] fp32, the layout fedfr_bn_apply /

@@ -1747,7 +1747,7 @@ def test_every_switch_alternative_matches_the_default(name):
         # kernels that round at other points (fused epilogues, derived statistics) move a 16-bit network by its storage noise; pure reorderings stay at 1e-4
         loose = name in ("fwd_xmom", "fuse_bnbwd", "fuse_bnbwd28", "c64p_bnbwd", "conv_c64p", "bn_sliced", "fuse_bnred_next", "stem_bnred", "nt_glds", "conv28_tpw2")
         assert dg < (2e-2 if loose else 1e-3), (name, val, dg)
-        if name in ("wgrad9p_bg",):
+        if name in ("wgrad9p_bg", "stem_fuse_wgrad"):       # (stem_fuse_wgrad: the fused kernel forms the same 16-bit operand, tests/test_stem_chain_gpu.py)
             assert got[0] == ref[0] and torch.equal(got[1], ref[1]) and torch.equal(got[2], ref[2]), name
 
 
