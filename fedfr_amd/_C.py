@@ -136,6 +136,9 @@ SIGNATURES = {
     "fedfr_fedavg_axpy": (i32, [vp, vp, f32, sz, i32, vp]),
     "fedfr_fedavg_multi": (i32, [vp, vp, vp, i32, sz, i32, vp]),
     "fedfr_fedavg_i64": (i32, [vp, vp, f32, i32, i32, vp, vp]),
+    "fedfr_fedopt_sqnorm_workspace_bytes": (sz, [i32, sz]),
+    "fedfr_fedopt_sqnorm": (i32, [vp, vp, vp, i32, sz, f32, vp, vp, vp, sz, vp]),
+    "fedfr_fedopt_multi": (i32, [i32, vp, vp, vp, vp, i32, sz, vp, vp, vp, i32, i32, f32, f32, f32, f32, f32, f32, vp]),
     "fedfr_pfc_rand": (i32, [vp, i32, u64, u64, vp]),
     "fedfr_pfc_localize": (i32, [vp, i32, i64, i32, vp, vp]),
     "fedfr_pfc_topk": (i32, [vp, i32, i32, vp, vp, vp]),

@@ -754,6 +754,17 @@ int fedfr_fedavg_multi(float* dst, const float* const* srcs, const float* ws, in
 int fedfr_fedavg_i64(float* acc, const long long* src, float w, int n, int accumulate, long long* out_trunc, void* stream) {
   return optim_fedavg_i64(acc, src, w, n, accumulate, out_trunc, ST(stream));
 }
+size_t fedfr_fedopt_sqnorm_workspace_bytes(int k, size_t n) { return optim_fedopt_sqnorm_ws_bytes(k, n); }
+int fedfr_fedopt_sqnorm(const float* x, const float* const* xs, const float* ws, int k, size_t n, float clip, double* sq, float* coef,
+                        void* workspace, size_t workspace_bytes, void* stream) {
+  return optim_fedopt_sqnorm(x, xs, ws, k, n, clip, sq, coef, workspace, workspace_bytes, ST(stream));
+}
+int fedfr_fedopt_multi(int kind, float* x_out, const float* x, const float* const* xs, const float* coef, int k, size_t n, float* m, float* v,
+                       float* delta_scratch, int first, int last, float lr, float beta1, float one_minus_beta1, float beta2,
+                       float one_minus_beta2, float tau, void* stream) {
+  return optim_fedopt_multi(kind, x_out, x, xs, coef, k, n, m, v, delta_scratch, first, last, lr, beta1, one_minus_beta1, beta2, one_minus_beta2,
+                            tau, ST(stream));
+}
 int fedfr_pfc_rand(float* perm, int n, unsigned long long seed, unsigned long long step, void* stream) {
   return optim_pfc_rand(perm, n, seed, step, ST(stream));
 }

@@ -6,6 +6,12 @@ int optim_sgd(float* p, float* g, float* buf, bf16_t* shadow, size_t n, float lr
               hipStream_t st, float gscale = 1.f, unsigned* overflow = nullptr);   // gscale != 1: g holds gradient / gscale; it is multiplied in the kernel and stored back
 int optim_fedavg_axpy(float* dst, const float* src, float w, size_t n, int accumulate, hipStream_t st);
 int optim_fedavg_multi(float* dst, const float* const* srcs, const float* ws, int k, size_t n, int accumulate, hipStream_t st);
+size_t optim_fedopt_sqnorm_ws_bytes(int k, size_t n);
+int optim_fedopt_sqnorm(const float* x, const float* const* xs, const float* ws, int k, size_t n, float clip, double* sq, float* coef,
+                        void* workspace, size_t ws_bytes, hipStream_t st);
+int optim_fedopt_multi(int kind, float* x_out, const float* x, const float* const* xs, const float* coef, int k, size_t n, float* m, float* v,
+                       float* scratch, int first, int last, float lr, float beta1, float one_minus_beta1, float beta2, float one_minus_beta2,
+                       float tau, hipStream_t st);
 int optim_fedavg_i64(float* acc, const long long* src, float w, int n, int accumulate, long long* out_trunc, hipStream_t st);
 int optim_pfc_rand(float* perm, int n, unsigned long long seed, unsigned long long step, hipStream_t st);
 int optim_pfc_localize(long long* label, int n, long long class_start, int num_local, float* perm, hipStream_t st);

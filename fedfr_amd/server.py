@@ -84,6 +84,184 @@ def FedPavg(models: List[dict], weights: Sequence[float]):
     return aggr
 
 
+# ---- server optimisers (Reddi et al., "Adaptive Federated Optimization"): csrc/optim.hip fedopt_sqnorm_kernel / fedopt_multi_kernel
+FEDOPT_KINDS = {"AVGM": 0, "ADAGRAD": 1, "ADAM": 2, "YOGI": 3}
+AGGR_ALG_KINDS = {"FedAvgM": "AVGM", "FedAdagrad": "ADAGRAD", "FedAdam": "ADAM", "FedYogi": "YOGI"}
+
+
+class ServerOptimizer:
+    """State and hyper-parameters of one server optimiser over the flat parameter buffer: ``kind`` "AVGM" (server momentum), "ADAGRAD",
+    "ADAM" or "YOGI" (the ``aggr_alg`` spellings "FedAvgM", "FedAdagrad", "FedAdam", "FedYogi" are accepted too).  ``m`` (and ``v`` for the
+    adaptive kinds) are flat fp32 device tensors, allocated on first use to the parameter count (m = 0, v = tau^2, no bias correction, as in
+    the paper), kept across rounds, dropped by ``reset()``.  ``clip_norm`` > 0 scales a client whose update norm ||x_i - x|| exceeds it down
+    to that norm before aggregation.  ``last_update_sqnorm`` (fp64) and ``last_coef`` (fp32) hold the last round's squared update norms and
+    aggregation coefficients, one per client, ON THE DEVICE: nothing reads them back unless the caller does.  (1 - beta) is formed in fp32, which is what the kernel and its restatement
+    (tests/fedopt_cases.py) multiply by."""
+
+    def __init__(self, kind, lr=1.0, beta1=0.9, beta2=0.99, tau=1e-3, clip_norm=0.0):
+        self.kind = self._kind(kind)
+        self.lr, self.beta1, self.beta2, self.tau, self.clip_norm = float(lr), float(beta1), float(beta2), float(tau), float(clip_norm)
+        if not (self.tau > 0.0) and self.adaptive:
+            raise ValueError("ServerOptimizer: tau must be positive for the adaptive kinds (got %r)" % (tau,))
+        if self.clip_norm < 0.0 or self.clip_norm != self.clip_norm:
+            raise ValueError("ServerOptimizer: clip_norm must be >= 0 (got %r)" % (clip_norm,))
+        self.reset()
+
+    @staticmethod
+    def _kind(kind):
+        k = AGGR_ALG_KINDS.get(kind, kind)
+        if k not in FEDOPT_KINDS:
+            raise ValueError("ServerOptimizer: kind must be one of %s or %s (got %r)" % (sorted(FEDOPT_KINDS), sorted(AGGR_ALG_KINDS), kind))
+        return k
+
+    @property
+    def adaptive(self) -> bool:
+        return self.kind != "AVGM"
+
+    def reset(self):
+        self.m = self.v = None
+        self.rounds = 0
+        self.last_update_sqnorm = self.last_coef = None
+        self._scratch = self._ws = None
+
+    def hyper(self):
+        """(lr, beta1, 1 - beta1, beta2, 1 - beta2, tau) as the fp32 values the kernel receives."""
+        g = np.float32
+        return tuple(float(t) for t in (g(self.lr), g(self.beta1), g(1) - g(self.beta1), g(self.beta2), g(1) - g(self.beta2), g(self.tau)))
+
+    def _ensure(self, like: torch.Tensor):
+        if self.m is not None and (self.m.numel() != like.numel() or self.m.device != like.device):
+            raise RuntimeError("fedfr_amd.ServerOptimizer: the moments hold %d elements on %s, the parameters %d on %s; reset() first"
+                               % (self.m.numel(), self.m.device, like.numel(), like.device))
+        if self.m is None:
+            self.m = torch.zeros(like.numel(), dtype=f32, device=like.device)
+        if self.adaptive and self.v is None:
+            t = np.float32(self.tau)
+            self.v = torch.full((like.numel(),), float(t * t), dtype=f32, device=like.device)
+
+    @staticmethod
+    def _check(x: torch.Tensor, xs: Sequence[torch.Tensor], what: str):
+        if not x.is_cuda:
+            raise RuntimeError("fedfr_amd.%s: state tensors must be on the GPU (no CPU fallback)" % what)
+        for t in [x] + list(xs):
+            if t.numel() != x.numel() or t.dtype != f32 or not t.is_contiguous() or t.device != x.device:
+                raise RuntimeError("fedfr_amd.%s: parameter states must be same-shape contiguous fp32 tensors on one device" % what)
+
+    def coefficients(self, x: torch.Tensor, xs: Sequence[torch.Tensor], ws: Sequence[float]) -> torch.Tensor:
+        """coef_i = w_i min(1, clip_norm / ||x_i - x||) as a DEVICE tensor (fedfr_fedopt_sqnorm: one pass over x and ≤ 8 client states
+        at a time, no host synchronisation); the squared norms stay in ``last_update_sqnorm``."""
+        import ctypes as C
+        self._check(x, xs, "ServerOptimizer")
+        n, dev = x.numel(), x.device
+        sq = torch.empty(len(xs), dtype=torch.float64, device=dev)
+        coef = torch.empty(len(xs), dtype=f32, device=dev)
+        need = int(_C.lib().fedfr_fedopt_sqnorm_workspace_bytes(min(8, len(xs)), n))
+        if self._ws is None or self._ws.numel() * 8 < need or self._ws.device != dev:
+            self._ws = torch.empty((need + 7) // 8, dtype=torch.float64, device=dev)
+        for c0 in range(0, len(xs), 8):
+            grp = xs[c0:c0 + 8]
+            k = len(grp)
+            ptrs = (C.c_void_p * k)(*[t.data_ptr() for t in grp])
+            wv = (C.c_float * k)(*[float(np.float32(w)) for w in ws[c0:c0 + 8]])
+            _C.call("fedfr_fedopt_sqnorm", x.data_ptr(), ptrs, wv, k, n, float(np.float32(self.clip_norm)), sq.data_ptr() + 8 * c0,
+                    coef.data_ptr() + 4 * c0, self._ws.data_ptr(), self._ws.numel() * 8, _C.stream())
+        self.last_update_sqnorm, self.last_coef = sq, coef
+        return coef
+
+    def apply(self, x_out: torch.Tensor, x: torch.Tensor, xs: Sequence[torch.Tensor], coef: torch.Tensor):
+        """x_out = x + step(Σ_i coef_i (x_i - x)) and the moment update (fedfr_fedopt_multi; ``x_out`` may be ``x``).  More than 8 client
+        states chain passes through a scratch Δ buffer, bit-identical to one ascending loop; only the last pass touches m, v and x_out."""
+        import ctypes as C
+        self._check(x, list(xs) + [x_out], "ServerOptimizer")
+        if coef.numel() != len(xs) or coef.dtype != f32 or coef.device != x.device or not coef.is_contiguous():
+            raise RuntimeError("fedfr_amd.ServerOptimizer: coef must be a contiguous fp32 device tensor with one entry per client state")
+        self._ensure(x)
+        n = x.numel()
+        if len(xs) > 8 and (self._scratch is None or self._scratch.numel() != n or self._scratch.device != x.device):
+            self._scratch = torch.empty(n, dtype=f32, device=x.device)
+        for c0 in range(0, len(xs), 8):
+            grp = xs[c0:c0 + 8]
+            k = len(grp)
+            ptrs = (C.c_void_p * k)(*[t.data_ptr() for t in grp])
+            _C.call("fedfr_fedopt_multi", FEDOPT_KINDS[self.kind], x_out.data_ptr(), x.data_ptr(), ptrs, coef.data_ptr() + 4 * c0, k, n,
+                    self.m.data_ptr(), self.v.data_ptr() if self.adaptive else None,
+                    self._scratch.data_ptr() if len(xs) > 8 else None, 1 if c0 == 0 else 0, 1 if c0 + 8 >= len(xs) else 0, *self.hyper(),
+                    _C.stream())
+        self.rounds += 1
+
+    def _pass(self, x_out, x, xi, coef, scratch, first, last):
+        import ctypes as C
+        ptrs = (C.c_void_p * 1)(xi.data_ptr())
+        _C.call("fedfr_fedopt_multi", FEDOPT_KINDS[self.kind], _C.ptr(x_out), x.data_ptr(), ptrs, coef.data_ptr(), 1, x.numel(),
+                _C.ptr(self.m) if last else None, _C.ptr(self.v) if last and self.adaptive else None, scratch.data_ptr(), first, last,
+                *self.hyper(), _C.stream())
+
+    def weighted_delta(self, dst: torch.Tensor, x: torch.Tensor, xi: torch.Tensor, w: float):
+        """dst = w (x_i - x), the term one client adds to Δ, with the two roundings it has inside ``apply`` (a first, non-last pass of
+        fedfr_fedopt_multi whose Δ buffer is ``dst``; ``dst`` may be ``xi``).  Moments and parameters are not touched."""
+        self._check(x, [xi, dst], "ServerOptimizer")
+        self._pass(None, x, xi, torch.tensor([w], dtype=f32, device=x.device), dst, 1, 0)
+
+    def apply_delta(self, x_out: torch.Tensor, x: torch.Tensor, delta: torch.Tensor):
+        """x_out = x + step(Δ) and the moment update for a Δ that already exists (``x_out`` may be ``delta`` or ``x``): the last pass of a
+        chain, whose one remaining "client" is x itself and adds 1 (x - x) = 0."""
+        self._check(x, [delta, x_out], "ServerOptimizer")
+        self._ensure(x)
+        self._pass(x_out, x, x, torch.ones(1, dtype=f32, device=x.device), delta, 0, 1)
+        self.rounds += 1
+
+    def state_dict(self) -> dict:
+        return {"kind": self.kind, "lr": self.lr, "beta1": self.beta1, "beta2": self.beta2, "tau": self.tau, "clip_norm": self.clip_norm,
+                "rounds": self.rounds, "m": None if self.m is None else self.m.clone(), "v": None if self.v is None else self.v.clone()}
+
+    def load_state_dict(self, sd: dict):
+        kind = self._kind(sd["kind"])
+        for name in ("m", "v"):
+            t = sd.get(name)
+            if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != f32 or t.dim() != 1):
+                raise ValueError("ServerOptimizer.load_state_dict: '%s' must be a flat fp32 tensor or None" % name)
+        if sd.get("m") is not None and sd.get("v") is not None and sd["m"].numel() != sd["v"].numel():
+            raise ValueError("ServerOptimizer.load_state_dict: m and v differ in length")
+        self.reset()
+        self.kind = kind
+        self.lr, self.beta1, self.beta2, self.tau, self.clip_norm = (float(sd[k]) for k in ("lr", "beta1", "beta2", "tau", "clip_norm"))
+        self.rounds = int(sd["rounds"])
+        self.m = None if sd.get("m") is None else sd["m"].clone().contiguous()
+        self.v = None if sd.get("v") is None or not self.adaptive else sd["v"].clone().contiguous()
+
+
+def FedOpt(global_state, models: List[dict], weights: Sequence[float], opt: ServerOptimizer):
+    """One server-optimiser round: the PARAMETERS of the new global state are x + step(Σ_i c_i (x_i - x)) with x = ``global_state``'s
+    parameters, c_i = (n_i/Σn) min(1, clip_norm / ||x_i - x||) and the step of ``opt`` (two streaming kernels: per-client norms and
+    coefficients, then the update with ≤ 8 client states per pass).  BN running statistics and ``num_batches_tracked`` are statistics,
+    not optimisation variables: they are averaged exactly as ``FedPavg`` averages them (same kernels, order and float counters).
+    Only GPU ``FlatStateDict``s are accepted."""
+    states = [global_state] + list(models)
+    if not models or not all(isinstance(m, FlatStateDict) and m.flat is not None for m in states):
+        raise RuntimeError("fedfr_amd.FedOpt: the global and the client states must be FlatStateDicts (client.flat_state_dict)")
+    if len(weights) != len(models):
+        raise RuntimeError("fedfr_amd.FedOpt: %d weights for %d client states" % (len(weights), len(models)))
+    tot = sum(weights)
+    ws = [w / tot for w in weights]
+    x = global_state.flat[0]
+    if not x.is_cuda:
+        raise RuntimeError("fedfr_amd.FedOpt: state tensors must be on the GPU (no CPU fallback)")
+    p0, b0, n0 = models[0].flat
+    xs = [m.flat[0] for m in models]
+    ServerOptimizer._check(x, xs, "FedOpt")
+    P, Bf = torch.empty_like(x), torch.empty_like(b0)
+    N = torch.empty(n0.numel(), dtype=f32, device=x.device)
+    opt.apply(P, x, xs, opt.coefficients(x, xs, ws))
+    for c0 in range(0, len(models), 8):                 # running statistics and counters: FedPavg's flat path, line for line
+        if Bf.numel():
+            _multi(Bf, [m.flat[1] for m in models[c0:c0 + 8]], ws[c0:c0 + 8], c0 > 0)
+    for i, (m, w) in enumerate(zip(models, ws)):
+        n = m.flat[2]
+        if n.numel():
+            _C.call("fedfr_fedavg_i64", N.data_ptr(), n.data_ptr(), float(np.float32(w)), n.numel(), 1 if i else 0, None, _C.stream())
+    return FlatStateDict.from_flat((P, Bf, N), models[0].table, models[0].layers)
+
+
 def FedAvg_on_FC(pretrain_fc, models, weights, p):
     """reference server.py:36-46."""
     tot = sum(weights)
@@ -120,7 +298,8 @@ def exchange_data_sizes(data_size: float, comm) -> float:
     return float(t.item())
 
 
-def fedavg_all_reduce(backbone, data_size: float, total_size: float, comm=None, _axpy=_axpy, _i64=_i64_scale, _trunc=_i64_trunc):
+def fedavg_all_reduce(backbone, data_size: float, total_size: float, comm=None, _axpy=_axpy, _i64=_i64_scale, _trunc=_i64_trunc,
+                      server_opt=None, prev_params=None):
     """One client per rank: the FedAvg of a round as ONE collective (replaces the CPU loop of server.py:25-34 and the state_dict
     hand-offs of server.py:286,311).  The local state — parameters, BN running statistics and a float image of the
     ``num_batches_tracked`` counters, which are slices of one fp32 tensor (``IResNet.exchange_buffer``) — is scaled in place by the
@@ -129,8 +308,22 @@ def fedavg_all_reduce(backbone, data_size: float, total_size: float, comm=None, 
     ``load_state_dict`` does (F9).  The summation ORDER is the collective's (a ring), not the reference's ascending client index: results
     agree with ``FedPavg`` to fp32 rounding, not bit for bit.
     ``comm``: fedfr_amd.comm communicator (default: the torch.distributed world).  ``_axpy`` / ``_i64`` / ``_trunc`` are the HIP
-    kernels (injectable only so the plumbing can be exercised by the gloo CPU test)."""
+    kernels (injectable only so the plumbing can be exercised by the gloo CPU test).
+    ``server_opt`` (a ``ServerOptimizer``) with ``prev_params`` = x (the caller's copy of the flat parameters taken BEFORE local
+    training): the PARAMETER slice enters the exchange as w_i (x_i - x), formed in place with the roundings ``FedOpt`` gives that term, so
+    after the all-reduce every rank holds Δ = Σ w_i (x_i - x) there (running statistics and counters: the plain mean, as without an
+    optimiser); each rank then applies the optimiser's step to it in place (``fedfr_fedopt_multi``) and keeps its own, replicated copy of
+    the moments.  Still ONE collective.  Under a communicator that adds in ascending rank order the result is ``FedOpt`` of the same client
+    states bit for bit, otherwise to the fp32 rounding of the collective's order.  ``server_opt.clip_norm > 0`` raises ``ValueError``: on
+    this path the clip would have to be applied by every rank to its OWN delta before the exchange (one more norm pass per rank) — a
+    different algorithm from the clip ``FedOpt`` applies inside one aggregation, and not provided here."""
     from .comm import TorchDistComm
+    if server_opt is not None:
+        if server_opt.clip_norm > 0:
+            raise ValueError("fedavg_all_reduce: clip_norm > 0 is not supported on the all-reduce path (clipping a rank's own delta before "
+                             "the exchange is a different algorithm); use FedOpt")
+        if prev_params is None:
+            raise ValueError("fedavg_all_reduce: server_opt needs prev_params (the flat parameters before local training)")
     if comm is None:
         comm = TorchDistComm()
     state, nbt_f, nbt = backbone.exchange_buffer()
@@ -140,12 +333,24 @@ def fedavg_all_reduce(backbone, data_size: float, total_size: float, comm=None, 
     n_float = nbt_f.storage_offset() - state.storage_offset()
     assert 0 <= n_float <= state.numel(), "exchange_buffer: the counter image is not a slice of the state tensor"
     fl = state[:n_float]
-    _axpy(fl, fl, w, False)
+    if server_opt is None:
+        _axpy(fl, fl, w, False)
+    else:
+        params = state[:backbone.flat_state()[0].numel()]
+        stats = fl[params.numel():]
+        if stats.numel() and stats.data_ptr() % 16:
+            raise RuntimeError("fedavg_all_reduce: server_opt needs the running statistics 16-byte aligned inside the exchange buffer "
+                               "(parameter count %d is not a multiple of 4)" % params.numel())
+        server_opt.weighted_delta(params, prev_params, params, w)
+        if stats.numel():
+            _axpy(stats, stats, w, False)
     if nbt.numel():
         _i64(nbt_f, nbt, w)
     comm.all_reduce(state, "sum")                  # THE exchange of the round
     if nbt.numel():
         _trunc(nbt_f, nbt)
+    if server_opt is not None:
+        server_opt.apply_delta(params, prev_params, params)
     backbone.mark_weights_dirty()
     return w
 
@@ -203,6 +408,7 @@ class Server(object):
         self.pretrain_fc = None                      # where the reference stores the FedAvg'd public centres (server.py:325, see train())
         self.callback_local_veri = None              # local 1:1 verification (server.py:105-108): see enable_local_verification()
         self.local_candidates = []
+        self.server_opt = None                       # ServerOptimizer of aggr_alg FedAvgM / FedAdagrad / FedAdam / FedYogi (built in train())
 
     def enable_local_verification(self, callback, candidates=None):
         """reference server.py:105-108: ``callback`` (``eval_local.CallBack_LocalVerifi``) is handed to the clients whose ``cid`` is a
@@ -245,6 +451,9 @@ class Server(object):
     @_C.on_device(lambda self: self.device)
     def train(self):
         from .config import config as cfg
+        aggr_alg = getattr(self.args, "aggr_alg", "FedAvg")
+        if aggr_alg not in ("FedAvg", "FedProx") and aggr_alg not in AGGR_ALG_KINDS:      # before a round of client training is spent on it
+            raise ValueError("Server.train: unknown aggr_alg %r (FedAvg, FedProx, %s)" % (aggr_alg, ", ".join(AGGR_ALG_KINDS)))
         models, models_fc, losses_, data_sizes = [], [], [], []
         public = bool(getattr(self.args, "add_pretrained_data", False))
         return_all = bool(getattr(self.args, "return_all", False))
@@ -325,8 +534,17 @@ class Server(object):
             self.pretrain_fc = FedAvg_on_FC(self.pretrained_fc, models_fc, data_sizes, p=1.0)
             if getattr(self.args, "feedback_public_fc", False):
                 self.pretrained_fc = self.pretrain_fc
-        if getattr(self.args, "aggr_alg", "FedAvg") in ("FedAvg", "FedProx"):
+        if aggr_alg in ("FedAvg", "FedProx"):
             aggr_state_dict = FedPavg(models, data_sizes)
+            self.federated_model.load_state_dict(aggr_state_dict)
+        elif aggr_alg in AGGR_ALG_KINDS:
+            # server optimiser (a build extension: the reference's flag runs FedAvg only): one optimiser per server, moments kept across rounds
+            if getattr(self, "server_opt", None) is None:
+                a = self.args
+                self.server_opt = ServerOptimizer(aggr_alg, lr=getattr(a, "server_lr", 1.0), beta1=getattr(a, "server_momentum", 0.9),
+                                                  beta2=getattr(a, "server_beta2", 0.99), tau=getattr(a, "server_tau", 1e-3),
+                                                  clip_norm=getattr(a, "clip_norm", 0.0))
+            aggr_state_dict = FedOpt(flat_state_dict(self.federated_model), models, data_sizes, self.server_opt)
             self.federated_model.load_state_dict(aggr_state_dict)
         # the round / epoch counters belong to the driver, as in the reference (train.py:87-88): call step_round() after train()
         return self.avg_loss

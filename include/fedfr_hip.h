@@ -516,6 +516,52 @@ int fedfr_fedavg_axpy(float* dst, const float* src, float w, size_t n, int accum
 int fedfr_fedavg_multi(float* dst, const float* const* srcs, const float* ws, int k, size_t n, int accumulate, void* stream);
 int fedfr_fedavg_i64(float* acc, const long long* src, float w, int n, int accumulate, long long* out_trunc,
                      void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * server optimisers with update clipping — no reference counterpart (its --aggr_alg runs FedAvg only, server.py:328): the server-side
+ * family of Reddi et al., "Adaptive Federated Optimization" (FedAvgM, FedAdagrad, FedAdam, FedYogi) on the flat fp32 parameter buffer,
+ * as two one-pass streaming kernels beside fedfr_fedavg_multi.  Notation: x = the global parameters before the round [n], x_i = client
+ * i's parameters after local training, k <= 8 clients per call, Delta = sum_i coef_i (x_i - x) the aggregated pseudo-gradient, m / v the
+ * optimiser moments [n] (m starts at 0, v at tau^2 in every element; the caller owns and initialises them).
+ *   1. fedfr_fedopt_sqnorm   sq_i = |x_i - x|^2 and coef_i = w_i min(1, clip / sqrt(sq_i)), on the device
+ *   2. fedfr_fedopt_multi    Delta, the moment update and x' = x + step, reading x, m, v and every x_i once and writing x', m, v once
+ * No call synchronises with the host; coef travels from 1 to 2 in device memory.  A caller that does not clip fills coef with w_i itself
+ * and skips 1.  Every fp32 operation of 2 is a single correctly rounded + - * / sqrt in the order given below (nothing is contracted into
+ * an fma), so a result can be reproduced bit for bit on a CPU (tests/fedopt_cases.py).
+ * ------------------------------------------------------------------------------------------------ */
+/* bytes of the workspace fedfr_fedopt_sqnorm needs for k clients of n elements: k x grid doubles, grid = min(ceil((n / 4 + 1) / 256), 2048)
+ * (fedfr_fedavg_multi's launch rule); 0 for k outside 1..8 or n = 0 */
+size_t fedfr_fedopt_sqnorm_workspace_bytes(int k, size_t n);
+/* Per-client squared update norms and clipped aggregation coefficients in one pass over x and the k client states (HOST arrays of k device
+ * pointers xs / k weights ws, as fedfr_fedavg_multi):
+ *   sq[i]   = sum_j (double) d_ij^2,  d_ij = x_i[j] - x[j] rounded to fp32 (the subtraction fedfr_fedopt_multi performs); square and sum in fp64
+ *   coef[i] = (float) (ws[i] * min(1, clip / sqrt(sq[i])))   computed in fp64 and rounded once;  clip <= 0 or sq[i] == 0: coef[i] = ws[i]
+ * sq (k doubles) and coef (k floats) are DEVICE arrays.  Deterministic, no atomics: every block writes one fp64 partial per client into
+ * `workspace` ([k][grid], need not be initialised), lanes are reduced by a fixed shuffle tree, waves in ascending order through LDS, and a
+ * second single-block launch adds the partials in ascending block order: two runs give identical bits.  x and xs[i] 16-byte aligned,
+ * sq / workspace 8-byte aligned; FEDFR_ERR_WORKSPACE if workspace_bytes < fedfr_fedopt_sqnorm_workspace_bytes(k, n). */
+int fedfr_fedopt_sqnorm(const float* x, const float* const* xs, const float* ws, int k, size_t n, float clip, double* sq, float* coef,
+                        void* workspace, size_t workspace_bytes, void* stream);
+/* One server-optimiser step.  kind: 0 FedAvgM, 1 FedAdagrad, 2 FedAdam, 3 FedYogi.  coef: DEVICE array of k floats (4-byte aligned).  Per element, every
+ * operation rounded to fp32 once, in this order (b1 = beta1, c1 = one_minus_beta1, b2 = beta2, c2 = one_minus_beta2; the caller forms c1, c2 in fp32):
+ *   D = first ? 0 : delta_scratch;  for i = 0 .. k-1:  D = D + coef[i] * (x_i - x)            (subtract, multiply, add)
+ *   not last:  delta_scratch = D, nothing else is written
+ *   last, kind 0:  m' = b1 * m + D                                        x' = x + lr * m'
+ *         kind 1:  m' = b1 * m + c1 * D    v' = v + D * D
+ *         kind 2:  m' = b1 * m + c1 * D    v' = b2 * v + c2 * (D * D)
+ *         kind 3:  m' = b1 * m + c1 * D    v' = v - (c2 * (D * D)) * sign(v - D * D)   (sign(0) = 0)
+ *         kinds 1-3:                                                      x' = x + (lr * m') / (sqrt(v') + tau)
+ * No bias correction (as in the paper).  m, v are updated in place; x_out may be x.  More than 8 clients: chain calls over groups of <= 8 in
+ * ascending client order with first = 1 on the first and last = 1 on the final group (delta_scratch [n] carries D between them; with one
+ * call first = last = 1 and delta_scratch may be NULL); the result is bit-identical to one ascending loop over all clients.  v and beta2 /
+ * one_minus_beta2 are ignored by kind 0 (v may be NULL); m, v, x_out may be NULL when last = 0.  delta_scratch may be one of the client
+ * states when last = 0 (D overwrites it) and x_out when last = 1 (the all-reduce path of server.py forms w_i (x_i - x) and applies the summed D so).  All [n] buffers 16-byte aligned;
+ * n % 4 trailing elements take a scalar path.  Bad arguments (NULL, k outside 1..8, misalignment, unknown kind) return FEDFR_ERR_ARG
+ * before anything is launched. */
+int fedfr_fedopt_multi(int kind, float* x_out, const float* x, const float* const* xs, const float* coef, int k, size_t n, float* m, float* v,
+                       float* delta_scratch, int first, int last, float lr, float beta1, float one_minus_beta1, float beta2,
+                       float one_minus_beta2, float tau, void* stream);
+
 int fedfr_pfc_rand(float* perm, int n, unsigned long long seed, unsigned long long step, void* stream);
 int fedfr_pfc_localize(long long* label, int n, long long class_start, int num_local, float* perm, void* stream);
 int fedfr_pfc_topk(const float* perm, int n, int k, long long* index, int* npos_out, void* stream);
