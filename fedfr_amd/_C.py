@@ -139,6 +139,10 @@ SIGNATURES = {
     "fedfr_fedopt_sqnorm_workspace_bytes": (sz, [i32, sz]),
     "fedfr_fedopt_sqnorm": (i32, [vp, vp, vp, i32, sz, f32, vp, vp, vp, sz, vp]),
     "fedfr_fedopt_multi": (i32, [i32, vp, vp, vp, vp, i32, sz, vp, vp, vp, i32, i32, f32, f32, f32, f32, f32, f32, vp]),
+    "fedfr_robust_trimmed_mean": (i32, [vp, vp, i32, i32, sz, vp]),
+    "fedfr_robust_pairdist_workspace_bytes": (sz, [i32, sz]),
+    "fedfr_robust_pairdist": (i32, [vp, i32, sz, vp, vp, sz, vp]),
+    "fedfr_robust_krum_select": (i32, [vp, i32, i32, i32, vp, vp, vp]),
     "fedfr_pfc_rand": (i32, [vp, i32, u64, u64, vp]),
     "fedfr_pfc_localize": (i32, [vp, i32, i64, i32, vp, vp]),
     "fedfr_pfc_topk": (i32, [vp, i32, i32, vp, vp, vp]),

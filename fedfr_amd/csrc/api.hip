@@ -9,6 +9,7 @@
 #include "head.h"
 #include "net.h"
 #include "optim.h"
+#include "robust.h"
 
 static thread_local char g_err[512] = "";
 extern int g_tn_use_tr;
@@ -764,6 +765,16 @@ int fedfr_fedopt_multi(int kind, float* x_out, const float* x, const float* cons
                        float one_minus_beta2, float tau, void* stream) {
   return optim_fedopt_multi(kind, x_out, x, xs, coef, k, n, m, v, delta_scratch, first, last, lr, beta1, one_minus_beta1, beta2, one_minus_beta2,
                             tau, ST(stream));
+}
+int fedfr_robust_trimmed_mean(float* dst, const float* const* srcs, int k, int trim, size_t n, void* stream) {
+  return robust_trimmed_mean(dst, srcs, k, trim, n, ST(stream));
+}
+size_t fedfr_robust_pairdist_workspace_bytes(int k, size_t n) { return robust_pairdist_ws_bytes(k, n); }
+int fedfr_robust_pairdist(const float* const* xs, int k, size_t n, double* dist, void* workspace, size_t workspace_bytes, void* stream) {
+  return robust_pairdist(xs, k, n, dist, workspace, workspace_bytes, ST(stream));
+}
+int fedfr_robust_krum_select(const double* dist, int k, int f, int m, double* score, int* selected, void* stream) {
+  return robust_krum_select(dist, k, f, m, score, selected, ST(stream));
 }
 int fedfr_pfc_rand(float* perm, int n, unsigned long long seed, unsigned long long step, void* stream) {
   return optim_pfc_rand(perm, n, seed, step, ST(stream));

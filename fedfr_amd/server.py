@@ -2,7 +2,8 @@
 averaging of client models, as HIP kernels over flat buffers (single process) or one RCCL all-reduce over
 xGMI when every client is its own rank (one client = one MI355X); the spread-out step on the clients' class centres
 (reference server.py:48-63, :340-371) on one fused HIP kernel; and the round's 1:1 verification of the global model with its
-checkpoints (reference server.py:135-148)."""
+checkpoints (reference server.py:135-148).  Build extensions beyond the reference's FedAvg: the server optimisers (``FedOpt``) and the
+robust rules (``FedRobust``: coordinate-wise trimmed mean / median, Krum / Multi-Krum)."""
 from __future__ import annotations
 
 import copy
@@ -262,6 +263,147 @@ def FedOpt(global_state, models: List[dict], weights: Sequence[float], opt: Serv
     return FlatStateDict.from_flat((P, Bf, N), models[0].table, models[0].layers)
 
 
+# ---- robust aggregation: csrc/robust.hip robust_trimmed_mean_kernel / robust_pairdist_kernel / robust_krum_select_kernel
+ROBUST_ALG_KINDS = {"TrimmedMean", "CoordMedian", "Krum", "MultiKrum"}
+ROBUST_MAX_CLIENTS = 32
+
+
+class RobustAggregator:
+    """One robust aggregation rule over the clients' flat states.  ``kind``: "TrimmedMean" (coordinate-wise mean of what is left after the
+    b smallest and b largest values of every coordinate are dropped; b = ``trim`` if given, else floor(``trim_ratio`` k)), "CoordMedian"
+    (b = (k - 1) // 2: the middle value or the mean of the middle two; ``trim`` / ``trim_ratio`` are ignored), "Krum" (the ONE client
+    whose k - f - 2 nearest neighbours are nearest, f = ``num_byzantine``) or "MultiKrum" (the plain mean of the m best-scored clients,
+    m = ``multi_m`` or k - f).  ``last_selected`` (ascending client indices), ``last_scores`` and ``last_dist`` (host numpy arrays) hold
+    the last Krum round for logging; they are None for the coordinate-wise kinds.  At most 32 clients: an order statistic (and a
+    selection) cannot be chained over groups of clients the way a sum can."""
+
+    def __init__(self, kind, trim_ratio=0.1, trim=None, num_byzantine=1, multi_m=None):
+        if kind not in ROBUST_ALG_KINDS:
+            raise ValueError("RobustAggregator: kind must be one of %s (got %r)" % (sorted(ROBUST_ALG_KINDS), kind))
+        self.kind = kind
+        self.trim_ratio = float(trim_ratio)
+        self.trim = None if trim is None else int(trim)
+        self.num_byzantine = int(num_byzantine)
+        self.multi_m = None if multi_m is None else int(multi_m)
+        if not 0.0 <= self.trim_ratio < 0.5:
+            raise ValueError("RobustAggregator: trim_ratio must be in [0, 0.5) (got %r)" % (trim_ratio,))
+        if self.trim is not None and self.trim < 0:
+            raise ValueError("RobustAggregator: trim must be >= 0 (got %r)" % (trim,))
+        if self.num_byzantine < 0:
+            raise ValueError("RobustAggregator: num_byzantine must be >= 0 (got %r)" % (num_byzantine,))
+        if self.multi_m is not None and self.multi_m < 1:
+            raise ValueError("RobustAggregator: multi_m must be >= 1 (got %r)" % (multi_m,))
+        self.last_selected = self.last_scores = self.last_dist = None
+        self._ws = None
+
+    @property
+    def coordinate_wise(self) -> bool:
+        return self.kind in ("TrimmedMean", "CoordMedian")
+
+    def trim_count(self, k: int) -> int:
+        """b for k clients (the coordinate-wise kinds)"""
+        if self.kind == "CoordMedian":
+            return (k - 1) // 2
+        return self.trim if self.trim is not None else int(np.floor(self.trim_ratio * k))
+
+    def select_count(self, k: int) -> int:
+        """m for k clients (the Krum kinds)"""
+        if self.kind == "Krum":
+            return 1
+        return self.multi_m if self.multi_m is not None else k - self.num_byzantine
+
+    def validate(self, k: int):
+        """ValueError for a client count this rule cannot serve"""
+        if k < 1:
+            raise ValueError("RobustAggregator(%s): no client states" % self.kind)
+        if k > ROBUST_MAX_CLIENTS:
+            raise ValueError("RobustAggregator(%s): %d clients, at most %d in one aggregation" % (self.kind, k, ROBUST_MAX_CLIENTS))
+        if self.coordinate_wise:
+            b = self.trim_count(k)
+            if 2 * b >= k:
+                raise ValueError("RobustAggregator(%s): trimming %d values at each end leaves nothing of %d clients (needs 2 b < k)"
+                                 % (self.kind, b, k))
+        else:
+            f, m = self.num_byzantine, self.select_count(k)
+            if k < 2 * f + 3:
+                raise ValueError("RobustAggregator(%s): %d clients with num_byzantine = %d (needs k >= 2 f + 3)" % (self.kind, k, f))
+            if not 1 <= m <= k - f:
+                raise ValueError("RobustAggregator(%s): selecting m = %d of %d clients with num_byzantine = %d (needs 1 <= m <= k - f)"
+                                 % (self.kind, m, k, f))
+
+    def trimmed_mean(self, dst: torch.Tensor, srcs: Sequence[torch.Tensor]):
+        """dst = the coordinate-wise trimmed mean of ``srcs`` at this rule's b (fedfr_robust_trimmed_mean: one pass, every state read once)"""
+        import ctypes as C
+        k = len(srcs)
+        self.validate(k)
+        ServerOptimizer._check(dst, srcs, "FedRobust")
+        ptrs = (C.c_void_p * k)(*[t.data_ptr() for t in srcs])
+        _C.call("fedfr_robust_trimmed_mean", dst.data_ptr(), ptrs, k, self.trim_count(k), dst.numel(), _C.stream())
+
+    def select(self, xs: Sequence[torch.Tensor]) -> List[int]:
+        """Krum / Multi-Krum: the ascending indices of the selected states.  Distances and scores are computed on the device
+        (fedfr_robust_pairdist, fedfr_robust_krum_select) into one buffer; then the host reads ``selected``, ``score`` and the distance
+        matrix (kept as ``last_dist`` for logging) back in ONE blocking copy of 2 k + k^2 doubles: THE one synchronisation of a robust
+        round (against a round of ~100 ms or more), needed because the
+        choice of the states to average is made by the host.  RuntimeError if a selected score is not finite (fewer than m clients have
+        k - f - 2 finite neighbours: nothing trustworthy to select)."""
+        import ctypes as C
+        k = len(xs)
+        self.validate(k)
+        ServerOptimizer._check(xs[0], xs, "FedRobust")
+        n, dev = xs[0].numel(), xs[0].device
+        need = int(_C.lib().fedfr_robust_pairdist_workspace_bytes(k, n))
+        if self._ws is None or self._ws.numel() * 8 < need or self._ws.device != dev:
+            self._ws = torch.empty((need + 7) // 8, dtype=torch.float64, device=dev)
+        # one device buffer of 2 k + k^2 doubles: [score | selected (k int32 in the first half of k doubles) | dist], so that ONE copy brings all back
+        out = torch.zeros(2 * k + k * k, dtype=torch.float64, device=dev)
+        score, sel, dist = out[:k], out[k:2 * k], out[2 * k:]
+        ptrs = (C.c_void_p * k)(*[t.data_ptr() for t in xs])
+        _C.call("fedfr_robust_pairdist", ptrs, k, n, dist.data_ptr(), self._ws.data_ptr(), self._ws.numel() * 8, _C.stream())
+        _C.call("fedfr_robust_krum_select", dist.data_ptr(), k, self.num_byzantine, self.select_count(k), score.data_ptr(), sel.data_ptr(),
+                _C.stream())
+        host = out.cpu().numpy()                                    # the synchronisation: one blocking copy
+        flags = host[k:2 * k].view(np.int32)[:k]
+        self.last_scores, self.last_dist = host[:k].copy(), host[2 * k:].reshape(k, k).copy()
+        self.last_selected = [int(i) for i in np.flatnonzero(flags)]
+        if not all(np.isfinite(self.last_scores[i]) for i in self.last_selected):
+            raise RuntimeError("fedfr_amd.FedRobust(%s): the score of a selected client is not finite (scores %s): fewer than %d clients "
+                               "sent finite states" % (self.kind, self.last_scores.tolist(), self.select_count(k)))
+        return self.last_selected
+
+
+def FedRobust(models: List[dict], weights: Sequence[float], agg: RobustAggregator):
+    """One robust aggregation of GPU ``FlatStateDict``s.
+    TrimmedMean / CoordMedian: the parameters and the BN running statistics each go through the coordinate-wise rule, UNWEIGHTED (the
+    data sizes are client-reported: weighting by them would hand a poisoning client its weight back); every kept value of a
+    ``running_var`` is >= 0, so the result is.  The ``num_batches_tracked`` counters take ``FedPavg``'s path (data-size weights, float).
+    Krum / MultiKrum: distances over the PARAMETER buffer, selection, then ``FedPavg`` of the selected states with unit weights (the
+    existing kernels: bit-identical to calling it so).  One host synchronisation, in ``RobustAggregator.select``."""
+    if not models or not all(isinstance(m, FlatStateDict) and m.flat is not None for m in models):
+        raise RuntimeError("fedfr_amd.FedRobust: the client states must be FlatStateDicts (client.flat_state_dict)")
+    if len(weights) != len(models):
+        raise RuntimeError("fedfr_amd.FedRobust: %d weights for %d client states" % (len(weights), len(models)))
+    agg.validate(len(models))
+    p0, b0, n0 = models[0].flat
+    if not p0.is_cuda:
+        raise RuntimeError("fedfr_amd.FedRobust: state tensors must be on the GPU (no CPU fallback)")
+    if not agg.coordinate_wise:
+        chosen = agg.select([m.flat[0] for m in models])
+        return FedPavg([models[i] for i in chosen], [1.0] * len(chosen))
+    tot = sum(weights)
+    ws = [w / tot for w in weights]
+    P, Bf = torch.empty_like(p0), torch.empty_like(b0)
+    N = torch.empty(n0.numel(), dtype=f32, device=p0.device)
+    agg.trimmed_mean(P, [m.flat[0] for m in models])
+    if Bf.numel():
+        agg.trimmed_mean(Bf, [m.flat[1] for m in models])
+    for i, (m, w) in enumerate(zip(models, ws)):            # counters: FedPavg's flat path, line for line
+        n = m.flat[2]
+        if n.numel():
+            _C.call("fedfr_fedavg_i64", N.data_ptr(), n.data_ptr(), float(np.float32(w)), n.numel(), 1 if i else 0, None, _C.stream())
+    return FlatStateDict.from_flat((P, Bf, N), models[0].table, models[0].layers)
+
+
 def FedAvg_on_FC(pretrain_fc, models, weights, p):
     """reference server.py:36-46."""
     tot = sum(weights)
@@ -318,6 +460,9 @@ def fedavg_all_reduce(backbone, data_size: float, total_size: float, comm=None, 
     this path the clip would have to be applied by every rank to its OWN delta before the exchange (one more norm pass per rank) — a
     different algorithm from the clip ``FedOpt`` applies inside one aggregation, and not provided here."""
     from .comm import TorchDistComm
+    if isinstance(server_opt, RobustAggregator):
+        raise ValueError("fedavg_all_reduce: a robust rule (%s) is not a sum and cannot ride a sum-all-reduce (every rank would need every "
+                         "state: an all-gather, not provided here); use FedRobust" % server_opt.kind)
     if server_opt is not None:
         if server_opt.clip_norm > 0:
             raise ValueError("fedavg_all_reduce: clip_norm > 0 is not supported on the all-reduce path (clipping a rank's own delta before "
@@ -409,6 +554,7 @@ class Server(object):
         self.callback_local_veri = None              # local 1:1 verification (server.py:105-108): see enable_local_verification()
         self.local_candidates = []
         self.server_opt = None                       # ServerOptimizer of aggr_alg FedAvgM / FedAdagrad / FedAdam / FedYogi (built in train())
+        self.robust_agg = None                       # RobustAggregator of aggr_alg TrimmedMean / CoordMedian / Krum / MultiKrum (built in train())
 
     def enable_local_verification(self, callback, candidates=None):
         """reference server.py:105-108: ``callback`` (``eval_local.CallBack_LocalVerifi``) is handed to the clients whose ``cid`` is a
@@ -452,8 +598,15 @@ class Server(object):
     def train(self):
         from .config import config as cfg
         aggr_alg = getattr(self.args, "aggr_alg", "FedAvg")
-        if aggr_alg not in ("FedAvg", "FedProx") and aggr_alg not in AGGR_ALG_KINDS:      # before a round of client training is spent on it
-            raise ValueError("Server.train: unknown aggr_alg %r (FedAvg, FedProx, %s)" % (aggr_alg, ", ".join(AGGR_ALG_KINDS)))
+        if aggr_alg not in ("FedAvg", "FedProx") and aggr_alg not in AGGR_ALG_KINDS and aggr_alg not in ROBUST_ALG_KINDS:      # before a round of client training is spent on it
+            raise ValueError("Server.train: unknown aggr_alg %r (FedAvg, FedProx, %s, %s)"
+                             % (aggr_alg, ", ".join(AGGR_ALG_KINDS), ", ".join(sorted(ROBUST_ALG_KINDS))))
+        if aggr_alg in ROBUST_ALG_KINDS:                   # a client count the rule cannot serve: also before anybody trains
+            if getattr(self, "robust_agg", None) is None or self.robust_agg.kind != aggr_alg:      # one aggregator per server (it keeps the distance workspace)
+                a = self.args
+                self.robust_agg = RobustAggregator(aggr_alg, trim_ratio=getattr(a, "trim_ratio", 0.1), num_byzantine=getattr(a, "num_byzantine", 1),
+                                                   multi_m=getattr(a, "multi_krum_m", None))
+            self.robust_agg.validate(len(self.current_client_list))
         models, models_fc, losses_, data_sizes = [], [], [], []
         public = bool(getattr(self.args, "add_pretrained_data", False))
         return_all = bool(getattr(self.args, "return_all", False))
@@ -545,6 +698,15 @@ class Server(object):
                                                   beta2=getattr(a, "server_beta2", 0.99), tau=getattr(a, "server_tau", 1e-3),
                                                   clip_norm=getattr(a, "clip_norm", 0.0))
             aggr_state_dict = FedOpt(flat_state_dict(self.federated_model), models, data_sizes, self.server_opt)
+            self.federated_model.load_state_dict(aggr_state_dict)
+        elif aggr_alg in ROBUST_ALG_KINDS:
+            # robust aggregation (a build extension): trimmed mean / median per coordinate, or Krum's selection (one host synchronisation)
+            aggr_state_dict = FedRobust(models, data_sizes, self.robust_agg)
+            if not self.robust_agg.coordinate_wise:
+                kept = set(self.robust_agg.last_selected)
+                cid = [getattr(self.clients[i], "cid", i) for i in order]
+                self.logger.info('%s kept clients %s, rejected clients %s' % (aggr_alg, [cid[j] for j in sorted(kept)],
+                                                                               [cid[j] for j in range(len(order)) if j not in kept]))
             self.federated_model.load_state_dict(aggr_state_dict)
         # the round / epoch counters belong to the driver, as in the reference (train.py:87-88): call step_round() after train()
         return self.avg_loss

@@ -562,6 +562,35 @@ int fedfr_fedopt_multi(int kind, float* x_out, const float* x, const float* cons
                        float* delta_scratch, int first, int last, float lr, float beta1, float one_minus_beta1, float beta2,
                        float one_minus_beta2, float tau, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * robust aggregation — no reference counterpart: every rule above is a weighted sum, so one client that returns a poisoned, diverged or NaN
+ * state moves (or wipes out) the global model.  Coordinate-wise trimmed mean / median (Yin et al., 2018) and Krum / Multi-Krum (Blanchard
+ * et al., 2017) over k <= 32 flat fp32 client states (HOST arrays of k device pointers, as fedfr_fedavg_multi), as streaming passes.
+ * ------------------------------------------------------------------------------------------------ */
+/* dst[j] = (s_trim + s_{trim+1} + ... + s_{k-1-trim}) / (float)(k - 2 trim), s_0 <= ... <= s_{k-1} the k values srcs[i][j] sorted, for every j.
+ *   ORDER: a total order on bit patterns.  A value with bits u that is not a NaN compares by the unsigned key u ^ (sign ? 0xFFFFFFFF :
+ *   0x80000000), so -inf < finite negatives < -0 < +0 < finite positives < +inf.  Every NaN has key 0xFFFFFFFF and sorts last: a NaN client
+ *   is the first to be trimmed.  (A NaN that is kept makes the result NaN.)
+ *   ARITHMETIC: acc = s_trim, then acc = acc + s_j in ascending sorted order, one fp32 rounding per addition; then one correctly rounded
+ *   fp32 division by (float)(k - 2 trim).  Nothing is contracted, so the result can be reproduced bit for bit (tests/robust_cases.py).
+ * trim = (k - 1) / 2 is the coordinate-wise median (the middle value, or the mean of the middle two); trim = 0 the unweighted mean in sorted
+ * order.  Requires 1 <= k <= 32 (an order statistic cannot be chained over groups of clients the way a sum can), 0 <= 2 trim < k, all
+ * buffers 16-byte aligned, dst overlapping no source.  Every source is read once (non-temporal loads); n % 4 trailing elements take a scalar path. */
+int fedfr_robust_trimmed_mean(float* dst, const float* const* srcs, int k, int trim, size_t n, void* stream);
+/* bytes of the workspace fedfr_robust_pairdist needs: k (k - 1) / 2 x grid doubles, grid = min(ceil((n / 4 + 1) / 256), 2048); 0 for k outside
+ * 2..32 or n = 0 */
+size_t fedfr_robust_pairdist_workspace_bytes(int k, size_t n);
+/* dist[i][j] = sum_e (double) d_e^2, d_e = xs[i][e] - xs[j][e] rounded to fp32; square and sum in fp64 (exact product, one rounding per term).
+ * dist: DEVICE array [k][k] of doubles, symmetric, zero diagonal.  Deterministic, no atomics: one fp64 partial per pair and block in
+ * `workspace` (need not be initialised), reduced in a fixed order (lanes, waves, blocks): two runs give identical bits.  2 <= k <= 32; k <= 13
+ * is one pass that reads every state once, more clients are tiled in groups of 8 (at most 16 distinct states per launch).  xs[i] 16-byte,
+ * dist / workspace 8-byte aligned; FEDFR_ERR_WORKSPACE if workspace_bytes < fedfr_robust_pairdist_workspace_bytes(k, n). */
+int fedfr_robust_pairdist(const float* const* xs, int k, size_t n, double* dist, void* workspace, size_t workspace_bytes, void* stream);
+/* Krum / Multi-Krum on a distance matrix (DEVICE [k][k] doubles): score[i] = the k - f - 2 smallest dist[i][j], j != i, added in ascending
+ * order in fp64 (an entry that is not finite counts as +inf); selected[i] = 1 for the m lowest scores (ties: the lower client index), else 0.
+ * score (k doubles) and selected (k int32) are DEVICE arrays.  Requires 2 f + 3 <= k <= 32 and 1 <= m <= k - f (m = 1: Krum). */
+int fedfr_robust_krum_select(const double* dist, int k, int f, int m, double* score, int* selected, void* stream);
+
 int fedfr_pfc_rand(float* perm, int n, unsigned long long seed, unsigned long long step, void* stream);
 int fedfr_pfc_localize(long long* label, int n, long long class_start, int num_local, float* perm, void* stream);
 int fedfr_pfc_topk(const float* perm, int n, int k, long long* index, int* npos_out, void* stream);
