@@ -333,6 +333,12 @@ def ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return t.data_ptr()
 
 
+def ptr_array(tensors):
+    """The ``const float* const*`` argument of the multi-state entry points (fedfr_fedavg_multi, fedfr_fedopt_*, fedfr_robust_*): the
+    tensors' device pointers as a ctypes array."""
+    return (vp * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
 def require_gpu_tensor(t: torch.Tensor, dtype=None, name: str = "tensor") -> torch.Tensor:
     if not t.is_cuda:
         raise RuntimeError("fedfr_amd: %s must live on an MI355X device (got %s); no CPU fallback exists" % (name, t.device))

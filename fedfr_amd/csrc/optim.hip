@@ -3,6 +3,7 @@
 // Reference semantics: torch.optim.SGD as used in client.py:335,527-529; server.py:25-46; partial_fc.py:89-116.
 #include "optim.h"
 #include "gemm_dev.h"   // ProfScope
+#include "multi_state.h"
 
 // ---------------------------------------------------------------------------------------------------------
 // SGD: g += wd*p ; buf = first ? g : mu*buf + g ; p -= lr*buf ; optional bf16 shadow of the new p.
@@ -124,57 +125,50 @@ int optim_fedavg_axpy(float* dst, const float* src, float w, size_t n, int accum
 // FedAvg over up to 8 client states in ONE pass: dst = (accumulate ? dst : 0) + w_0 * src_0 + w_1 * src_1 + ... in ascending client order with
 // the same two roundings per term as fedavg_axpy_kernel, so the result is bit-identical to k sequential axpy launches (server.py:27-33) while
 // every state is read once and the aggregate is written once: (k + 1) x n x 4 B instead of (3k - 1) x n x 4 B.
-struct FedavgMulti {
-  const float* src[8];
+struct StateWeights {      // the weights of up to 8 states as one kernel argument
   float w[8];
 };
+// Two explicit loops on float4, not for_each_vec_then_tail / fvec<4>: this kernel is the yardstick of all the others, and only this form
+// compiles to the instruction stream it has always had (either other form reschedules the vector loop; the callable cost 2 % at k = 8).
 template <int K>
-__global__ __launch_bounds__(256) void fedavg_multi_kernel(float* __restrict__ dst, FedavgMulti p, size_t n, int accumulate) {
+__global__ __launch_bounds__(MULTI_STATE_BLOCK) void fedavg_multi_kernel(float* __restrict__ dst, StatePtrs<8> p, StateWeights wt, size_t n, int accumulate) {
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   const size_t n4 = n / 4;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
     float4 s[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-      typedef float f4v __attribute__((ext_vector_type(4)));
-      const f4v v = __builtin_nontemporal_load(reinterpret_cast<const f4v*>(p.src[k]) + i);      // each state is read once
+      const fvec<4> v = ld_once<4>(p.src[k], i);
       s[k] = make_float4(v.x, v.y, v.z, v.w);
     }
     float4 d = accumulate ? reinterpret_cast<float4*>(dst)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-      d.x = __fadd_rn(d.x, __fmul_rn(p.w[k], s[k].x));
-      d.y = __fadd_rn(d.y, __fmul_rn(p.w[k], s[k].y));
-      d.z = __fadd_rn(d.z, __fmul_rn(p.w[k], s[k].z));
-      d.w = __fadd_rn(d.w, __fmul_rn(p.w[k], s[k].w));
+      d.x = __fadd_rn(d.x, __fmul_rn(wt.w[k], s[k].x));
+      d.y = __fadd_rn(d.y, __fmul_rn(wt.w[k], s[k].y));
+      d.z = __fadd_rn(d.z, __fmul_rn(wt.w[k], s[k].z));
+      d.w = __fadd_rn(d.w, __fmul_rn(wt.w[k], s[k].w));
     }
     reinterpret_cast<float4*>(dst)[i] = d;
   }
   for (size_t i = n4 * 4 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     float d = accumulate ? dst[i] : 0.f;
 #pragma unroll
-    for (int k = 0; k < K; ++k) d = __fadd_rn(d, __fmul_rn(p.w[k], p.src[k][i]));
+    for (int k = 0; k < K; ++k) d = __fadd_rn(d, __fmul_rn(wt.w[k], p.src[k][i]));
     dst[i] = d;
   }
 }
 int optim_fedavg_multi(float* dst, const float* const* srcs, const float* ws, int k, size_t n, int accumulate, hipStream_t st) {
   FEDFR_REQUIRE(dst && srcs && ws && n > 0 && k >= 1 && k <= 8, "fedavg_multi: bad args (k=%d)", k);
-  FedavgMulti p{};
+  StatePtrs<8> p{};
+  StateWeights wt{};
   uintptr_t al = (uintptr_t)dst;
-  for (int i = 0; i < k; ++i) {
-    FEDFR_REQUIRE(srcs[i] != nullptr, "fedavg_multi: source %d is null", i);
-    p.src[i] = srcs[i];
-    p.w[i] = ws[i];
-    al |= (uintptr_t)srcs[i];
-  }
+  FEDFR_TRY(state_ptrs_fill(p, srcs, k, "fedavg_multi", "source", al));
+  for (int i = 0; i < k; ++i) wt.w[i] = ws[i];
   FEDFR_REQUIRE((al & 15) == 0, "fedavg_multi: buffers must be 16-byte aligned");
-  const size_t work = n / 4 + 1;
-  const int grid = (int)((work + 255) / 256 > 2048 ? 2048 : (work + 255) / 256);
-  switch (k) {
-#define FM_CASE(K_) case K_: hipLaunchKernelGGL(fedavg_multi_kernel<K_>, dim3(grid), dim3(256), 0, st, dst, p, n, accumulate); break;
-    FM_CASE(1) FM_CASE(2) FM_CASE(3) FM_CASE(4) FM_CASE(5) FM_CASE(6) FM_CASE(7) FM_CASE(8)
-#undef FM_CASE
-  }
+  dispatch_int<1, 8>(k, [&](auto kc) {
+    hipLaunchKernelGGL(fedavg_multi_kernel<decltype(kc)::value>, dim3(multi_state_grid(n)), dim3(MULTI_STATE_BLOCK), 0, st, dst, p, wt, n, accumulate);
+  });
   FEDFR_LAUNCH_CHECK("fedavg_multi");
   return FEDFR_OK;
 }
@@ -197,7 +191,7 @@ int optim_fedavg_i64(float* acc, const long long* src, float w, int n, int accum
 
 // ---------------------------------------------------------------------------------------------------------
 // Server optimisers (Reddi et al., "Adaptive Federated Optimization"): FedAvgM / FedAdagrad / FedAdam / FedYogi on the flat parameter
-// buffer, with a per-client update-norm clip.  Two streaming passes, both siblings of fedavg_multi_kernel:
+// buffer, with a per-client update-norm clip.  Two streaming passes on the skeleton fedavg_multi_kernel uses (multi_state.h):
 //   fedopt_sqnorm_kernel<K>       sq_i = sum_j (x_i[j] - x[j])^2 per client (fp32 subtract, fp64 square and sum; no atomics: one fp64
 //                                 partial per client and block, added in ascending block order by fedopt_sqnorm_final_kernel, which also forms
 //                                 coef_i = w_i min(1, clip / sqrt(sq_i)) on the device: no host synchronisation between the two passes)
@@ -208,94 +202,42 @@ int optim_fedavg_i64(float* acc, const long long* src, float w, int n, int accum
 // (-fhip-fp32-correctly-rounded-divide-sqrt) expands __builtin_sqrtf and the division behind __fdiv_rn to correctly rounded sequences.
 // ---------------------------------------------------------------------------------------------------------
 enum { FEDOPT_AVGM = 0, FEDOPT_ADAGRAD = 1, FEDOPT_ADAM = 2, FEDOPT_YOGI = 3 };
-struct FedoptSrc {
-  const float* src[8];
-};
 struct FedoptHyper {
   float lr, b1, omb1, b2, omb2, tau;      // omb1 = 1 - beta1, omb2 = 1 - beta2: formed by the host in fp32
 };
-static inline int fedopt_grid(size_t n) {      // fedavg_multi's rule
-  const size_t work = n / 4 + 1;
-  return (int)((work + 255) / 256 > 2048 ? 2048 : (work + 255) / 256);
-}
-typedef float fedopt_f4v __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 fedopt_ld_once(const float* p, size_t i4) {      // a state that is read exactly once
-  const fedopt_f4v v = __builtin_nontemporal_load(reinterpret_cast<const fedopt_f4v*>(p) + i4);
-  return make_float4(v.x, v.y, v.z, v.w);
-}
 
 template <int K>
-__global__ __launch_bounds__(256) void fedopt_sqnorm_kernel(const float* __restrict__ x, FedoptSrc p, size_t n, double* __restrict__ part) {
+__global__ __launch_bounds__(MULTI_STATE_BLOCK) void fedopt_sqnorm_kernel(const float* __restrict__ x, StatePtrs<8> p, size_t n, double* __restrict__ part) {
   __shared__ double red[4][8];
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  const size_t n4 = n / 4;
   double acc[K];
 #pragma unroll
   for (int k = 0; k < K; ++k) acc[k] = 0.0;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    float4 s[K];
+  for_each_vec_then_tail<4>(n, [&](auto width, size_t i) {
+    constexpr int W = decltype(width)::value;
+    fvec<W> s[K];
 #pragma unroll
-    for (int k = 0; k < K; ++k) s[k] = fedopt_ld_once(p.src[k], i);
-    const float4 xv = fedopt_ld_once(x, i);
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      // the square of an fp32 value is exact in fp64 (48 bits): fma(d, d, acc) == acc + d * d with ONE rounding either way
-      const double d0 = (double)__fsub_rn(s[k].x, xv.x), d1 = (double)__fsub_rn(s[k].y, xv.y);
-      const double d2 = (double)__fsub_rn(s[k].z, xv.z), d3 = (double)__fsub_rn(s[k].w, xv.w);
-      acc[k] = __fma_rn(d0, d0, acc[k]);
-      acc[k] = __fma_rn(d1, d1, acc[k]);
-      acc[k] = __fma_rn(d2, d2, acc[k]);
-      acc[k] = __fma_rn(d3, d3, acc[k]);
-    }
-  }
-  for (size_t i = n4 * 4 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const float xv = x[i];
+    for (int k = 0; k < K; ++k) s[k] = ld_once<W>(p.src[k], i);
+    const fvec<W> xv = ld_once<W>(x, i);
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-      const double d = (double)__fsub_rn(p.src[k][i], xv);
-      acc[k] = __fma_rn(d, d, acc[k]);
-    }
-  }
-  // lanes: xor-shuffle tree; waves: LDS, ascending wave; blocks: fedopt_sqnorm_final_kernel, ascending block.  All three orders are fixed
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
-  for (int k = 0; k < K; ++k) {
-    const double t = wave_sum_d(acc[k]);
-    if (lane == 0) red[w][k] = t;
-  }
-  __syncthreads();
-  if (threadIdx.x < K) {
-    const int k = threadIdx.x;
-    part[(size_t)k * gridDim.x + blockIdx.x] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
-  }
+      for (int c = 0; c < W; ++c) {
+        // the square of an fp32 value is exact in fp64 (48 bits): fma(d, d, acc) == acc + d * d with ONE rounding either way
+        const double d = (double)__fsub_rn(s[k][c], xv[c]);
+        acc[k] = __fma_rn(d, d, acc[k]);
+      }
+    }
+  });
+  // lanes, waves: block_partial_d; blocks: fedopt_sqnorm_final_kernel, ascending block.  All three orders are fixed
+  block_partial_d<K>(acc, red, part, [](int k) { return k; });
 }
-struct FedoptW {
-  float w[8];
-};
-// one block, wave i owns client i: its `grid` partials are added in ascending block order, coef_i is formed in fp64 and rounded to fp32 once.
-// A lone thread walking the row pays a memory round trip per handful of partials (measured: ~0.1 ms of a 0.54 ms call at grid = 2048); here the
-// wave fetches 256 partials at a time, one per lane and load, and every lane adds them in order out of the lanes' registers (v_readlane), so
-// the serial part is the chain of 2048 fp64 additions and nothing else.  Slots past `grid` hold 0.0: s + 0.0 == s bit for bit (s >= +0).
-__global__ __launch_bounds__(512) void fedopt_sqnorm_final_kernel(const double* __restrict__ part, int grid, int k, FedoptW wt, float clip,
+// one block, wave i owns client i: its `grid` partials are added in ascending block order (ordered_partial_sum), coef_i is formed in fp64 and
+// rounded to fp32 once.
+__global__ __launch_bounds__(512) void fedopt_sqnorm_final_kernel(const double* __restrict__ part, int grid, int k, StateWeights wt, float clip,
                                                                   double* __restrict__ sq, float* __restrict__ coef) {
   const int i = threadIdx.x >> 6, lane = threadIdx.x & 63;
   if (i >= k) return;
-  const double* row = part + (size_t)i * grid;
-  double s = 0.0;
-  for (int b0 = 0; b0 < grid; b0 += 256) {
-    double p[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int b = b0 + 64 * q + lane;
-      p[q] = b < grid ? row[b] : 0.0;
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int lo = __double2loint(p[q]), hi = __double2hiint(p[q]);
-#pragma unroll
-      for (int j = 0; j < 64; ++j) s += __hiloint2double(__builtin_amdgcn_readlane(hi, j), __builtin_amdgcn_readlane(lo, j));
-    }
-  }
+  const double s = ordered_partial_sum(part + (size_t)i * grid, grid, lane);
   if (lane != 0) return;
   sq[i] = s;
   double c = (double)wt.w[i];
@@ -307,34 +249,28 @@ __global__ __launch_bounds__(512) void fedopt_sqnorm_final_kernel(const double* 
 }
 size_t optim_fedopt_sqnorm_ws_bytes(int k, size_t n) {
   if (k < 1 || k > 8 || n == 0) return 0;
-  return (size_t)k * fedopt_grid(n) * sizeof(double);
+  return (size_t)k * multi_state_grid(n) * sizeof(double);
 }
 int optim_fedopt_sqnorm(const float* x, const float* const* xs, const float* ws, int k, size_t n, float clip, double* sq, float* coef,
                         void* wsp, size_t ws_bytes, hipStream_t st) {
   FEDFR_REQUIRE(x && xs && ws && sq && coef && wsp && n > 0 && k >= 1 && k <= 8, "fedopt_sqnorm: bad args (k=%d)", k);
   FEDFR_REQUIRE(clip == clip, "fedopt_sqnorm: clip is NaN");
-  FedoptSrc p{};
-  FedoptW wt{};
+  StatePtrs<8> p{};
+  StateWeights wt{};
   uintptr_t al = (uintptr_t)x;
-  for (int i = 0; i < k; ++i) {
-    FEDFR_REQUIRE(xs[i] != nullptr, "fedopt_sqnorm: client state %d is null", i);
-    p.src[i] = xs[i];
-    wt.w[i] = ws[i];
-    al |= (uintptr_t)xs[i];
-  }
+  FEDFR_TRY(state_ptrs_fill(p, xs, k, "fedopt_sqnorm", "client state", al));
+  for (int i = 0; i < k; ++i) wt.w[i] = ws[i];
   FEDFR_REQUIRE((al & 15) == 0, "fedopt_sqnorm: parameter buffers must be 16-byte aligned");
   FEDFR_REQUIRE((((uintptr_t)sq | (uintptr_t)wsp) & 7) == 0 && ((uintptr_t)coef & 3) == 0, "fedopt_sqnorm: sq / workspace must be 8-byte, coef 4-byte aligned");
-  const int grid = fedopt_grid(n);
+  const int grid = multi_state_grid(n);
   if (ws_bytes < (size_t)k * grid * sizeof(double)) {
     fedfr_set_error("fedopt_sqnorm: workspace of %zu bytes, %zu needed", ws_bytes, (size_t)k * grid * sizeof(double));
     return FEDFR_ERR_WORKSPACE;
   }
   double* part = reinterpret_cast<double*>(wsp);
-  switch (k) {
-#define FS_CASE(K_) case K_: hipLaunchKernelGGL(fedopt_sqnorm_kernel<K_>, dim3(grid), dim3(256), 0, st, x, p, n, part); break;
-    FS_CASE(1) FS_CASE(2) FS_CASE(3) FS_CASE(4) FS_CASE(5) FS_CASE(6) FS_CASE(7) FS_CASE(8)
-#undef FS_CASE
-  }
+  dispatch_int<1, 8>(k, [&](auto kc) {
+    hipLaunchKernelGGL(fedopt_sqnorm_kernel<decltype(kc)::value>, dim3(grid), dim3(MULTI_STATE_BLOCK), 0, st, x, p, n, part);
+  });
   FEDFR_LAUNCH_CHECK("fedopt_sqnorm");
   hipLaunchKernelGGL(fedopt_sqnorm_final_kernel, dim3(1), dim3(512), 0, st, part, grid, k, wt, clip, sq, coef);
   FEDFR_LAUNCH_CHECK("fedopt_sqnorm_final");
@@ -362,8 +298,9 @@ __device__ __forceinline__ void fedopt_one(float d, float x, float& m, float& v,
 
 // first: Delta starts at 0 (else at scratch); last: the update is applied (else Delta goes to scratch and m, v, x are untouched).  xo may be x;
 // scratch may be a client state on a non-last pass and xo on the last one (every thread reads index i of each before it writes index i).
+// Two explicit loops, not for_each_vec_then_tail: through the callable 23 of the 32 instantiations need 4-11 more VGPRs.
 template <int K, int KIND>
-__global__ __launch_bounds__(256) void fedopt_multi_kernel(float* xo, const float* x, FedoptSrc p, const float* __restrict__ coef, float* __restrict__ m,
+__global__ __launch_bounds__(MULTI_STATE_BLOCK) void fedopt_multi_kernel(float* xo, const float* x, StatePtrs<8> p, const float* __restrict__ coef, float* __restrict__ m,
                                                            float* __restrict__ v, float* scratch, size_t n, int first, int last,
                                                            FedoptHyper h) {
   constexpr bool HAS_V = KIND != FEDOPT_AVGM;
@@ -373,9 +310,9 @@ __global__ __launch_bounds__(256) void fedopt_multi_kernel(float* xo, const floa
 #pragma unroll
   for (int k = 0; k < K; ++k) c[k] = coef[k];
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    float4 s[K];
+    fvec<4> s[K];
 #pragma unroll
-    for (int k = 0; k < K; ++k) s[k] = fedopt_ld_once(p.src[k], i);
+    for (int k = 0; k < K; ++k) s[k] = ld_once<4>(p.src[k], i);
     const float4 xv = reinterpret_cast<const float4*>(x)[i];
     float4 d = first ? make_float4(0.f, 0.f, 0.f, 0.f) : reinterpret_cast<const float4*>(scratch)[i];
 #pragma unroll
@@ -416,15 +353,6 @@ __global__ __launch_bounds__(256) void fedopt_multi_kernel(float* xo, const floa
     xo[i] = o;
   }
 }
-template <int KIND>
-static void fedopt_launch(int k, int grid, hipStream_t st, float* xo, const float* x, const FedoptSrc& p, const float* coef, float* m, float* v,
-                          float* scratch, size_t n, int first, int last, const FedoptHyper& h) {
-  switch (k) {
-#define FO_CASE(K_) case K_: hipLaunchKernelGGL((fedopt_multi_kernel<K_, KIND>), dim3(grid), dim3(256), 0, st, xo, x, p, coef, m, v, scratch, n, first, last, h); break;
-    FO_CASE(1) FO_CASE(2) FO_CASE(3) FO_CASE(4) FO_CASE(5) FO_CASE(6) FO_CASE(7) FO_CASE(8)
-#undef FO_CASE
-  }
-}
 int optim_fedopt_multi(int kind, float* x_out, const float* x, const float* const* xs, const float* coef, int k, size_t n, float* m, float* v,
                        float* scratch, int first, int last, float lr, float beta1, float one_minus_beta1, float beta2, float one_minus_beta2,
                        float tau, hipStream_t st) {
@@ -434,23 +362,18 @@ int optim_fedopt_multi(int kind, float* x_out, const float* x, const float* cons
   last = last ? 1 : 0;
   FEDFR_REQUIRE((first && last) || scratch, "fedopt_multi: a chained pass (first=%d last=%d) needs the scratch buffer", first, last);
   FEDFR_REQUIRE(!last || (x_out && m && (kind == FEDOPT_AVGM || v)), "fedopt_multi: the last pass needs x_out, m%s", kind == FEDOPT_AVGM ? "" : " and v");
-  FedoptSrc p{};
+  StatePtrs<8> p{};
   uintptr_t al = (uintptr_t)x | (uintptr_t)x_out | (uintptr_t)m | (uintptr_t)v | (uintptr_t)scratch;      // (null: no bits)
-  for (int i = 0; i < k; ++i) {
-    FEDFR_REQUIRE(xs[i] != nullptr, "fedopt_multi: client state %d is null", i);
-    p.src[i] = xs[i];
-    al |= (uintptr_t)xs[i];
-  }
+  FEDFR_TRY(state_ptrs_fill(p, xs, k, "fedopt_multi", "client state", al));
   FEDFR_REQUIRE((al & 15) == 0, "fedopt_multi: buffers must be 16-byte aligned");
   FEDFR_REQUIRE(((uintptr_t)coef & 3) == 0, "fedopt_multi: coef must be 4-byte aligned");
   const FedoptHyper h{lr, beta1, one_minus_beta1, beta2, one_minus_beta2, tau};
-  const int grid = fedopt_grid(n);
-  switch (kind) {
-    case FEDOPT_AVGM: fedopt_launch<FEDOPT_AVGM>(k, grid, st, x_out, x, p, coef, m, v, scratch, n, first, last, h); break;
-    case FEDOPT_ADAGRAD: fedopt_launch<FEDOPT_ADAGRAD>(k, grid, st, x_out, x, p, coef, m, v, scratch, n, first, last, h); break;
-    case FEDOPT_ADAM: fedopt_launch<FEDOPT_ADAM>(k, grid, st, x_out, x, p, coef, m, v, scratch, n, first, last, h); break;
-    default: fedopt_launch<FEDOPT_YOGI>(k, grid, st, x_out, x, p, coef, m, v, scratch, n, first, last, h); break;
-  }
+  dispatch_int<FEDOPT_AVGM, FEDOPT_YOGI>(kind, [&](auto kindc) {
+    dispatch_int<1, 8>(k, [&](auto kc) {
+      hipLaunchKernelGGL((fedopt_multi_kernel<decltype(kc)::value, decltype(kindc)::value>), dim3(multi_state_grid(n)), dim3(MULTI_STATE_BLOCK), 0, st, x_out, x, p,
+                         coef, m, v, scratch, n, first, last, h);
+    });
+  });
   FEDFR_LAUNCH_CHECK("fedopt_multi");
   return FEDFR_OK;
 }

@@ -1,4 +1,4 @@
-// Robust aggregation over k flat fp32 client states: siblings of fedavg_multi_kernel / fedopt_sqnorm_kernel (optim.hip), HBM-bound streaming passes.
+// Robust aggregation over k flat fp32 client states: HBM-bound streaming passes on the skeleton of multi_state.h (as fedavg_multi_kernel / fedopt_sqnorm_kernel, optim.hip).
 //   robust_trimmed_mean_kernel<K, V>   coordinate-wise trimmed mean (Yin et al., 2018); trim = (K - 1) / 2 is the coordinate-wise median
 //   robust_pairdist_kernel<TA, TB>     all pairwise squared distances of the states, fp64, no atomics
 //   robust_krum_select_kernel          Krum / Multi-Krum scores and selection (Blanchard et al., 2017) from the distance matrix, one block
@@ -14,6 +14,7 @@
 // lives in scratch memory.  `trim` is a runtime argument: the kept range is chosen with selects on the unrolled sum.
 #include "robust.h"
 #include "robust_net.h"
+#include "multi_state.h"
 #include <utility>
 
 // ---------------------------------------------------------------------------------------------------------
@@ -53,14 +54,12 @@ __device__ __forceinline__ float robust_kept_mean(const unsigned (&key)[K][V], i
   }
   return __fdiv_rn(acc, cnt);
 }
-template <int K>
-struct RobustSrc {
-  const float* src[K];
-};
 // V floats per lane and load: 4 for K <= 16 (64 key registers at K = 16), 2 for K = 17 .. 32 (64 key registers at K = 32).  dst aliases no source.
+// Two explicit loops, not for_each_vec_then_tail: through the callable most K need 30-60 more VGPRs (K = 8: 41 -> 88) and lose occupancy
+// (profiles/multi_state_resources_v1.txt).
 template <int K, int V>
-__global__ __launch_bounds__(256) void robust_trimmed_mean_kernel(float* __restrict__ dst, RobustSrc<K> p, size_t n, int b) {
-  typedef float vec __attribute__((ext_vector_type(V)));
+__global__ __launch_bounds__(MULTI_STATE_BLOCK) void robust_trimmed_mean_kernel(float* __restrict__ dst, StatePtrs<K> p, size_t n, int b) {
+  typedef fvec<V> vec;
   constexpr auto seq = std::make_index_sequence<robust_make_net<K>().n>{};
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   const size_t nv = n / V;
@@ -68,7 +67,7 @@ __global__ __launch_bounds__(256) void robust_trimmed_mean_kernel(float* __restr
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += stride) {
     vec v[K];
 #pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = __builtin_nontemporal_load(reinterpret_cast<const vec*>(p.src[k]) + i);      // each state is read once; all K loads in flight
+    for (int k = 0; k < K; ++k) v[k] = ld_once<V>(p.src[k], i);      // all K loads in flight
     __builtin_amdgcn_sched_barrier(0);      // keep the K loads together in front of their first use (at some K the scheduler otherwise waits for each in turn)
     unsigned key[K][V];
 #pragma unroll
@@ -90,35 +89,21 @@ __global__ __launch_bounds__(256) void robust_trimmed_mean_kernel(float* __restr
     dst[i] = robust_kept_mean<K, 1>(key, 0, b, cnt);
   }
 }
-static inline int robust_grid(size_t n) {      // fedopt_grid's rule (optim.hip)
-  const size_t work = n / 4 + 1;
-  return (int)((work + 255) / 256 > 2048 ? 2048 : (work + 255) / 256);
-}
-template <int K, int V>
-static void robust_tm_launch(float* dst, const float* const* srcs, size_t n, int trim, hipStream_t st) {
-  RobustSrc<K> p{};
-  for (int i = 0; i < K; ++i) p.src[i] = srcs[i];
-  hipLaunchKernelGGL((robust_trimmed_mean_kernel<K, V>), dim3(robust_grid(n)), dim3(256), 0, st, dst, p, n, trim);
-}
 int robust_trimmed_mean(float* dst, const float* const* srcs, int k, int trim, size_t n, hipStream_t st) {
   FEDFR_REQUIRE(dst && srcs && n > 0, "robust_trimmed_mean: bad args");
   FEDFR_REQUIRE(k >= 1 && k <= 32, "robust_trimmed_mean: k must be 1..32: an order statistic cannot be chained over groups of clients (k=%d)", k);
   FEDFR_REQUIRE(trim >= 0 && trim <= (k - 1) / 2, "robust_trimmed_mean: trim must satisfy 0 <= 2 trim < k (trim=%d k=%d)", trim, k);
+  StatePtrs<32> all{};
   uintptr_t al = (uintptr_t)dst;
-  for (int i = 0; i < k; ++i) {
-    FEDFR_REQUIRE(srcs[i] != nullptr, "robust_trimmed_mean: source %d is null", i);
-    al |= (uintptr_t)srcs[i];
-    FEDFR_REQUIRE(srcs[i] + n <= dst || dst + n <= srcs[i], "robust_trimmed_mean: dst overlaps source %d", i);
-  }
+  FEDFR_TRY(state_ptrs_fill(all, srcs, k, "robust_trimmed_mean", "source", al));
+  for (int i = 0; i < k; ++i) FEDFR_REQUIRE(srcs[i] + n <= dst || dst + n <= srcs[i], "robust_trimmed_mean: dst overlaps source %d", i);
   FEDFR_REQUIRE((al & 15) == 0, "robust_trimmed_mean: buffers must be 16-byte aligned");
-  switch (k) {
-#define TM4(K_) case K_: robust_tm_launch<K_, 4>(dst, srcs, n, trim, st); break;
-#define TM2(K_) case K_: robust_tm_launch<K_, 2>(dst, srcs, n, trim, st); break;
-    TM4(1) TM4(2) TM4(3) TM4(4) TM4(5) TM4(6) TM4(7) TM4(8) TM4(9) TM4(10) TM4(11) TM4(12) TM4(13) TM4(14) TM4(15) TM4(16)
-    TM2(17) TM2(18) TM2(19) TM2(20) TM2(21) TM2(22) TM2(23) TM2(24) TM2(25) TM2(26) TM2(27) TM2(28) TM2(29) TM2(30) TM2(31) TM2(32)
-#undef TM4
-#undef TM2
-  }
+  dispatch_int<1, 32>(k, [&](auto kc) {
+    constexpr int K = decltype(kc)::value;
+    StatePtrs<K> p;      // CAP = K: the kernel argument is no larger than the states it names
+    for (int i = 0; i < K; ++i) p.src[i] = all.src[i];
+    hipLaunchKernelGGL((robust_trimmed_mean_kernel<K, (K <= 16 ? 4 : 2)>), dim3(multi_state_grid(n)), dim3(MULTI_STATE_BLOCK), 0, st, dst, p, n, trim);
+  });
   FEDFR_LAUNCH_CHECK("robust_trimmed_mean");
   return FEDFR_OK;
 }
@@ -131,21 +116,19 @@ int robust_trimmed_mean(float* dst, const float* const* srcs, int k, int trim, s
 // no scratch) is the largest that stays inside the 256 architectural registers (TA = 14 compiles to 256 VGPRs + 34 AGPRs of copies at one wave per
 // SIMD): k <= 13 is ONE launch that reads every state once.  More clients are cut into groups of 8: one TB == 0 launch per group and one TB > 0
 // launch per pair of groups (the 8 x TB pairs between them, float2 loads, <= 64 accumulators, 16 distinct states).
+// Two explicit loops, not for_each_vec_then_tail: through the callable <5, 0> and <6, 0> need 30 and 58 more VGPRs and lose occupancy.
 // ---------------------------------------------------------------------------------------------------------
-struct RobustPairSrc {
-  const float* a[16];
-  const float* b[8];
-};
 __host__ __device__ static inline int robust_pair_index(int i, int j, int k) {      // i < j: row-major upper triangle
   return i * k - i * (i + 1) / 2 + (j - i - 1);
 }
 template <int TA, int TB>
-__global__ __launch_bounds__(256) void robust_pairdist_kernel(RobustPairSrc p, size_t n, int a0, int b0, int k, double* __restrict__ part) {
+__global__ __launch_bounds__(MULTI_STATE_BLOCK) void robust_pairdist_kernel(StatePtrs<16> pa, StatePtrs<8> pb, size_t n, int a0, int b0, int k,
+                                                              double* __restrict__ part) {
   constexpr bool CROSS = TB > 0;
   constexpr int P = CROSS ? TA * TB : TA * (TA - 1) / 2;
   constexpr int V = (CROSS || TA > 8) ? 2 : 4;
   constexpr int NB = CROSS ? TB : 1;
-  typedef float vec __attribute__((ext_vector_type(V)));
+  typedef fvec<V> vec;
   __shared__ double red[4][P];
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   const size_t nv = n / V;
@@ -155,10 +138,10 @@ __global__ __launch_bounds__(256) void robust_pairdist_kernel(RobustPairSrc p, s
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += stride) {
     vec sa[TA], sb[NB];
 #pragma unroll
-    for (int a = 0; a < TA; ++a) sa[a] = __builtin_nontemporal_load(reinterpret_cast<const vec*>(p.a[a]) + i);
+    for (int a = 0; a < TA; ++a) sa[a] = ld_once<V>(pa.src[a], i);
     if (CROSS) {
 #pragma unroll
-      for (int b = 0; b < NB; ++b) sb[b] = __builtin_nontemporal_load(reinterpret_cast<const vec*>(p.b[b]) + i);
+      for (int b = 0; b < NB; ++b) sb[b] = ld_once<V>(pb.src[b], i);
     }
 #pragma unroll
     for (int a = 0; a < TA; ++a) {
@@ -177,10 +160,10 @@ __global__ __launch_bounds__(256) void robust_pairdist_kernel(RobustPairSrc p, s
   for (size_t i = nv * V + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     float sa[TA], sb[NB];
 #pragma unroll
-    for (int a = 0; a < TA; ++a) sa[a] = p.a[a][i];
+    for (int a = 0; a < TA; ++a) sa[a] = pa.src[a][i];
     if (CROSS) {
 #pragma unroll
-      for (int b = 0; b < NB; ++b) sb[b] = p.b[b][i];
+      for (int b = 0; b < NB; ++b) sb[b] = pb.src[b][i];
     }
 #pragma unroll
     for (int a = 0; a < TA; ++a) {
@@ -192,15 +175,7 @@ __global__ __launch_bounds__(256) void robust_pairdist_kernel(RobustPairSrc p, s
       }
     }
   }
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int q = 0; q < P; ++q) {
-    const double t = wave_sum_d(acc[q]);
-    if (lane == 0) red[w][q] = t;
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < P) {
-    const int q = threadIdx.x;
+  block_partial_d<P>(acc, red, part, [&](int q) {      // the row of the workspace: the pair's index among all k states
     int a = 0, b = 0;
     if (CROSS) {
       a = q / NB;
@@ -209,13 +184,11 @@ __global__ __launch_bounds__(256) void robust_pairdist_kernel(RobustPairSrc p, s
       while (robust_pair_index(a + 1, a + 2, TA) <= q && a + 2 < TA) ++a;      // the row of the upper triangle that holds q
       b = a + 1 + (q - robust_pair_index(a, a + 1, TA));
     }
-    const int gi = a0 + a, gj = (CROSS ? b0 : a0) + b;
-    part[(size_t)robust_pair_index(gi, gj, k) * gridDim.x + blockIdx.x] = ((red[0][q] + red[1][q]) + red[2][q]) + red[3][q];
-  }
+    return robust_pair_index(a0 + a, (CROSS ? b0 : a0) + b, k);
+  });
 }
-// one wave per pair: its `grid` partials are added in ascending block order (the scheme of fedopt_sqnorm_final_kernel: 256 partials fetched at a
-// time, one per lane and load, added in order out of the lanes' registers; slots past `grid` hold 0.0 and s + 0.0 == s for s >= +0).  Writes
-// D[i][j] and D[j][i]; the k waves after the last pair write the zero diagonal.
+// one wave per pair: its `grid` partials are added in ascending block order (ordered_partial_sum).  Writes D[i][j] and D[j][i]; the k waves
+// after the last pair write the zero diagonal.
 __global__ __launch_bounds__(256) void robust_pairdist_final_kernel(const double* __restrict__ part, int grid, int k, double* __restrict__ dist) {
   const int gw = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int npairs = k * (k - 1) / 2;
@@ -223,22 +196,7 @@ __global__ __launch_bounds__(256) void robust_pairdist_final_kernel(const double
     if (gw < npairs + k && lane == 0) dist[(size_t)(gw - npairs) * k + (gw - npairs)] = 0.0;
     return;
   }
-  const double* row = part + (size_t)gw * grid;
-  double s = 0.0;
-  for (int b0 = 0; b0 < grid; b0 += 256) {
-    double p[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int b = b0 + 64 * q + lane;
-      p[q] = b < grid ? row[b] : 0.0;
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int lo = __double2loint(p[q]), hi = __double2hiint(p[q]);
-#pragma unroll
-      for (int j = 0; j < 64; ++j) s += __hiloint2double(__builtin_amdgcn_readlane(hi, j), __builtin_amdgcn_readlane(lo, j));
-    }
-  }
+  const double s = ordered_partial_sum(part + (size_t)gw * grid, grid, lane);
   if (lane != 0) return;
   int i = 0;
   while (i + 2 < k && robust_pair_index(i + 1, i + 2, k) <= gw) ++i;
@@ -248,33 +206,17 @@ __global__ __launch_bounds__(256) void robust_pairdist_final_kernel(const double
 }
 size_t robust_pairdist_ws_bytes(int k, size_t n) {
   if (k < 2 || k > 32 || n == 0) return 0;
-  return (size_t)(k * (k - 1) / 2) * robust_grid(n) * sizeof(double);
-}
-static void robust_pd_diag(int ta, int grid, hipStream_t st, const RobustPairSrc& p, size_t n, int a0, int k, double* part) {
-  switch (ta) {
-#define PD_CASE(T_) case T_: hipLaunchKernelGGL((robust_pairdist_kernel<T_, 0>), dim3(grid), dim3(256), 0, st, p, n, a0, a0, k, part); break;
-    PD_CASE(2) PD_CASE(3) PD_CASE(4) PD_CASE(5) PD_CASE(6) PD_CASE(7) PD_CASE(8) PD_CASE(9) PD_CASE(10) PD_CASE(11) PD_CASE(12) PD_CASE(13)
-#undef PD_CASE
-  }
-}
-static void robust_pd_cross(int tb, int grid, hipStream_t st, const RobustPairSrc& p, size_t n, int a0, int b0, int k, double* part) {
-  switch (tb) {
-#define PD_CASE(T_) case T_: hipLaunchKernelGGL((robust_pairdist_kernel<8, T_>), dim3(grid), dim3(256), 0, st, p, n, a0, b0, k, part); break;
-    PD_CASE(1) PD_CASE(2) PD_CASE(3) PD_CASE(4) PD_CASE(5) PD_CASE(6) PD_CASE(7) PD_CASE(8)
-#undef PD_CASE
-  }
+  return (size_t)(k * (k - 1) / 2) * multi_state_grid(n) * sizeof(double);
 }
 int robust_pairdist(const float* const* xs, int k, size_t n, double* dist, void* wsp, size_t ws_bytes, hipStream_t st) {
   FEDFR_REQUIRE(xs && dist && wsp && n > 0, "robust_pairdist: bad args");
   FEDFR_REQUIRE(k >= 2 && k <= 32, "robust_pairdist: k must be 2..32 (k=%d)", k);
+  StatePtrs<32> all{};
   uintptr_t al = 0;
-  for (int i = 0; i < k; ++i) {
-    FEDFR_REQUIRE(xs[i] != nullptr, "robust_pairdist: client state %d is null", i);
-    al |= (uintptr_t)xs[i];
-  }
+  FEDFR_TRY(state_ptrs_fill(all, xs, k, "robust_pairdist", "client state", al));
   FEDFR_REQUIRE((al & 15) == 0, "robust_pairdist: client states must be 16-byte aligned");
   FEDFR_REQUIRE((((uintptr_t)dist | (uintptr_t)wsp) & 7) == 0, "robust_pairdist: dist / workspace must be 8-byte aligned");
-  const int grid = robust_grid(n);
+  const int grid = multi_state_grid(n);
   const size_t need = (size_t)(k * (k - 1) / 2) * grid * sizeof(double);
   if (ws_bytes < need) {
     fedfr_set_error("robust_pairdist: workspace of %zu bytes, %zu needed", ws_bytes, need);
@@ -285,13 +227,18 @@ int robust_pairdist(const float* const* xs, int k, size_t n, double* dist, void*
   const int gs = k <= ONE ? ONE : 8, ng = (k + gs - 1) / gs;
   for (int ga = 0; ga < ng; ++ga) {
     const int a0 = gs * ga, ta = k - a0 < gs ? k - a0 : gs;
-    RobustPairSrc p{};
-    for (int a = 0; a < ta; ++a) p.a[a] = xs[a0 + a];
-    if (ta >= 2) robust_pd_diag(ta, grid, st, p, n, a0, k, part);
+    StatePtrs<16> pa{};
+    StatePtrs<8> pb{};
+    for (int a = 0; a < ta; ++a) pa.src[a] = all.src[a0 + a];
+    dispatch_int<2, ONE>(ta, [&](auto tc) {      // (a last group of one state has no pair of its own)
+      hipLaunchKernelGGL((robust_pairdist_kernel<decltype(tc)::value, 0>), dim3(grid), dim3(MULTI_STATE_BLOCK), 0, st, pa, pb, n, a0, a0, k, part);
+    });
     for (int gb = ga + 1; gb < ng; ++gb) {      // (only with groups of 8, and ga is not the last group here: ta == 8)
       const int b0 = gs * gb, tb = k - b0 < gs ? k - b0 : gs;
-      for (int b = 0; b < tb; ++b) p.b[b] = xs[b0 + b];
-      robust_pd_cross(tb, grid, st, p, n, a0, b0, k, part);
+      for (int b = 0; b < tb; ++b) pb.src[b] = all.src[b0 + b];
+      dispatch_int<1, 8>(tb, [&](auto tc) {
+        hipLaunchKernelGGL((robust_pairdist_kernel<8, decltype(tc)::value>), dim3(grid), dim3(MULTI_STATE_BLOCK), 0, st, pa, pb, n, a0, b0, k, part);
+      });
     }
   }
   FEDFR_LAUNCH_CHECK("robust_pairdist");

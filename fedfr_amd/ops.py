@@ -176,15 +176,13 @@ def sharded_softmax_ce_grad(cosine: torch.Tensor, label: torch.Tensor, s: float,
 
 def sum_slabs(slabs: torch.Tensor) -> torch.Tensor:
     """Σ_s slabs[s] over the split-K slabs [S, ...] of ``sgemm(..., splits=S)``, ascending s (fedfr_fedavg_multi: ≤ 8 tensors per pass)."""
-    import ctypes as C
     slabs = _chk(slabs, "slabs")
     S = slabs.shape[0]
     out = torch.empty_like(slabs[0])
     for s0 in range(0, S, 8):
         k = min(8, S - s0)
-        ptrs = (C.c_void_p * k)(*[slabs[s0 + i].data_ptr() for i in range(k)])
-        wv = (C.c_float * k)(*([1.0] * k))
-        _C.call("fedfr_fedavg_multi", out.data_ptr(), ptrs, wv, k, out.numel(), 1 if s0 else 0, _C.stream())
+        _C.call("fedfr_fedavg_multi", out.data_ptr(), _C.ptr_array(slabs[s0:s0 + k]), (_C.f32 * k)(*([1.0] * k)), k, out.numel(), 1 if s0 else 0,
+                _C.stream())
     return out
 
 

@@ -26,16 +26,66 @@ def _axpy(dst: torch.Tensor, src: torch.Tensor, w: float, accumulate: bool):
             _C.stream())
 
 
+def _check_states(x: torch.Tensor, xs: Sequence[torch.Tensor], what: str):
+    """RuntimeError unless ``x`` and every tensor of ``xs`` are same-shape contiguous fp32 tensors on one GPU: what the multi-state kernels
+    (csrc/multi_state.h) take as raw pointers"""
+    if not x.is_cuda:
+        raise RuntimeError("fedfr_amd.%s: state tensors must be on the GPU (no CPU fallback)" % what)
+    for t in [x] + list(xs):
+        if t.numel() != x.numel() or t.dtype != f32 or not t.is_contiguous() or t.device != x.device:
+            raise RuntimeError("fedfr_amd.%s: states must be same-shape contiguous fp32 tensors on one device" % what)
+
+
+class _Workspace:
+    """the fp64 device buffer a kernel keeps its per-block partial sums in: grown on demand, kept between calls"""
+
+    def __init__(self):
+        self.buf = None
+
+    def ensure(self, nbytes: int, dev):
+        """(pointer, size in bytes) of at least ``nbytes`` on ``dev``"""
+        if self.buf is None or self.buf.numel() * 8 < nbytes or self.buf.device != dev:
+            self.buf = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+        return self.buf.data_ptr(), self.buf.numel() * 8
+
+
 def _multi(dst: torch.Tensor, srcs: Sequence[torch.Tensor], ws: Sequence[float], accumulate: bool):
     """dst (+)= Σ_i ws[i]·srcs[i] over ≤ 8 same-shape contiguous fp32 tensors in one kernel (csrc/optim.hip: fedavg_multi_kernel)."""
-    import ctypes as C
-    k = len(srcs)
-    for t in srcs:
-        if t.numel() != dst.numel() or t.dtype != f32 or not t.is_contiguous() or t.device != dst.device:
-            raise RuntimeError("fedfr_amd.FedPavg: client states must be same-shape contiguous fp32 tensors on one device")
-    ptrs = (C.c_void_p * k)(*[t.data_ptr() for t in srcs])
-    wv = (C.c_float * k)(*[float(np.float32(w)) for w in ws])
-    _C.call("fedfr_fedavg_multi", dst.data_ptr(), ptrs, wv, k, dst.numel(), 1 if accumulate else 0, _C.stream())
+    _check_states(dst, srcs, "FedPavg")
+    wv = (_C.f32 * len(srcs))(*[float(np.float32(w)) for w in ws])
+    _C.call("fedfr_fedavg_multi", dst.data_ptr(), _C.ptr_array(srcs), wv, len(srcs), dst.numel(), 1 if accumulate else 0, _C.stream())
+
+
+def _client_weights(what: str, models: List[dict], weights: Sequence[float], also=()) -> List[float]:
+    """The n_i / Σn of the client states ``models``; RuntimeError unless they (and the states in ``also``) are FlatStateDicts that hold their
+    flat buffers and there is one weight per client.  That the buffers are on the GPU is checked where they reach a kernel."""
+    if not models or not all(isinstance(m, FlatStateDict) and m.flat is not None for m in list(also) + list(models)):
+        raise RuntimeError("fedfr_amd.%s: the %sclient states must be FlatStateDicts (client.flat_state_dict)"
+                           % (what, "global and the " if also else ""))
+    if len(weights) != len(models):
+        raise RuntimeError("fedfr_amd.%s: %d weights for %d client states" % (what, len(weights), len(models)))
+    tot = sum(weights)
+    return [w / tot for w in weights]
+
+
+def _average_stats(models: List[dict], ws: Sequence[float], stats_rule=None):
+    """(Bf, N) of a flat aggregate: the BN running statistics as Σ_i ws[i]·stats_i, ≤ 8 clients per pass of ``_multi`` in ascending order
+    (or ``stats_rule(Bf, [stats_i])`` where the rule has its own), and the ``num_batches_tracked`` counters as the float
+    Σ_i ws[i]·float(counter_i), ascending i: what the reference loop computes for these entries (F9)."""
+    _, b0, n0 = models[0].flat
+    Bf = torch.empty_like(b0)
+    N = torch.empty(n0.numel(), dtype=f32, device=b0.device)
+    if Bf.numel():                                  # (sphnet has no BatchNorm: no running statistics, no counters)
+        if stats_rule is not None:
+            stats_rule(Bf, [m.flat[1] for m in models])
+        else:
+            for c0 in range(0, len(models), 8):
+                _multi(Bf, [m.flat[1] for m in models[c0:c0 + 8]], ws[c0:c0 + 8], c0 > 0)
+    for i, (m, w) in enumerate(zip(models, ws)):
+        n = m.flat[2]
+        if n.numel():
+            _C.call("fedfr_fedavg_i64", N.data_ptr(), n.data_ptr(), float(np.float32(w)), n.numel(), 1 if i else 0, None, _C.stream())
+    return Bf, N
 
 
 def FedPavg(models: List[dict], weights: Sequence[float]):
@@ -45,27 +95,16 @@ def FedPavg(models: List[dict], weights: Sequence[float]):
     bit-identical to it.  int64 ``num_batches_tracked`` entries come back as float32, like the reference (F9).
     Fast path: FlatStateDicts → one pass over up to 8 clients' flat states (3 launches per 8 clients + one per counter vector); generic path: one kernel per key per client.
     """
-    tot = sum(weights)
-    ws = [w / tot for w in weights]
-    if all(isinstance(m, FlatStateDict) and m.flat is not None for m in models):
-        p0, b0, n0 = models[0].flat
-        dev = p0.device
-        if not p0.is_cuda:
-            raise RuntimeError("fedfr_amd.FedPavg: state tensors must be on the GPU (no CPU fallback)")
-        P, Bf = torch.empty_like(p0), torch.empty_like(b0)
-        N = torch.empty(n0.numel(), dtype=f32, device=dev)
+    if models and all(isinstance(m, FlatStateDict) and m.flat is not None for m in models):
+        ws = _client_weights("FedPavg", models, weights)
+        P = torch.empty_like(models[0].flat[0])
         # up to 8 client states per pass (fedfr_fedavg_multi: every state read once, the aggregate written once; same op order and
         # roundings as one axpy per client, so still bit-identical to the reference loop)
         for c0 in range(0, len(models), 8):
-            grp, wgrp = models[c0:c0 + 8], ws[c0:c0 + 8]
-            _multi(P, [m.flat[0] for m in grp], wgrp, c0 > 0)
-            if Bf.numel():                          # (sphnet has no BatchNorm: no running statistics, no counters)
-                _multi(Bf, [m.flat[1] for m in grp], wgrp, c0 > 0)
-        for i, (m, w) in enumerate(zip(models, ws)):
-            n = m.flat[2]
-            if n.numel():
-                _C.call("fedfr_fedavg_i64", N.data_ptr(), n.data_ptr(), float(np.float32(w)), n.numel(), 1 if i else 0, None, _C.stream())
-        return FlatStateDict.from_flat((P, Bf, N), models[0].table, models[0].layers)
+            _multi(P, [m.flat[0] for m in models[c0:c0 + 8]], ws[c0:c0 + 8], c0 > 0)
+        return FlatStateDict.from_flat((P, *_average_stats(models, ws)), models[0].table, models[0].layers)
+    tot = sum(weights)
+    ws = [w / tot for w in weights]
     aggr = OrderedDict()
     for name in models[0]:
         t0 = models[0][name]
@@ -123,7 +162,7 @@ class ServerOptimizer:
         self.m = self.v = None
         self.rounds = 0
         self.last_update_sqnorm = self.last_coef = None
-        self._scratch = self._ws = None
+        self._scratch, self._ws = None, _Workspace()
 
     def hyper(self):
         """(lr, beta1, 1 - beta1, beta2, 1 - beta2, tau) as the fp32 values the kernel receives."""
@@ -140,40 +179,26 @@ class ServerOptimizer:
             t = np.float32(self.tau)
             self.v = torch.full((like.numel(),), float(t * t), dtype=f32, device=like.device)
 
-    @staticmethod
-    def _check(x: torch.Tensor, xs: Sequence[torch.Tensor], what: str):
-        if not x.is_cuda:
-            raise RuntimeError("fedfr_amd.%s: state tensors must be on the GPU (no CPU fallback)" % what)
-        for t in [x] + list(xs):
-            if t.numel() != x.numel() or t.dtype != f32 or not t.is_contiguous() or t.device != x.device:
-                raise RuntimeError("fedfr_amd.%s: parameter states must be same-shape contiguous fp32 tensors on one device" % what)
-
     def coefficients(self, x: torch.Tensor, xs: Sequence[torch.Tensor], ws: Sequence[float]) -> torch.Tensor:
         """coef_i = w_i min(1, clip_norm / ||x_i - x||) as a DEVICE tensor (fedfr_fedopt_sqnorm: one pass over x and ≤ 8 client states
         at a time, no host synchronisation); the squared norms stay in ``last_update_sqnorm``."""
-        import ctypes as C
-        self._check(x, xs, "ServerOptimizer")
+        _check_states(x, xs, "ServerOptimizer")
         n, dev = x.numel(), x.device
         sq = torch.empty(len(xs), dtype=torch.float64, device=dev)
         coef = torch.empty(len(xs), dtype=f32, device=dev)
-        need = int(_C.lib().fedfr_fedopt_sqnorm_workspace_bytes(min(8, len(xs)), n))
-        if self._ws is None or self._ws.numel() * 8 < need or self._ws.device != dev:
-            self._ws = torch.empty((need + 7) // 8, dtype=torch.float64, device=dev)
+        wsp = self._ws.ensure(int(_C.lib().fedfr_fedopt_sqnorm_workspace_bytes(min(8, len(xs)), n)), dev)
         for c0 in range(0, len(xs), 8):
             grp = xs[c0:c0 + 8]
-            k = len(grp)
-            ptrs = (C.c_void_p * k)(*[t.data_ptr() for t in grp])
-            wv = (C.c_float * k)(*[float(np.float32(w)) for w in ws[c0:c0 + 8]])
-            _C.call("fedfr_fedopt_sqnorm", x.data_ptr(), ptrs, wv, k, n, float(np.float32(self.clip_norm)), sq.data_ptr() + 8 * c0,
-                    coef.data_ptr() + 4 * c0, self._ws.data_ptr(), self._ws.numel() * 8, _C.stream())
+            wv = (_C.f32 * len(grp))(*[float(np.float32(w)) for w in ws[c0:c0 + 8]])
+            _C.call("fedfr_fedopt_sqnorm", x.data_ptr(), _C.ptr_array(grp), wv, len(grp), n, float(np.float32(self.clip_norm)),
+                    sq.data_ptr() + 8 * c0, coef.data_ptr() + 4 * c0, *wsp, _C.stream())
         self.last_update_sqnorm, self.last_coef = sq, coef
         return coef
 
     def apply(self, x_out: torch.Tensor, x: torch.Tensor, xs: Sequence[torch.Tensor], coef: torch.Tensor):
         """x_out = x + step(Σ_i coef_i (x_i - x)) and the moment update (fedfr_fedopt_multi; ``x_out`` may be ``x``).  More than 8 client
         states chain passes through a scratch Δ buffer, bit-identical to one ascending loop; only the last pass touches m, v and x_out."""
-        import ctypes as C
-        self._check(x, list(xs) + [x_out], "ServerOptimizer")
+        _check_states(x, list(xs) + [x_out], "ServerOptimizer")
         if coef.numel() != len(xs) or coef.dtype != f32 or coef.device != x.device or not coef.is_contiguous():
             raise RuntimeError("fedfr_amd.ServerOptimizer: coef must be a contiguous fp32 device tensor with one entry per client state")
         self._ensure(x)
@@ -182,31 +207,27 @@ class ServerOptimizer:
             self._scratch = torch.empty(n, dtype=f32, device=x.device)
         for c0 in range(0, len(xs), 8):
             grp = xs[c0:c0 + 8]
-            k = len(grp)
-            ptrs = (C.c_void_p * k)(*[t.data_ptr() for t in grp])
-            _C.call("fedfr_fedopt_multi", FEDOPT_KINDS[self.kind], x_out.data_ptr(), x.data_ptr(), ptrs, coef.data_ptr() + 4 * c0, k, n,
+            _C.call("fedfr_fedopt_multi", FEDOPT_KINDS[self.kind], x_out.data_ptr(), x.data_ptr(), _C.ptr_array(grp), coef.data_ptr() + 4 * c0, len(grp), n,
                     self.m.data_ptr(), self.v.data_ptr() if self.adaptive else None,
                     self._scratch.data_ptr() if len(xs) > 8 else None, 1 if c0 == 0 else 0, 1 if c0 + 8 >= len(xs) else 0, *self.hyper(),
                     _C.stream())
         self.rounds += 1
 
     def _pass(self, x_out, x, xi, coef, scratch, first, last):
-        import ctypes as C
-        ptrs = (C.c_void_p * 1)(xi.data_ptr())
-        _C.call("fedfr_fedopt_multi", FEDOPT_KINDS[self.kind], _C.ptr(x_out), x.data_ptr(), ptrs, coef.data_ptr(), 1, x.numel(),
+        _C.call("fedfr_fedopt_multi", FEDOPT_KINDS[self.kind], _C.ptr(x_out), x.data_ptr(), _C.ptr_array([xi]), coef.data_ptr(), 1, x.numel(),
                 _C.ptr(self.m) if last else None, _C.ptr(self.v) if last and self.adaptive else None, scratch.data_ptr(), first, last,
                 *self.hyper(), _C.stream())
 
     def weighted_delta(self, dst: torch.Tensor, x: torch.Tensor, xi: torch.Tensor, w: float):
         """dst = w (x_i - x), the term one client adds to Δ, with the two roundings it has inside ``apply`` (a first, non-last pass of
         fedfr_fedopt_multi whose Δ buffer is ``dst``; ``dst`` may be ``xi``).  Moments and parameters are not touched."""
-        self._check(x, [xi, dst], "ServerOptimizer")
+        _check_states(x, [xi, dst], "ServerOptimizer")
         self._pass(None, x, xi, torch.tensor([w], dtype=f32, device=x.device), dst, 1, 0)
 
     def apply_delta(self, x_out: torch.Tensor, x: torch.Tensor, delta: torch.Tensor):
         """x_out = x + step(Δ) and the moment update for a Δ that already exists (``x_out`` may be ``delta`` or ``x``): the last pass of a
         chain, whose one remaining "client" is x itself and adds 1 (x - x) = 0."""
-        self._check(x, [delta, x_out], "ServerOptimizer")
+        _check_states(x, [delta, x_out], "ServerOptimizer")
         self._ensure(x)
         self._pass(x_out, x, x, torch.ones(1, dtype=f32, device=x.device), delta, 0, 1)
         self.rounds += 1
@@ -237,30 +258,12 @@ def FedOpt(global_state, models: List[dict], weights: Sequence[float], opt: Serv
     coefficients, then the update with ≤ 8 client states per pass).  BN running statistics and ``num_batches_tracked`` are statistics,
     not optimisation variables: they are averaged exactly as ``FedPavg`` averages them (same kernels, order and float counters).
     Only GPU ``FlatStateDict``s are accepted."""
-    states = [global_state] + list(models)
-    if not models or not all(isinstance(m, FlatStateDict) and m.flat is not None for m in states):
-        raise RuntimeError("fedfr_amd.FedOpt: the global and the client states must be FlatStateDicts (client.flat_state_dict)")
-    if len(weights) != len(models):
-        raise RuntimeError("fedfr_amd.FedOpt: %d weights for %d client states" % (len(weights), len(models)))
-    tot = sum(weights)
-    ws = [w / tot for w in weights]
-    x = global_state.flat[0]
-    if not x.is_cuda:
-        raise RuntimeError("fedfr_amd.FedOpt: state tensors must be on the GPU (no CPU fallback)")
-    p0, b0, n0 = models[0].flat
-    xs = [m.flat[0] for m in models]
-    ServerOptimizer._check(x, xs, "FedOpt")
-    P, Bf = torch.empty_like(x), torch.empty_like(b0)
-    N = torch.empty(n0.numel(), dtype=f32, device=x.device)
+    ws = _client_weights("FedOpt", models, weights, also=[global_state])
+    x, xs = global_state.flat[0], [m.flat[0] for m in models]
+    _check_states(x, xs, "FedOpt")
+    P = torch.empty_like(x)
     opt.apply(P, x, xs, opt.coefficients(x, xs, ws))
-    for c0 in range(0, len(models), 8):                 # running statistics and counters: FedPavg's flat path, line for line
-        if Bf.numel():
-            _multi(Bf, [m.flat[1] for m in models[c0:c0 + 8]], ws[c0:c0 + 8], c0 > 0)
-    for i, (m, w) in enumerate(zip(models, ws)):
-        n = m.flat[2]
-        if n.numel():
-            _C.call("fedfr_fedavg_i64", N.data_ptr(), n.data_ptr(), float(np.float32(w)), n.numel(), 1 if i else 0, None, _C.stream())
-    return FlatStateDict.from_flat((P, Bf, N), models[0].table, models[0].layers)
+    return FlatStateDict.from_flat((P, *_average_stats(models, ws)), models[0].table, models[0].layers)
 
 
 # ---- robust aggregation: csrc/robust.hip robust_trimmed_mean_kernel / robust_pairdist_kernel / robust_krum_select_kernel
@@ -294,7 +297,7 @@ class RobustAggregator:
         if self.multi_m is not None and self.multi_m < 1:
             raise ValueError("RobustAggregator: multi_m must be >= 1 (got %r)" % (multi_m,))
         self.last_selected = self.last_scores = self.last_dist = None
-        self._ws = None
+        self._ws = _Workspace()
 
     @property
     def coordinate_wise(self) -> bool:
@@ -333,12 +336,10 @@ class RobustAggregator:
 
     def trimmed_mean(self, dst: torch.Tensor, srcs: Sequence[torch.Tensor]):
         """dst = the coordinate-wise trimmed mean of ``srcs`` at this rule's b (fedfr_robust_trimmed_mean: one pass, every state read once)"""
-        import ctypes as C
         k = len(srcs)
         self.validate(k)
-        ServerOptimizer._check(dst, srcs, "FedRobust")
-        ptrs = (C.c_void_p * k)(*[t.data_ptr() for t in srcs])
-        _C.call("fedfr_robust_trimmed_mean", dst.data_ptr(), ptrs, k, self.trim_count(k), dst.numel(), _C.stream())
+        _check_states(dst, srcs, "FedRobust")
+        _C.call("fedfr_robust_trimmed_mean", dst.data_ptr(), _C.ptr_array(srcs), k, self.trim_count(k), dst.numel(), _C.stream())
 
     def select(self, xs: Sequence[torch.Tensor]) -> List[int]:
         """Krum / Multi-Krum: the ascending indices of the selected states.  Distances and scores are computed on the device
@@ -347,19 +348,15 @@ class RobustAggregator:
         round (against a round of ~100 ms or more), needed because the
         choice of the states to average is made by the host.  RuntimeError if a selected score is not finite (fewer than m clients have
         k - f - 2 finite neighbours: nothing trustworthy to select)."""
-        import ctypes as C
         k = len(xs)
         self.validate(k)
-        ServerOptimizer._check(xs[0], xs, "FedRobust")
+        _check_states(xs[0], xs, "FedRobust")
         n, dev = xs[0].numel(), xs[0].device
-        need = int(_C.lib().fedfr_robust_pairdist_workspace_bytes(k, n))
-        if self._ws is None or self._ws.numel() * 8 < need or self._ws.device != dev:
-            self._ws = torch.empty((need + 7) // 8, dtype=torch.float64, device=dev)
+        wsp = self._ws.ensure(int(_C.lib().fedfr_robust_pairdist_workspace_bytes(k, n)), dev)
         # one device buffer of 2 k + k^2 doubles: [score | selected (k int32 in the first half of k doubles) | dist], so that ONE copy brings all back
         out = torch.zeros(2 * k + k * k, dtype=torch.float64, device=dev)
         score, sel, dist = out[:k], out[k:2 * k], out[2 * k:]
-        ptrs = (C.c_void_p * k)(*[t.data_ptr() for t in xs])
-        _C.call("fedfr_robust_pairdist", ptrs, k, n, dist.data_ptr(), self._ws.data_ptr(), self._ws.numel() * 8, _C.stream())
+        _C.call("fedfr_robust_pairdist", _C.ptr_array(xs), k, n, dist.data_ptr(), *wsp, _C.stream())
         _C.call("fedfr_robust_krum_select", dist.data_ptr(), k, self.num_byzantine, self.select_count(k), score.data_ptr(), sel.data_ptr(),
                 _C.stream())
         host = out.cpu().numpy()                                    # the synchronisation: one blocking copy
@@ -379,29 +376,14 @@ def FedRobust(models: List[dict], weights: Sequence[float], agg: RobustAggregato
     ``running_var`` is >= 0, so the result is.  The ``num_batches_tracked`` counters take ``FedPavg``'s path (data-size weights, float).
     Krum / MultiKrum: distances over the PARAMETER buffer, selection, then ``FedPavg`` of the selected states with unit weights (the
     existing kernels: bit-identical to calling it so).  One host synchronisation, in ``RobustAggregator.select``."""
-    if not models or not all(isinstance(m, FlatStateDict) and m.flat is not None for m in models):
-        raise RuntimeError("fedfr_amd.FedRobust: the client states must be FlatStateDicts (client.flat_state_dict)")
-    if len(weights) != len(models):
-        raise RuntimeError("fedfr_amd.FedRobust: %d weights for %d client states" % (len(weights), len(models)))
+    ws = _client_weights("FedRobust", models, weights)
     agg.validate(len(models))
-    p0, b0, n0 = models[0].flat
-    if not p0.is_cuda:
-        raise RuntimeError("fedfr_amd.FedRobust: state tensors must be on the GPU (no CPU fallback)")
     if not agg.coordinate_wise:
         chosen = agg.select([m.flat[0] for m in models])
         return FedPavg([models[i] for i in chosen], [1.0] * len(chosen))
-    tot = sum(weights)
-    ws = [w / tot for w in weights]
-    P, Bf = torch.empty_like(p0), torch.empty_like(b0)
-    N = torch.empty(n0.numel(), dtype=f32, device=p0.device)
+    P = torch.empty_like(models[0].flat[0])
     agg.trimmed_mean(P, [m.flat[0] for m in models])
-    if Bf.numel():
-        agg.trimmed_mean(Bf, [m.flat[1] for m in models])
-    for i, (m, w) in enumerate(zip(models, ws)):            # counters: FedPavg's flat path, line for line
-        n = m.flat[2]
-        if n.numel():
-            _C.call("fedfr_fedavg_i64", N.data_ptr(), n.data_ptr(), float(np.float32(w)), n.numel(), 1 if i else 0, None, _C.stream())
-    return FlatStateDict.from_flat((P, Bf, N), models[0].table, models[0].layers)
+    return FlatStateDict.from_flat((P, *_average_stats(models, ws, agg.trimmed_mean)), models[0].table, models[0].layers)
 
 
 def FedAvg_on_FC(pretrain_fc, models, weights, p):
@@ -689,7 +671,6 @@ class Server(object):
                 self.pretrained_fc = self.pretrain_fc
         if aggr_alg in ("FedAvg", "FedProx"):
             aggr_state_dict = FedPavg(models, data_sizes)
-            self.federated_model.load_state_dict(aggr_state_dict)
         elif aggr_alg in AGGR_ALG_KINDS:
             # server optimiser (a build extension: the reference's flag runs FedAvg only): one optimiser per server, moments kept across rounds
             if getattr(self, "server_opt", None) is None:
@@ -698,16 +679,16 @@ class Server(object):
                                                   beta2=getattr(a, "server_beta2", 0.99), tau=getattr(a, "server_tau", 1e-3),
                                                   clip_norm=getattr(a, "clip_norm", 0.0))
             aggr_state_dict = FedOpt(flat_state_dict(self.federated_model), models, data_sizes, self.server_opt)
-            self.federated_model.load_state_dict(aggr_state_dict)
-        elif aggr_alg in ROBUST_ALG_KINDS:
-            # robust aggregation (a build extension): trimmed mean / median per coordinate, or Krum's selection (one host synchronisation)
+        else:
+            # ROBUST_ALG_KINDS (nothing else passed the check above).  Robust aggregation (a build extension): trimmed mean / median per
+            # coordinate, or Krum's selection (one host synchronisation)
             aggr_state_dict = FedRobust(models, data_sizes, self.robust_agg)
             if not self.robust_agg.coordinate_wise:
                 kept = set(self.robust_agg.last_selected)
                 cid = [getattr(self.clients[i], "cid", i) for i in order]
                 self.logger.info('%s kept clients %s, rejected clients %s' % (aggr_alg, [cid[j] for j in sorted(kept)],
                                                                                [cid[j] for j in range(len(order)) if j not in kept]))
-            self.federated_model.load_state_dict(aggr_state_dict)
+        self.federated_model.load_state_dict(aggr_state_dict)
         # the round / epoch counters belong to the driver, as in the reference (train.py:87-88): call step_round() after train()
         return self.avg_loss
 

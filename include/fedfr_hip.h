@@ -530,7 +530,7 @@ int fedfr_fedavg_i64(float* acc, const long long* src, float w, int n, int accum
  * an fma), so a result can be reproduced bit for bit on a CPU (tests/fedopt_cases.py).
  * ------------------------------------------------------------------------------------------------ */
 /* bytes of the workspace fedfr_fedopt_sqnorm needs for k clients of n elements: k x grid doubles, grid = min(ceil((n / 4 + 1) / 256), 2048)
- * (fedfr_fedavg_multi's launch rule); 0 for k outside 1..8 or n = 0 */
+ * (multi_state_grid in csrc/multi_state.h: the one launch rule of fedfr_fedavg_multi, fedfr_fedopt_* and fedfr_robust_*); 0 for k outside 1..8 or n = 0 */
 size_t fedfr_fedopt_sqnorm_workspace_bytes(int k, size_t n);
 /* Per-client squared update norms and clipped aggregation coefficients in one pass over x and the k client states (HOST arrays of k device
  * pointers xs / k weights ws, as fedfr_fedavg_multi):
@@ -577,8 +577,8 @@ int fedfr_fedopt_multi(int kind, float* x_out, const float* x, const float* cons
  * order.  Requires 1 <= k <= 32 (an order statistic cannot be chained over groups of clients the way a sum can), 0 <= 2 trim < k, all
  * buffers 16-byte aligned, dst overlapping no source.  Every source is read once (non-temporal loads); n % 4 trailing elements take a scalar path. */
 int fedfr_robust_trimmed_mean(float* dst, const float* const* srcs, int k, int trim, size_t n, void* stream);
-/* bytes of the workspace fedfr_robust_pairdist needs: k (k - 1) / 2 x grid doubles, grid = min(ceil((n / 4 + 1) / 256), 2048); 0 for k outside
- * 2..32 or n = 0 */
+/* bytes of the workspace fedfr_robust_pairdist needs: k (k - 1) / 2 x grid doubles, grid as for fedfr_fedopt_sqnorm_workspace_bytes
+ * (multi_state_grid); 0 for k outside 2..32 or n = 0 */
 size_t fedfr_robust_pairdist_workspace_bytes(int k, size_t n);
 /* dist[i][j] = sum_e (double) d_e^2, d_e = xs[i][e] - xs[j][e] rounded to fp32; square and sum in fp64 (exact product, one rounding per term).
  * dist: DEVICE array [k][k] of doubles, symmetric, zero diagonal.  Deterministic, no atomics: one fp64 partial per pair and block in

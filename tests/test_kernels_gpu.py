@@ -1018,22 +1018,24 @@ def test_pad_input_nhwc():
 def test_fedavg_multi_equals_sequential_axpy(k):
     """fedfr_fedavg_multi (one pass over up to 8 client states; FedPavg's flat path chains passes for more) is bit-identical to one
     fedfr_fedavg_axpy per client in ascending order = the reference loop server.py:27-33 (fp32 multiply, then fp32 add, per client);
-    odd length exercises the scalar tail."""
+    odd length exercises the scalar tail.  At k = 1, 2, 3, 8 also over the sizes of fedopt_cases.SIZES: tail only, below / at / above one
+    float4, around one block, grid-stride wrap with a tail (the tail and wrap code of the kernel's two loops)."""
     import numpy as np
+    import fedopt_cases
     from fedfr_amd import server
     DEV = dev()
-    n = 4 * 50_001 + 3
-    g = torch.Generator().manual_seed(5 + k)
-    srcs = [(torch.randn(n, generator=g) * (1 + i)).to(DEV) for i in range(k)]
-    ws = [float(np.float32((1000.0 + 7 * i) / sum(1000.0 + 7 * j for j in range(k)))) for i in range(k)]
-    ref = torch.empty(n, device=DEV)
-    for i in range(k):
-        _C.call("fedfr_fedavg_axpy", ref.data_ptr(), srcs[i].data_ptr(), ws[i], n, 1 if i else 0, _C.stream())
-    out = torch.full((n,), float("nan"), device=DEV)
-    for c0 in range(0, k, 8):
-        server._multi(out, srcs[c0:c0 + 8], ws[c0:c0 + 8], c0 > 0)
-    assert torch.equal(out, ref)
-    cpu = torch.zeros(n)
-    for i in range(k):
-        cpu = cpu + torch.tensor(ws[i], dtype=torch.float32) * srcs[i].cpu()
-    assert torch.equal(out.cpu(), cpu)                     # and to the reference's own torch expression
+    for n in (4 * 50_001 + 3,) + (fedopt_cases.SIZES if k in fedopt_cases.KS else ()):
+        g = torch.Generator().manual_seed(5 + k)
+        srcs = [(torch.randn(n, generator=g) * (1 + i)).to(DEV) for i in range(k)]
+        ws = [float(np.float32((1000.0 + 7 * i) / sum(1000.0 + 7 * j for j in range(k)))) for i in range(k)]
+        ref = torch.empty(n, device=DEV)
+        for i in range(k):
+            _C.call("fedfr_fedavg_axpy", ref.data_ptr(), srcs[i].data_ptr(), ws[i], n, 1 if i else 0, _C.stream())
+        out = torch.full((n,), float("nan"), device=DEV)
+        for c0 in range(0, k, 8):
+            server._multi(out, srcs[c0:c0 + 8], ws[c0:c0 + 8], c0 > 0)
+        assert torch.equal(out, ref), n
+        cpu = torch.zeros(n)
+        for i in range(k):
+            cpu = cpu + torch.tensor(ws[i], dtype=torch.float32) * srcs[i].cpu()
+        assert torch.equal(out.cpu(), cpu), n                  # and to the reference's own torch expression
