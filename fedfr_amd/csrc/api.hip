@@ -384,6 +384,42 @@ int fedfr_conv2d_dgrad_bnbwd(const uint16_t* dy, const uint16_t* wd, uint16_t* d
   p.bwd_fused = fused_rows;
   return gemm_nt_launch(p, 1, ST(stream));
 }
+// the eval-mode output epilogue of the LDS-DMA conv kernels, one launch (the GemmNT of net.hip: conv_fwd_ep)
+int fedfr_conv2d_fwd_epilogue(const uint16_t* x, const uint16_t* w, uint16_t* y, const float* scale, const float* shift, const float* alpha,
+                              const uint16_t* add, uint16_t* y2, const float* scale2, const float* shift2, int batch, int hin, int cin,
+                              int cout, void* stream) {
+  FEDFR_TRY(conv_args_ok(batch, hin, cin, cout, 3, 1));
+  FEDFR_REQUIRE(x && w && y && scale && shift && (!y2 || (scale2 && shift2)), "conv2d_fwd_epilogue: null argument");
+  if (!gemm_nt_conv_epilogue_ok(hin, cin, cout, batch * hin * hin, 3, 1)) {
+    fedfr_set_error("conv2d_fwd_epilogue: no kernel with the output epilogue serves batch=%d hin=%d cin=%d cout=%d", batch, hin, cin, cout);
+    return FEDFR_ERR_UNSUPPORTED;
+  }
+  GemmNT p{};
+  p.A = BF(x); p.B = BF(w); p.M = batch * hin * hin; p.N = cout; p.K = 9 * cin;
+  p.mode = 1; p.H = hin; p.W = hin; p.C = cin; p.Ho = hin; p.Wo = hin; p.S = 3; p.stride = 1; p.pad = 1; p.up = 1;
+  p.Cb = BFM(y); p.ldc = cout;
+  p.esc = scale; p.esh = shift; p.ealpha = alpha; p.eadd = BF(add);
+  if (y2) { p.Cb2 = BFM(y2); p.esc2 = scale2; p.esh2 = shift2; }
+  return gemm_nt_launch(p, 1, ST(stream));
+}
+// the PReLU-apply dgrad (GemmNT::bmom == 2), one launch (the GemmNT of net_sph.inc: dgrad_prelu)
+int fedfr_conv2d_dgrad_papply(const uint16_t* dy, const uint16_t* wd, uint16_t* dz, int batch, int hin, int cin, int cout, const uint16_t* act_x,
+                              const float* bias, const float* alpha, float* partials, int* rows, void* stream) {
+  FEDFR_TRY(conv_args_ok(batch, hin, cin, cout, 3, 1));
+  FEDFR_REQUIRE(dy && wd && dz && act_x && alpha && partials && rows, "conv2d_dgrad_papply: null argument");
+  *rows = 0;
+  if (!((hin == 14 || hin == 28) && gemm_nt_conv_epilogue_ok(hin, cout, cin, batch * hin * hin, 3, 1))) {
+    fedfr_set_error("conv2d_dgrad_papply: no kernel with the PReLU-apply epilogue serves batch=%d hin=%d cin=%d cout=%d", batch, hin, cin, cout);
+    return FEDFR_ERR_UNSUPPORTED;
+  }
+  GemmNT p{};
+  p.A = BF(dy); p.B = BF(wd); p.N = cin; p.K = 9 * cout; p.Cb = BFM(dz); p.ldc = cin;
+  p.mode = 1; p.M = batch * hin * hin; p.H = hin; p.W = hin; p.C = cout; p.Ho = hin; p.Wo = hin; p.S = 3; p.stride = 1; p.pad = 1; p.up = 1;
+  p.bx = BF(act_x); p.bbeta = bias; p.balpha = alpha;
+  p.bmean = alpha; p.brstd = alpha;                     // (read, never used in this mode)
+  p.bpart = partials; p.bmom = 2; p.bwd_fused = rows;
+  return gemm_nt_launch(p, 1, ST(stream));
+}
 size_t fedfr_conv2d_wgrad_ws_bytes(int batch, int hin, int cin, int cout, int ksize, int stride) {
   const int hout = hin / (stride > 0 ? stride : 1);
   const int NJ = ksize * ksize * cin;

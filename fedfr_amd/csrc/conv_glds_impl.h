@@ -89,6 +89,7 @@ __global__ __launch_bounds__(128 * WN) void conv3x3_glds_kernel(GemmNT p, int st
   constexpr int VG = PWL / 16, NRB = TM + 2 * VG;
   static_assert(PT <= 2 * MW && PT > MW && W_ % R_ == 0 && (R_ + 2) * PWL <= NPA * 8 && NPA % NW == 0 && (BN / 8) % NW == 0 && MPR >= 1 &&
                     !(FUSED && ONECHUNK), "tile geometry");
+  static_assert(!RST || ONECHUNK || !GLDS_ASPREAD || AP <= 6, "padded-raster loop: the next chunk's image goes out one piece per tap over the first taps of a chunk");
   typedef __attribute__((address_space(3))) void* lds_ptr_t;
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
   unsigned char* sA = smem;                       // [2][A_BYTES]

@@ -14,10 +14,15 @@ struct PreluThr {
 };
 __device__ __forceinline__ PreluThr prelu_threshold(float sc, float sh) {
   PreluThr th;
-  const float T = -sh / fabsf(sc);
+  // The threshold must never be -0: with t = -0 the difference t - sgn(sc) x is -0 for x = +0, sc > 0 (sign bit set) although z == 0 belongs to the
+  // negative branch.  The sign of a zero threshold is cleared on the BITS of both forms, so that no floating-point identity decides it.
+  unsigned tb = __float_as_uint(-sh / fabsf(sc));
+  if ((tb & 0x7fffffffu) == 0u) tb = 0u;
+  const float T = __uint_as_float(tb);
   unsigned hb = (unsigned)__builtin_bit_cast(unsigned short, (_Float16)T);      // round to nearest ...
   const float hf = (float)__builtin_bit_cast(_Float16, (unsigned short)hb);
   if (hf > T) hb = hb == 0u ? 0x8001u : ((hb & 0x8000u) ? hb + 1u : hb - 1u);   // ... then down to the largest fp16 <= T
+  if ((hb & 0x7fffu) == 0u) hb = 0u;                                            // (a zero that is left is the largest fp16 <= some T >= 0)
   if (sc == 0.f) hb = sh <= 0.f ? 0x7c00u : 0xfc00u;                            // z = sh everywhere: always / never in the PReLU's negative branch
   th.t162 = hb | (hb << 16);
   th.nsgn2 = sc < 0.f ? 0x3c003c00u : 0xbc00bc00u;

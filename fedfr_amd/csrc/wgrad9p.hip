@@ -389,7 +389,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #elif W9P_SPREAD == 2      // the same four steps, the pieces eight MFMAs apart (slots 4, 12, 20, 28)
                 if (last && (slot & 7) == 4 && slot < 32 && !(W9P_ABLATE & 1)) issue_piece(slot >> 3, it & 1);
                 if (!last && kb < 3 && (slot & 7) == 4 && slot < 32 && !(W9P_ABLATE & 1)) issue_piece(PPS * (kb + 1) + (slot >> 3), (it & 1) ^ 1);
-#else                      // six steps (the last one and steps 0-4 of the next sub-image): 3 + 3 + 3 + 3 + 2 + 2 pieces at slots 33 .. 35
+#else                      // six steps (the last one and steps 0-4 of the next sub-image): 3, 3, 3, 3, 3, 1 pieces at slots 33 .. 35
+                static_assert(KS - 1 >= 5 && 18 >= NPW, "six K-steps of three pieces: five steps in front of the last one, and they must cover a stage's pieces per wave");
                 if (last && slot >= 33 && slot < 36 && !(W9P_ABLATE & 1)) issue_piece(slot - 33, it & 1);
                 if (!last && kb < 5 && slot >= 33 && slot < 36 && 3 * (kb + 1) + slot - 33 < NPW && !(W9P_ABLATE & 1)) issue_piece(3 * (kb + 1) + slot - 33, (it & 1) ^ 1);
 #endif

@@ -189,6 +189,21 @@ int fedfr_conv2d_dgrad_bnbwd(const uint16_t* dy, const uint16_t* wd, uint16_t* d
                              int ksize, int stride, const uint16_t* bn_x, const float* mean, const float* rstd,
                              const float* gamma, const float* beta, const float* alpha, float* partials, int* fused_rows,
                              void* stream);
+/* The two conv epilogues that only whole networks used to reach, one kernel launch each (tests/test_conv_branches_gpu.py).
+ * fedfr_conv2d_fwd_epilogue: the eval-mode forward of a 3x3 / stride-1 conv (what fedfr_net_forward(training = 0) runs under option
+ *   "eval_fuse"): y = acc * scale[n] + shift[n] on the fp32 accumulator, PReLU with alpha[n] (NULL: none), rounded to 16 bits; with add
+ *   [M][cout] y = round16(y + add); with y2, y2 = round16(y * scale2[n] + shift2[n]) of the STORED y.  Served for the shapes the LDS-DMA
+ *   kernels take (14x14 / 28x28 maps with cin, cout multiples of 128, 56x56 with 64 -> 64 / 64 -> 128 / 128 -> 64, 112x112 with 64 -> 64,
+ *   each from the batch at which they run on 128-row tiles); any other shape is FEDFR_ERR_UNSUPPORTED, nothing is launched.
+ * fedfr_conv2d_dgrad_papply: sphnet's dgrad with the backward of the PReLU(+bias) in FRONT of the conv in its epilogue: z = act_x + bias
+ *   (bias NULL: 0), dz = dgrad * (z <= 0 ? alpha[n] : 1) is what is stored, partials [*rows][3][cin] = (sum dz, sum dgrad z over z <= 0, the
+ *   same again); *rows = batch * hin * hin / 196 (28x28 maps on the two-tiles kernel: / 392).  14x14 / 28x28 maps with cin, cout multiples
+ *   of 128 from the batch at which they run on 128-row tiles; any other shape is FEDFR_ERR_UNSUPPORTED, nothing is launched. */
+int fedfr_conv2d_fwd_epilogue(const uint16_t* x, const uint16_t* w, uint16_t* y, const float* scale, const float* shift, const float* alpha,
+                              const uint16_t* add, uint16_t* y2, const float* scale2, const float* shift2, int batch, int hin, int cin,
+                              int cout, void* stream);
+int fedfr_conv2d_dgrad_papply(const uint16_t* dy, const uint16_t* wd, uint16_t* dz, int batch, int hin, int cin, int cout,
+                              const uint16_t* act_x, const float* bias, const float* alpha, float* partials, int* rows, void* stream);
 /* lowest-priority HIP stream for the aux_stream argument of fedfr_net_backward2 (no reference counterpart; the reference trains on
  * one stream).  Destroy with fedfr_stream_destroy. */
 int fedfr_stream_create_low_priority(void** stream);

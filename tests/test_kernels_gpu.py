@@ -48,16 +48,17 @@ CONV_CASES = [
     (2, 28, 128, 128, 3, 1),
     (1, 14, 256, 256, 3, 1),     # M = 196: ragged M tile
     (5, 8, 512, 512, 3, 2),
-    (40, 14, 256, 256, 3, 1),    # M = 7840 -> 128-row tiles with tail
-    # large-M 3x3/s1 shapes take the LDS-halo kernel (fwd + dgrad): every halo size, BN = 64 / 128, ragged M
+    (40, 14, 256, 256, 3, 1),    # M = 7840: a 64-row shape with 36 K-steps -> gemm_nt_glds
+    # large-M 3x3/s1 shapes (fwd + dgrad): the LDS-DMA kernels on 14x14 / 28x28 / 56x56 / 112x112 maps from the batch at which they run on 128-row tiles
+    # (which kernel serves which shape is asserted row by row in test_conv_branches_gpu.py)
     (131, 14, 256, 256, 3, 1),
     (17, 56, 64, 64, 3, 1),
-    (4, 112, 64, 128, 3, 1),
+    (4, 112, 64, 128, 3, 1),     # 64 -> 128 on a 112x112 map: no LDS-DMA instantiation, the generic tiles
     (9, 112, 64, 64, 3, 1),
     (65, 28, 128, 128, 3, 1),
-    (260, 14, 64, 64, 3, 1),     # zero-padded-image kernel, BN = 64 instantiation
+    (260, 14, 64, 64, 3, 1),     # 64 channels on a 14x14 map: no LDS-DMA instantiation, the generic <128,64> tile
     (131, 28, 128, 256, 3, 1),
-    (9, 56, 64, 128, 3, 1),      # LDS-DMA kernel, single input chunk -> 128-wide tile (fwd) / two chunks -> 64-wide tile (dgrad)
+    (9, 56, 64, 128, 3, 1),      # 56x56 below 16 images: 64-row shapes on the generic tiles (the LDS-DMA 64 -> 128 / 128 -> 64 kernels start at B = 16)
     (3, 56, 128, 64, 3, 1),
     # 64 -> 64 channel layers: persistent kernel with the filter bank in registers (conv_c64p.hip): 1, 2 and 5 tiles per workgroup
     (1, 56, 64, 64, 3, 1),
