@@ -1,6 +1,6 @@
 // Train-mode BatchNorm passes WITHOUT the finalize launch between the statistics and their consumer (round 2).
 //
-// A BatchNorm is a grid-wide dependency: statistics over all pixels, then a per-pixel pass.  The row-slab kernels of ew.hip hand the
+// A BatchNorm is a grid-wide dependency: statistics over all pixels, then a per-pixel pass.  The row-slab kernels of bn_rowslab.hip hand the
 // statistics over through a tiny kernel (bn_finalize8 / bn_bwd_finalize8: P partial rows -> per-channel coefficients) because a
 // workgroup that streams whole 512-B pixel rows would have to reduce P x C partials itself.  In an iresnet100 step that is 306
 // launches of 5-6 us in a dependent chain (1.7 ms of 18.5).  Here the consumer does the reduction itself, which is cheap once a
@@ -13,10 +13,11 @@
 //     before the first add) while its first tensor loads are already in flight, derives the coefficients, and group 0 of every slice
 //     writes what later passes need (saved scale / shift / mean / rstd + running statistics; dgamma / dbeta / dalpha);
 //   * partial rows it produces (statistics of its output for the next BatchNorm; the next BatchNorm-backward's sums) are G rows of the
-//     same [row][statistic][C] layout the ew.hip kernels and the conv epilogues write, so fused and unfused passes mix freely.
+//     same [row][statistic][C] layout the bn_rowslab.hip kernels and the conv epilogues write, so fused and unfused passes mix freely.
 // Rows are read and written by different workgroups of one launch with no ordering between them: the output rows must not alias the
 // input rows (net.hip alternates between two partial-row buffers).
 #include "ew.h"
+#include "bn_math.h"
 #include "gemm_dev.h"   // ProfScope
 
 #ifndef BNS_PRIO
@@ -161,7 +162,7 @@ __global__ __launch_bounds__(NTH) void bn_apply_s_kernel(BnApplyS p) {
   opt8(p.alpha, p.part, c0, al, 1.f);
   float4 fv[kFwdFL];
   fan_in_issue<2, kFwdFL>(p.part, p.P, p.C, 2, cs, fv);
-  const double ic = 1.0 / p.count;                      // (ew.h: bn_rsqrt; formed here, under the loads)
+  const double ic = 1.0 / p.count;                      // (bn_math.h: bn_rsqrt; formed here, under the loads)
   asm volatile("" ::"v"(ic));
   uint4 a1[NP], a2[X2 ? NP : 1];
 #pragma unroll
@@ -175,20 +176,12 @@ __global__ __launch_bounds__(NTH) void bn_apply_s_kernel(BnApplyS p) {
   fan_in_finish<2, kFwdFL>(fv, p.P, tot, red);
   if (tid < SW) {
     const int c = cs + tid;
-    const double mean = tot[tid] * ic;
-    double var = tot[SW + tid] * ic - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const double rstd = bn_rsqrt(var + (double)p.eps);
-    const float sc = (float)((double)ga * rstd), sh = (float)((double)be - mean * (double)ga * rstd);
-    cf[0][tid] = sc;
-    cf[1][tid] = sh;
+    const BnFwdCoef k = bn_fwd_coef(tot[tid], tot[SW + tid], ic, p.eps, ga, be);
+    cf[0][tid] = k.scale;
+    cf[1][tid] = k.shift;
     if (g == 0) {                                       // one workgroup per slice leaves what the backward pass / the caller reads
-      p.scale[c] = sc; p.shift[c] = sh; p.mean[c] = (float)mean; p.rstd[c] = (float)rstd;
-      if (p.rm) {
-        const double unb = p.count > 1.0 ? var * p.count / (p.count - 1.0) : var;
-        p.rm[c] = (float)((1.0 - p.momentum) * (double)rm0 + p.momentum * mean);
-        p.rv[c] = (float)((1.0 - p.momentum) * (double)rv0 + p.momentum * unb);
-      }
+      p.scale[c] = k.scale; p.shift[c] = k.shift; p.mean[c] = (float)k.mean; p.rstd[c] = (float)k.rstd;
+      if (p.rm) bn_running_update(k, p.count, p.momentum, rm0, rv0, &p.rm[c], &p.rv[c]);
     }
   }
   __syncthreads();
@@ -256,7 +249,7 @@ __global__ __launch_bounds__(NTH) void bn_apply2_s_kernel(BnApply2S p) {
   float4 fv[FL];
   fan_in_issue<3, FL>(p.part, p.P, p.C, 3, cs, fv);
   uint4 a1[NP], a2[NP];
-  const double ic = 1.0 / p.count;                      // (ew.h: bn_rsqrt) the count's reciprocal and the identity path's variance: formed under the loads
+  const double ic = 1.0 / p.count;                      // (bn_math.h: bn_rsqrt) the count's reciprocal and the identity path's variance: formed under the loads
   double vx = 1.0 / ((double)xr * (double)xr) - (double)p.eps;
   if (vx < 0.0) vx = 0.0;
   asm volatile("" ::"v"(ic), "v"(vx));
@@ -268,7 +261,7 @@ __global__ __launch_bounds__(NTH) void bn_apply2_s_kernel(BnApply2S p) {
     a2[u] = ld16(p.x2 + off);
   }
   fan_in_finish<3, FL>(fv, p.P, tot, red);
-  if (tid < SW) {
+  if (tid < SW) {                                         // typed out, not bn_math.h's: the running variances below round differently (momentum * var * k)
     const int c = cs + tid;
     const double mean = tot[tid] * ic;
     double var = tot[2 * SW + tid] * ic - mean * mean;
@@ -362,18 +355,7 @@ __global__ __launch_bounds__(NTH) void bn_bwd_reduce_s_kernel(BnBwdS p) {
     unpack8(vd, dy);
     unpack8(vx, x);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float dz = dy[j];
-      if (ALPHA) {
-        const float z = x[j] * G[j] + H[j];
-        if (z <= 0.f) {
-          acc[2][j] += dy[j] * z;
-          dz = dy[j] * al[j];
-        }
-      }
-      acc[0][j] += dz;
-      acc[1][j] += dz * (x[j] - mean[j]);
-    }
+    for (int j = 0; j < 8; ++j) bn_bwd_sums<ALPHA>(dy[j], x[j], mean[j], G[j], H[j], al[j], acc[0][j], acc[1][j], acc[2][j]);
   };
   uint4 ad[U], ax[U];
   issue(m0, ad, ax);
@@ -453,7 +435,7 @@ __global__ __launch_bounds__(NTH) void bn_bwd_apply_s_kernel(BnBwdS p) {
 #pragma unroll
   for (int u = 0; u < NPRE; ++u) pre[u] = fetch(m0 + u * PXP + pl);
 
-  const double ic = 1.0 / p.count;                      // (ew.h: bn_rsqrt; formed under the loads)
+  const double ic = 1.0 / p.count;                      // (bn_math.h: bn_rsqrt; formed under the loads)
   asm volatile("" ::"v"(ic));
   fan_in_finish<NV, FL>(fv, p.P, tot, red);
   if (tid < SW) {
@@ -464,11 +446,10 @@ __global__ __launch_bounds__(NTH) void bn_bwd_apply_s_kernel(BnBwdS p) {
       if (p.dbeta) p.dbeta[c] = (float)t1;
       if (ALPHA && p.dalpha) p.dalpha[c] = (float)tot[(NV - 1) * SW + tid];
     }
-    const double ga = (double)ga_, r = (double)r_, mu = (double)mu_;
-    const double a = (double)(float)(ga * r), cb = t1 * ic, cq = t2 * ic;
-    cf[0][tid] = (float)a;
-    cf[1][tid] = (float)(-a * cq * r);
-    cf[2][tid] = (float)(a * (cq * r * mu - cb));
+    const BnBwdCoef k = bn_bwd_coef(t1, t2, ic, ga_, r_, mu_);
+    cf[0][tid] = k.a;
+    cf[1][tid] = k.A;
+    cf[2][tid] = k.B;
   }
   __syncthreads();
   float ca[8], cA[8], cB[8];
@@ -486,14 +467,7 @@ __global__ __launch_bounds__(NTH) void bn_bwd_apply_s_kernel(BnBwdS p) {
     unpack8(v.d, dy);
     unpack8(v.x, x);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float dz = dy[j];
-      if (ALPHA) {
-        const float z = x[j] * G[j] + H[j];
-        if (z <= 0.f) dz = dy[j] * al[j];
-      }
-      o[j] = ca[j] * dz + (cA[j] * x[j] + cB[j]);
-    }
+    for (int j = 0; j < 8; ++j) o[j] = bn_bwd_dx<ALPHA>(dy[j], x[j], G[j], H[j], al[j], ca[j], cA[j], cB[j]);
     if (ADD) {
       float a[8];
       unpack8(v.a, a);
@@ -507,10 +481,7 @@ __global__ __launch_bounds__(NTH) void bn_bwd_apply_s_kernel(BnBwdS p) {
       unpack8(ov, dn);
       unpack8(v.n, xn);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        nacc[0][j] += dn[j];
-        nacc[1][j] += dn[j] * (xn[j] - nmean[j]);
-      }
+      for (int j = 0; j < 8; ++j) bn_bwd_sums(dn[j], xn[j], nmean[j], nacc[0][j], nacc[1][j]);
     }
   };
   int base = m0 + NPRE * PXP;

@@ -1,28 +1,16 @@
 // HBM-bound elementwise / column-reduction kernels: train-mode BatchNorm (stats finalize, apply,
 // backward), PReLU, residual add, layout conversions, split-K slab reduction, stem conv.
 // All activations are NHWC bf16 viewed as [M = N*H*W][C]; per-channel parameters are fp32.
+// Sources: bn_rowslab.hip (row-slab BatchNorm / PReLU passes and their finalizes), bn_sliced.hip (channel-sliced passes), stem.hip, ew.hip (the rest);
+// the BatchNorm algebra every path shares is bn_math.h.
 #pragma once
 #include "common.h"
 
-// 1 / sqrt(v) in fp64 (v > 0): the hardware estimate + two Newton steps.  `1.0 / sqrt(v)` is a square-root and a divide sequence — ~70 dependent
-// fp64 operations — on the critical path of EVERY BatchNorm pass (each workgroup derives its coefficients itself, bn_sliced.hip), and so were the
-// divisions by the pixel count: the passes multiply by its reciprocal, formed while their loads are in flight.  Every path (sliced passes, finalize
-// kernels) uses the same expressions, so fused and unfused passes still agree bit for bit.
-__device__ __forceinline__ double bn_rsqrt(double v) {
-  double y = __builtin_amdgcn_rsq(v);
-  y = y * (1.5 - 0.5 * v * y * y);
-  y = y * (1.5 - 0.5 * v * y * y);
-  return y;
-}
-
-// ---- forward BN -------------------------------------------------------------------------------------
-// partials: [P][2][C] (sum, sumsq).  tmp must hold 64*2*C floats when P > 1024 (two-stage reduce).
+// ---- forward BN (bn_rowslab.hip) ----------------------------------------------------------------------
+// partials: [P][2][C] (sum, sumsq), C % 8 == 0.  tmp must hold 64*2*C floats when P > 1024 (two-stage reduce).
 int ew_bn_finalize(const float* partials, int P, int C, double count, const float* gamma, const float* beta,
                    float* running_mean, float* running_var, float momentum, float eps,
                    float* scale, float* shift, float* save_mean, float* save_rstd, float* tmp, hipStream_t st);
-// eval mode: scale/shift from running stats
-int ew_bn_eval_coeffs(int C, const float* gamma, const float* beta, const float* running_mean,
-                      const float* running_var, float eps, float* scale, float* shift, hipStream_t st);
 
 struct BnApply {
   const bf16_t* x1; const float* sc1; const float* sh1; const float* alpha;   // y = prelu?(x1*sc1+sh1)
@@ -129,7 +117,6 @@ int ew_bn1d_bwd(const float* dy, const float* x, float* dx, int B, int C, const 
 int ew_reduce_slabs(float* dst, const float* slabs, int nsplit, size_t n, const float* bias, int bias_n,
                     hipStream_t st);
 int ew_reduce_slabs2(float* dst0, const float* slabs0, float* dst1, const float* slabs1, int nsplit, size_t n, hipStream_t st);
-int ew_reduce_slabs_bf16(bf16_t* dst, const float* slabs, int nsplit, size_t n, hipStream_t st);
 
 // ---- conversions -----------------------------------------------------------------------------------------------
 int ew_cast_f32_bf16(const float* src, bf16_t* dst, size_t n, hipStream_t st);
@@ -137,10 +124,8 @@ int ew_cast_f32_bf16(const float* src, bf16_t* dst, size_t n, hipStream_t st);
 int ew_weight_dgrad_shadow(const float* w, bf16_t* dst, int Cout, int R, int S, int Cin, hipStream_t st);
 // fp32 [B][C][HW] -> bf16 [B][HW][C]
 int ew_nchw_f32_to_nhwc_bf16(const float* src, bf16_t* dst, int B, int C, int HW, hipStream_t st);
-// bf16 [R][Ccols] -> bf16 [Ccols][R]
-int ew_transpose_bf16(const bf16_t* src, bf16_t* dst, int R, int Ccols, hipStream_t st);
 
-// ---- stem: conv3x3(3->64, s1, p1) on fp32 NCHW input ----------------------------------------------------------
+// ---- stem: conv3x3(3->64, s1, p1) on fp32 NCHW input (stem.hip) -------------------------------------------------
 // w: KRSC fp32 [64][3][3][3]; y: NHWC bf16 [B][H][W][64]; stats partials [stem_stat_rows][2][64]
 int ew_stem_stat_rows(int B, int H, int W);
 int ew_stem_fwd(const float* x, const float* w, bf16_t* y, float* stats, int B, int H, int W, hipStream_t st);

@@ -687,7 +687,7 @@ static const int g_wgrad_depth = kWgradDepth;   // generations of weight-gradien
 int g_fuse_bnred_next = 1;   // option "fuse_bnred_next": a BN-backward apply pass also reduces its output for the BN that consumes it
 // BatchNorm (+PReLU) backward: dx = a dz + A x + B (+ addend).  `have`: partial rows that already exist (left by the pass that produced
 // dy); else a reduce pass runs first.  With next_bn, dx is also reduced as the dy of that BatchNorm's backward -> *next_rows.
-// Channel-sliced passes without a finalize launch where the shape allows (bn_sliced.hip), else reduce / finalize / apply of ew.hip.
+// Channel-sliced passes without a finalize launch where the shape allows (bn_sliced.hip), else reduce / finalize / apply of bn_rowslab.hip.
 static int bn_bwd(const Ctx& c, const BnD& b, const float* alpha, const bf16_t* dy, const bf16_t* x, int M, const bf16_t* add,
                   const bf16_t* add_up, int H, bf16_t* dx, long long alpha_off, Rows have = Rows{nullptr, 0}, const BnD* next_bn = nullptr,
                   const bf16_t* next_x = nullptr, Rows* next_rows = nullptr, const float* next_alpha = nullptr, bool coef_only = false) {

@@ -128,6 +128,7 @@ __global__ __launch_bounds__(256) void f32_colsum_kernel(ColOp o, int M, int C, 
   }
 }
 // BatchNorm forward finalize: mean / rstd / scale / shift (+ running statistics in training)
+// (its own plain expressions, not bn_math.h's: this is the fp32 validation path the tests hold the product kernels against)
 __global__ void f32_bn_finalize_kernel(const double* __restrict__ part, int S, int C, double count, const float* gamma, const float* beta, float* rm,
                                        float* rv, int training, float* save /* [4][C]: scale, shift, mean, rstd */) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;

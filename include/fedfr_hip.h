@@ -237,6 +237,8 @@ int fedfr_stem_wgrad_fused(const float* x, const uint16_t* dy_act, const uint16_
  * BatchNorm2d (train) + PReLU + residual — replace nn.BatchNorm2d / nn.PReLU / `out += identity`
  * (iresnet.py:37-56).  Tensors are [M][C] views (16-bit storage type) of NHWC activations.
  * ------------------------------------------------------------------------------------------------ */
+/* partials: P rows [2][C] of (sum, sumsq); C % 8 == 0, as for every [M][C] entry point (any other C: FEDFR_ERR_ARG with a message);
+ * tmp: 64 * 2 * C floats, needed when P > 1024 */
 int fedfr_bn_finalize(const float* partials, int P, int C, double count, const float* gamma, const float* beta,
                       float* running_mean, float* running_var, float momentum, float eps, float* scale, float* shift,
                       float* save_mean, float* save_rstd, float* tmp, void* stream);

@@ -1,5 +1,5 @@
 """Inputs and fp64 references for the direct tests of the end of the backward pass: the stem conv (forward, weight gradient plain and
-with the BatchNorm + PReLU backward fused in) and the row-slab BatchNorm backward chain (csrc/ew.hip), in the manner of head_cases.py.
+with the BatchNorm + PReLU backward fused in) and the row-slab BatchNorm backward chain (csrc/stem.hip, csrc/bn_rowslab.hip), in the manner of head_cases.py.
 
 Every reference is a plain torch formula evaluated at ``dtype``.  The float64 evaluation is what the kernels are held to
 (tests/test_stem_chain_gpu.py); the float32 evaluation is the same formula in the kernels' order of operations (the 16-bit roundings the
@@ -76,13 +76,13 @@ def exceeds(val, q):
     return err_over_tol(val, q) > 1.0
 
 
-# ------------------------------------------------------------------------------------------------ geometry (formulas of csrc/ew.hip)
+# ------------------------------------------------------------------------------------------------ geometry (formulas of csrc/bn_rowslab.hip and csrc/stem.hip)
 def rows_per_pass(C):
     return EW_THREADS // (C >> 3)
 
 
 def slab_rows(M, C, max_blocks):
-    """ew.hip slab_rows: max(8 rpp, ceil(M / max_blocks)) rounded up to a multiple of rpp = 256 / (C / 8)"""
+    """bn_rowslab.hip slab_rows: max(8 rpp, ceil(M / max_blocks)) rounded up to a multiple of rpp = 256 / (C / 8)"""
     rpp = rows_per_pass(C)
     rows = max(rpp * 8, -(-M // max_blocks))
     return -(-rows // rpp) * rpp
@@ -97,7 +97,7 @@ def colsum_chain(slab, C):
 
 
 def stem_px_per_block(M, sw_px=128):
-    """ew.hip stem_px_per_block: ceil(M / 1024) rounded up to whole stages of SW_PX pixels"""
+    """stem.hip stem_px_per_block: ceil(M / 1024) rounded up to whole stages of SW_PX pixels"""
     return max(sw_px, -(-(-(-M // 1024)) // sw_px) * sw_px)
 
 

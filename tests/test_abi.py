@@ -62,6 +62,12 @@ def test_plan_layout_matches_reference_inventory(built_lib):
     assert not lib.fedfr_net_create((C.c_int * 4)(2, 2, 2, 2), 0, 112, 512)
     assert b"net_create" in lib.fedfr_last_error_string()
     assert lib.fedfr_set_option(b"no_such_option", 1) != 0
+    # fedfr_bn_finalize serves C % 8 == 0 only, like every other [M][C] entry point: C = 12 is an argument error (checked before any HIP call)
+    buf = (C.c_float * 64)()
+    err_arg = int(re.search(r"#define FEDFR_ERR_ARG \((-?\d+)\)", open(HEADER).read()).group(1))
+    assert lib.fedfr_bn_finalize(buf, 2, 12, 8.0, buf, buf, None, None, 0.1, 1e-5, buf, buf, buf, buf, None, None) == err_arg
+    msg = lib.fedfr_last_error_string()
+    assert b"bn_finalize" in msg and b"12" in msg, msg
 
 
 def test_documented_options_exist_and_unknown_ones_are_errors(built_lib):

@@ -536,6 +536,51 @@ def test_bn_apply_sliced(M, C, prelu, second, rows_in):
                 shift.data_ptr(), mean.data_ptr(), rstd.data_ptr(), xd.data_ptr(), None, None, y.data_ptr(), M, C, None, _C.stream())
 
 
+@pytest.mark.parametrize("M,C,rows_in", [(3001, 64, 7), (1000, 256, 1), (784, 256, 8)])
+def test_sliced_and_finalize_coefficients_agree_bitwise(M, C, rows_in):
+    """fedfr_bn_finalize and fedfr_bn_apply_sliced derive scale / shift / mean / rstd and the running statistics from the same partial rows with
+    the same expressions (bn_math.h): bit-identical.  x holds multiples of 1/8 in [-2, 2], so every partial sum is exact in fp32 (|sum| < 2^14 on a
+    2^-6 grid) and every fp64 summation order of the rows gives the same total: a difference can only come from the coefficient expressions."""
+    assert _C.lib().fedfr_bn_sliced_ok(M, C, rows_in, 0) == 1
+    g = torch.Generator().manual_seed(11)
+    xf = torch.randint(-16, 17, (M, C), generator=g).float() / 8
+    x = bf(xf)
+    assert torch.equal(x.float(), xf)
+    gamma, beta = rnd((C,), 2) * 0.2 + 1, rnd((C,), 3) * 0.1
+    rm, rv = rnd((C,), 4) * 0.1, rnd((C,), 5) * 0.1 + 1
+    bounds = np.linspace(0, M, rows_in + 1).astype(int)
+    part = torch.stack([torch.stack([xf[a:b].sum(0), (xf[a:b] ** 2).sum(0)]) for a, b in zip(bounds[:-1], bounds[1:])])
+    # exact by construction: the rows equal their fp64 sums, and their totals do not depend on the order
+    part64 = torch.stack([torch.stack([xf[a:b].double().sum(0), (xf[a:b].double() ** 2).sum(0)]) for a, b in zip(bounds[:-1], bounds[1:])])
+    assert torch.equal(part.double(), part64)
+    fwd, rev = torch.zeros(2, C, dtype=torch.float64), torch.zeros(2, C, dtype=torch.float64)
+    for r in range(rows_in):
+        fwd += part[r].double()
+        rev += part[rows_in - 1 - r].double()
+    assert torch.equal(fwd, rev) and torch.equal(fwd, torch.stack([xf.double().sum(0), (xf.double() ** 2).sum(0)]))
+    assert float(fwd.abs().max()) < 2 ** 14
+    d = dev()
+    partd, xd, g_, b_ = part.to(d), x.to(d), gamma.to(d), beta.to(d)
+    out = []
+    for sliced in (False, True):
+        rm_, rv_ = rm.to(d), rv.to(d)
+        scale, shift, mean, rstd = (torch.full((C,), float("nan"), device=d) for _ in range(4))
+        if sliced:
+            y = torch.empty_like(xd)
+            _C.call("fedfr_bn_apply_sliced", partd.data_ptr(), rows_in, float(M), g_.data_ptr(), b_.data_ptr(), rm_.data_ptr(), rv_.data_ptr(), 0.1,
+                    1e-5, scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), rstd.data_ptr(), xd.data_ptr(), None, None, y.data_ptr(), M, C, None,
+                    _C.stream())
+        else:
+            tmp = torch.empty(64 * 2 * C, device=d)
+            _C.call("fedfr_bn_finalize", partd.data_ptr(), rows_in, C, float(M), g_.data_ptr(), b_.data_ptr(), rm_.data_ptr(), rv_.data_ptr(), 0.1,
+                    1e-5, scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), rstd.data_ptr(), tmp.data_ptr(), _C.stream())
+        torch.cuda.synchronize()
+        out.append([t.cpu() for t in (scale, shift, mean, rstd, rm_, rv_)])
+    for name, a, b in zip(("scale", "shift", "save_mean", "save_rstd", "running_mean", "running_var"), out[0], out[1]):
+        assert not torch.isnan(a).any(), name
+        assert torch.equal(a, b), "%s: finalize and sliced differ by up to %g" % (name, float((a - b).abs().max()))
+
+
 @pytest.mark.parametrize("M,C,prelu,with_add,with_next", [(25088, 256, True, False, False), (25088, 256, False, True, True),
                                                           (6272, 512, False, False, True), (3001, 64, True, True, True),
                                                           (100352, 128, False, True, False), (784, 256, False, True, True),

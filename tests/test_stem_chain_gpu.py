@@ -7,7 +7,7 @@ tolerances reachable by a correct fp32 kernel and tight enough to see one row, o
 from the library's own row / size queries: a retune of the slab sizes or the stage size fails here instead of skipping a path.
 
 The fused stem weight gradient is held to equal bn_bwd_apply + the plain form BIT FOR BIT (test_stem_wgrad_plain_and_fused asserts
-torch.equal at every shape), as ew.h / ew.hip state: both kernels write the same expression, a dz + (A x0 + B), on the same operands, the
+torch.equal at every shape), as ew.h / stem.hip state: both kernels call the same expression (bn_math.h: bn_bwd_dx), a dz + (A x0 + B), on the same operands, the
 library is built with -ffp-contract=on (contraction within a statement only), and both round the result to the same 16 bits."""
 
 import pytest
@@ -111,7 +111,7 @@ def test_stem_wgrad_plain_and_fused(B, HW):
     (2^-17 + L 2^-24) sum |dz col| of the float64 gradient PER WEIGHT ELEMENT, and the two equal bit for bit."""
     c = K.StemWgradCase(B, HW, S16())
     M = c.M
-    stages = c.ppb // 128                              # SW_PX = 128 pixels per stage, ppb from ew.hip's stem_px_per_block (the workspace query confirms nblk)
+    stages = c.ppb // 128                              # SW_PX = 128 pixels per stage, ppb from stem.hip's stem_px_per_block (the workspace query confirms nblk)
     if (B, HW) == (11, 112):
         assert stages == 2 and M % c.ppb == 0
     elif (B, HW) == (53, 50):

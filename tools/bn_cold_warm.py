@@ -48,7 +48,7 @@ def main():
         g, b, rm, rv = torch.ones(C, device=d), torch.zeros(C, device=d), torch.zeros(C, device=d), torch.ones(C, device=d)
         sc, sh, mu, rs = (torch.rand(C, device=d) + 0.5 for _ in range(4))
         al = torch.full((C,), 0.25, device=d)
-        # row-slab pass (ew.hip): y = prelu(x * sc + sh)
+        # row-slab pass (bn_rowslab.hip): y = prelu(x * sc + sh)
         def slab(p):
             _C.call("fedfr_bn_apply", p[0].data_ptr(), sc.data_ptr(), sh.data_ptr(), al.data_ptr(), None, None, None, p[1].data_ptr(), M, C, 0, None, st)
         rows = [("row-slab bn_apply + PReLU", slab)]
