@@ -145,6 +145,10 @@ SIGNATURES = {
     "fedfr_robust_pairdist_workspace_bytes": (sz, [i32, sz]),
     "fedfr_robust_pairdist": (i32, [vp, i32, sz, vp, vp, sz, vp]),
     "fedfr_robust_krum_select": (i32, [vp, i32, i32, i32, vp, vp, vp]),
+    "fedfr_delta_code_bytes": (sz, [i32, sz]),
+    "fedfr_delta_scale_bytes": (sz, [sz]),
+    "fedfr_delta_quantize": (i32, [vp, vp, vp, vp, vp, i32, sz, vp, vp]),
+    "fedfr_delta_aggregate": (i32, [vp, vp, vp, vp, vp, i32, i32, sz, i32, vp]),
     "fedfr_pfc_rand": (i32, [vp, i32, u64, u64, vp]),
     "fedfr_pfc_localize": (i32, [vp, i32, i64, i32, vp, vp]),
     "fedfr_pfc_topk": (i32, [vp, i32, i32, vp, vp, vp]),

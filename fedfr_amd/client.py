@@ -1100,6 +1100,17 @@ class Client(object):
     def get_model(self):
         return self.backbone_state_dict
 
+    @_C.on_device(lambda self: self.device)
+    def get_compressed_update(self, global_state, bits, error_feedback=True):
+        """The trained state as a compressed upload against ``global_state`` (the state the round started from): ``compress.CompressedDelta``
+        of ``bits`` = 8 or 4.  The client's ``DeltaCompressor`` — and with it the residual e_i of the error feedback — is created on first
+        use and again whenever ``bits`` or ``error_feedback`` differs from the one it holds, and lives across rounds."""
+        from .compress import DeltaCompressor
+        comp = getattr(self, "compressor", None)
+        if comp is None or comp.bits != bits or comp.error_feedback != bool(error_feedback):
+            comp = self.compressor = DeltaCompressor(bits, error_feedback)
+        return comp.compress(global_state, self.backbone_state_dict)
+
     def get_global_fc(self):
         return self.fc_module.get_pretrain_fc()
 

@@ -10,6 +10,7 @@
 #include "net.h"
 #include "optim.h"
 #include "robust.h"
+#include "compress.h"
 
 static thread_local char g_err[512] = "";
 extern int g_tn_use_tr;
@@ -811,6 +812,16 @@ int fedfr_robust_pairdist(const float* const* xs, int k, size_t n, double* dist,
 }
 int fedfr_robust_krum_select(const double* dist, int k, int f, int m, double* score, int* selected, void* stream) {
   return robust_krum_select(dist, k, f, m, score, selected, ST(stream));
+}
+size_t fedfr_delta_code_bytes(int bits, size_t n) { return delta_code_bytes(bits, n); }
+size_t fedfr_delta_scale_bytes(size_t n) { return delta_scale_bytes(n); }
+int fedfr_delta_quantize(const float* x, const float* xi, float* resid, void* codes, unsigned char* scales, int bits, size_t n, int* nonfinite_blocks,
+                         void* stream) {
+  return delta_quantize(x, xi, resid, codes, scales, bits, n, nonfinite_blocks, ST(stream));
+}
+int fedfr_delta_aggregate(float* dst, const float* base, const void* const* codes, const unsigned char* const* scales, const float* ws, int k, int bits,
+                          size_t n, int accumulate, void* stream) {
+  return delta_aggregate(dst, base, codes, scales, ws, k, bits, n, accumulate, ST(stream));
 }
 int fedfr_pfc_rand(float* perm, int n, unsigned long long seed, unsigned long long step, void* stream) {
   return optim_pfc_rand(perm, n, seed, step, ST(stream));

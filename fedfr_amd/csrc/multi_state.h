@@ -1,6 +1,8 @@
 // The streaming skeleton of the kernels that read up to K flat fp32 states once each and write one result (optim.hip: fedavg_multi,
 // fedopt_sqnorm, fedopt_multi; robust.hip: robust_trimmed_mean, robust_pairdist): launch rule, pointer-array argument and its host check,
 // read-once loads, the vector-then-tail element loop, instantiation dispatch, and the fixed-order fp64 reduction lanes -> waves -> blocks.
+// compress.hip (delta_quantize, delta_aggregate: block-scaled integer codes of x_i - x) goes on the same skeleton with 8 elements per thread:
+// multi_state_grid_per<8> and BytePtrs below are its variants of the launch rule and of the pointer array.
 #pragma once
 #include "common.h"
 #include <type_traits>
@@ -10,6 +12,13 @@
 constexpr int MULTI_STATE_BLOCK = 256;
 static inline int multi_state_grid(size_t n) {
   const size_t blocks = (n / 4 + 1 + MULTI_STATE_BLOCK - 1) / MULTI_STATE_BLOCK;
+  return (int)(blocks > 2048 ? 2048 : blocks);
+}
+// the variant of the rule for a kernel whose threads take PER elements each instead of one float4 (compress.hip: 8): one block per 256 units
+// of PER elements (+ 1), 2048 at the most
+template <int PER>
+static inline int multi_state_grid_per(size_t n) {
+  const size_t blocks = (n / PER + 1 + MULTI_STATE_BLOCK - 1) / MULTI_STATE_BLOCK;
   return (int)(blocks > 2048 ? 2048 : blocks);
 }
 
@@ -24,6 +33,21 @@ static inline int state_ptrs_fill(StatePtrs<CAP>& p, const float* const* srcs, i
   for (int i = 0; i < k; ++i) {
     FEDFR_REQUIRE(srcs[i] != nullptr, "%s: %s %d is null", who, what, i);
     p.src[i] = srcs[i];
+    al |= (uintptr_t)srcs[i];
+  }
+  return FEDFR_OK;
+}
+
+// the same for up to CAP byte buffers (compress.hip: the codes and the scale bytes of compressed uploads)
+template <int CAP>
+struct BytePtrs {
+  const unsigned char* src[CAP];
+};
+template <int CAP>
+static inline int byte_ptrs_fill(BytePtrs<CAP>& p, const void* const* srcs, int k, const char* who, const char* what, uintptr_t& al) {
+  for (int i = 0; i < k; ++i) {
+    FEDFR_REQUIRE(srcs[i] != nullptr, "%s: %s %d is null", who, what, i);
+    p.src[i] = static_cast<const unsigned char*>(srcs[i]);
     al |= (uintptr_t)srcs[i];
   }
   return FEDFR_OK;

@@ -2,8 +2,9 @@
 averaging of client models, as HIP kernels over flat buffers (single process) or one RCCL all-reduce over
 xGMI when every client is its own rank (one client = one MI355X); the spread-out step on the clients' class centres
 (reference server.py:48-63, :340-371) on one fused HIP kernel; and the round's 1:1 verification of the global model with its
-checkpoints (reference server.py:135-148).  Build extensions beyond the reference's FedAvg: the server optimisers (``FedOpt``) and the
-robust rules (``FedRobust``: coordinate-wise trimmed mean / median, Krum / Multi-Krum)."""
+checkpoints (reference server.py:135-148).  Build extensions beyond the reference's FedAvg: the server optimisers (``FedOpt``), the
+robust rules (``FedRobust``: coordinate-wise trimmed mean / median, Krum / Multi-Krum) and compressed client uploads (``FedCompressed``:
+8 / 4-bit block-scaled deltas with error feedback, see compress.py)."""
 from __future__ import annotations
 
 import copy
@@ -386,6 +387,62 @@ def FedRobust(models: List[dict], weights: Sequence[float], agg: RobustAggregato
     return FlatStateDict.from_flat((P, *_average_stats(models, ws, agg.trimmed_mean)), models[0].table, models[0].layers)
 
 
+# ---- compressed uploads: csrc/compress.hip delta_quantize_kernel (client side, compress.py) / delta_aggregate_kernel
+class _StatsOnly:
+    """what ``_average_stats`` reads of a client state, for an upload that carries no fp32 parameters"""
+
+    def __init__(self, stats, counters):
+        self.flat = (None, stats, counters)
+
+
+def FedCompressed(global_state, updates, weights: Sequence[float], server_opt=None):
+    """One round from compressed uploads (``compress.CompressedDelta``, all of one width): the PARAMETERS of the new global state are
+    x + Σ_i (n_i/Σn)·dq_i with x = ``global_state``'s parameters and dq_i the dequantised upload of client i (fedfr_delta_aggregate: ≤ 8
+    uploads per pass, every code and scale byte read once; more clients chain passes with ``accumulate``, and x is added by the last pass
+    only, so the sum has the roundings of one ascending loop).  With ``server_opt`` (a ``ServerOptimizer``) the same sum WITHOUT x is the
+    pseudo-gradient Δ and goes through ``server_opt.apply_delta``; ``clip_norm`` > 0 raises ``ValueError`` (the clip needs per-client norms
+    of the dequantised deltas: not provided).  BN running statistics and ``num_batches_tracked`` arrive uncompressed and are averaged
+    exactly as ``FedPavg`` averages them.  A block a client sent as non-finite is NaN in the result, as it would be with fp32 uploads.
+    Only a GPU ``FlatStateDict`` is accepted as ``global_state``."""
+    from .compress import CompressedDelta
+    if not isinstance(global_state, FlatStateDict) or global_state.flat is None:
+        raise RuntimeError("fedfr_amd.FedCompressed: the global state must be a FlatStateDict (client.flat_state_dict)")
+    if not updates or not all(isinstance(u, CompressedDelta) for u in updates):
+        raise RuntimeError("fedfr_amd.FedCompressed: the client updates must be CompressedDeltas (Client.get_compressed_update)")
+    if len(weights) != len(updates):
+        raise RuntimeError("fedfr_amd.FedCompressed: %d weights for %d client updates" % (len(weights), len(updates)))
+    if isinstance(server_opt, RobustAggregator):
+        raise ValueError("FedCompressed: a robust rule (%s) needs whole client states, not compressed uploads" % server_opt.kind)
+    if server_opt is not None and server_opt.clip_norm > 0:
+        raise ValueError("FedCompressed: clip_norm > 0 needs per-client norms of the dequantised deltas, which compressed uploads do not "
+                         "provide; use FedOpt on uncompressed states")
+    tot = sum(weights)
+    ws = [w / tot for w in weights]
+    x = global_state.flat[0]
+    _check_states(x, [], "FedCompressed")
+    n, bits = x.numel(), updates[0].bits
+    lib = _C.lib()
+    for u in updates:
+        if u.bits != bits or u.n != n:
+            raise RuntimeError("fedfr_amd.FedCompressed: an update of %d bits and %d parameters among updates of %d bits for %d parameters"
+                               % (u.bits, u.n, bits, n))
+        for t, need, what in ((u.codes, lib.fedfr_delta_code_bytes(bits, n), "codes"), (u.scales, lib.fedfr_delta_scale_bytes(n), "scales")):
+            if t.dtype != torch.uint8 or t.numel() != need or t.device != x.device or not t.is_contiguous():
+                raise RuntimeError("fedfr_amd.FedCompressed: %s must be a contiguous uint8 tensor of %d bytes on %s" % (what, need, x.device))
+    P = torch.empty_like(x)
+    for c0 in range(0, len(updates), 8):
+        grp = updates[c0:c0 + 8]
+        last = c0 + 8 >= len(updates)
+        wv = (_C.f32 * len(grp))(*[float(np.float32(w)) for w in ws[c0:c0 + 8]])
+        if n:
+            _C.call("fedfr_delta_aggregate", P.data_ptr(), x.data_ptr() if last and server_opt is None else None, _C.ptr_array([u.codes for u in grp]),
+                    _C.ptr_array([u.scales for u in grp]), wv, len(grp), bits, n, 1 if c0 > 0 else 0, _C.stream())
+    if server_opt is not None:
+        server_opt.apply_delta(P, x, P)
+    stats = _average_stats([_StatsOnly(u.stats, u.counters) for u in updates], ws)
+    return FlatStateDict.from_flat((P, *stats), global_state.table, global_state.layers)
+
+
 def FedAvg_on_FC(pretrain_fc, models, weights, p):
     """reference server.py:36-46."""
     tot = sum(weights)
@@ -589,6 +646,16 @@ class Server(object):
                 self.robust_agg = RobustAggregator(aggr_alg, trim_ratio=getattr(a, "trim_ratio", 0.1), num_byzantine=getattr(a, "num_byzantine", 1),
                                                    multi_m=getattr(a, "multi_krum_m", None))
             self.robust_agg.validate(len(self.current_client_list))
+        compress_bits = getattr(self.args, "compress_bits", 0) or 0          # compressed uploads (a build extension): absent or 0 = off
+        if compress_bits:                                                    # what cannot be served: also before anybody trains
+            from .compress import check_bits
+            check_bits(compress_bits, "Server.train")
+            if aggr_alg in ROBUST_ALG_KINDS:
+                raise ValueError("Server.train: compress_bits=%d cannot be combined with aggr_alg=%r: a robust rule needs whole client states"
+                                 % (compress_bits, aggr_alg))
+            if float(getattr(self.args, "clip_norm", 0.0) or 0.0) > 0:
+                raise ValueError("Server.train: compress_bits=%d cannot be combined with clip_norm=%r: the clip needs per-client norms of the "
+                                 "dequantised deltas, which are not provided" % (compress_bits, self.args.clip_norm))
         models, models_fc, losses_, data_sizes = [], [], [], []
         public = bool(getattr(self.args, "add_pretrained_data", False))
         return_all = bool(getattr(self.args, "return_all", False))
@@ -654,9 +721,15 @@ class Server(object):
                     t.join()
                 if errs:
                     raise errs[0]
+        if compress_bits:
+            global_state = flat_state_dict(self.federated_model)              # what the round started from: the clients trained on copies
+            feedback = bool(getattr(self.args, "error_feedback", True))
         for i in order:
             losses_.append(self.clients[i].get_train_loss())
-            models.append(self.clients[i].get_model())
+            if compress_bits:                                                 # "client sends Q(x_i - x + e_i)" and keeps e_i
+                models.append(self.clients[i].get_compressed_update(global_state, compress_bits, feedback))
+            else:
+                models.append(self.clients[i].get_model())
             if return_all:
                 models_fc.append(self.clients[i].get_global_fc().to(self.device))
                 self.clients[i].fc_module.remove_pretrain()
@@ -669,15 +742,25 @@ class Server(object):
             self.pretrain_fc = FedAvg_on_FC(self.pretrained_fc, models_fc, data_sizes, p=1.0)
             if getattr(self.args, "feedback_public_fc", False):
                 self.pretrained_fc = self.pretrain_fc
-        if aggr_alg in ("FedAvg", "FedProx"):
+        if aggr_alg in AGGR_ALG_KINDS and getattr(self, "server_opt", None) is None:
+            # server optimiser (a build extension: the reference's flag runs FedAvg only): one optimiser per server, moments kept across rounds
+            a = self.args
+            self.server_opt = ServerOptimizer(aggr_alg, lr=getattr(a, "server_lr", 1.0), beta1=getattr(a, "server_momentum", 0.9),
+                                              beta2=getattr(a, "server_beta2", 0.99), tau=getattr(a, "server_tau", 1e-3),
+                                              clip_norm=getattr(a, "clip_norm", 0.0))
+        if compress_bits:
+            aggr_state_dict = FedCompressed(global_state, models, data_sizes, self.server_opt if aggr_alg in AGGR_ALG_KINDS else None)
+            sent, dense = sum(u.nbytes for u in models), sum(u.dense_nbytes for u in models)
+            self.logger.info('Compressed uploads (%d bits%s): %d bytes from %d clients, %.4f of the %d bytes of fp32 states'
+                             % (compress_bits, ", error feedback" if feedback else "", sent, len(models), sent / dense, dense))
+            bad = torch.cat([u.nonfinite_blocks for u in models]).cpu().tolist()      # one small copy: the round's one read of the counters
+            for j, nb in enumerate(bad):
+                if nb > 0:
+                    self.logger.warning('Client %s sent %d non-finite blocks (NaN in the aggregate there)'
+                                        % (getattr(self.clients[order[j]], "cid", order[j]), nb))
+        elif aggr_alg in ("FedAvg", "FedProx"):
             aggr_state_dict = FedPavg(models, data_sizes)
         elif aggr_alg in AGGR_ALG_KINDS:
-            # server optimiser (a build extension: the reference's flag runs FedAvg only): one optimiser per server, moments kept across rounds
-            if getattr(self, "server_opt", None) is None:
-                a = self.args
-                self.server_opt = ServerOptimizer(aggr_alg, lr=getattr(a, "server_lr", 1.0), beta1=getattr(a, "server_momentum", 0.9),
-                                                  beta2=getattr(a, "server_beta2", 0.99), tau=getattr(a, "server_tau", 1e-3),
-                                                  clip_norm=getattr(a, "clip_norm", 0.0))
             aggr_state_dict = FedOpt(flat_state_dict(self.federated_model), models, data_sizes, self.server_opt)
         else:
             # ROBUST_ALG_KINDS (nothing else passed the check above).  Robust aggregation (a build extension): trimmed mean / median per

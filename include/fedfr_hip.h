@@ -608,6 +608,50 @@ int fedfr_robust_pairdist(const float* const* xs, int k, size_t n, double* dist,
  * score (k doubles) and selected (k int32) are DEVICE arrays.  Requires 2 f + 3 <= k <= 32 and 1 <= m <= k - f (m = 1: Krum). */
 int fedfr_robust_krum_select(const double* dist, int k, int f, int m, double* score, int* selected, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * compressed client uploads with error feedback — no reference counterpart (its clients hand over full fp32 states).  A client sends
+ * Q(x_i - x + e_i) and keeps the quantisation error e_i for the next round.  Codes of bits = 8 or 4 with ONE shared power-of-two scale
+ * per 32 elements (the OCP microscaling layout): 8.25 or 4.25 bits per parameter instead of 32.  Every scale is a power of two, so
+ * scaling and rescaling are exact and every output of both kernels can be reproduced bit for bit (tests/compress_cases.py).
+ * THE FORMAT.  qmax = 2^(bits-1) - 1 (127 or 7); block b = elements 32 b .. min(32 b + 31, n - 1) (the last block may be short).
+ *   1. value to send   v_j = (x_i[j] - x[j]) + e[j]: two fp32 operations in that order; without error feedback v_j = x_i[j] - x[j].
+ *   2. non-finite      a block with any v_j NaN or +-inf: scale byte 255 (reserved for exactly this: step 3 never produces it), all codes
+ *                      0, new residual +0 for the whole block (a diverged round must not poison the residual forever), and the block
+ *                      adds 1 to the nonfinite_blocks counter.
+ *   3. scale           otherwise amax = max |v_j| over the block, Ef = the biased exponent field of amax (0 for zero and subnormals);
+ *                      scale byte eb = clamp(Ef - (bits - 2), 0, 254), scale = 2^(eb - 127).  amax / scale is in [2^(bits-2), 2^(bits-1))
+ *                      unless eb is clamped at 0 (which only makes it smaller); Ef <= 254 gives eb <= 252.
+ *   4. code            q_j = clamp(rint(v_j * 2^(127 - eb)), -qmax, qmax), rint = round half to even.  The product is exact wherever the
+ *                      result can be non-zero; only |v_j| >= (qmax + 1/2) scale saturates.
+ *   5. layout          8 bits: byte j = q_j as int8.  4 bits: byte j holds q_2j in the low and q_2j+1 in the high nibble (two's-complement
+ *                      nibbles; a missing last element is 0).  Scale byte b belongs to block b.  ceil(n bits / 8) code bytes, ceil(n / 32)
+ *                      scale bytes.
+ *   6. dequantise      dq_j = float(q_j) * 2^(eb - 127): exact, subnormal scales included; eb = 255 gives NaN for the whole block, so the
+ *                      server sees the poison as it would with fp32 uploads.
+ *   7. residual        e'[j] = v_j - dq_j, one fp32 subtraction: dq + e' == v exactly for every finite block, |e'| < scale, and
+ *                      |e'| <= scale / 2 where the element did not saturate.
+ * ------------------------------------------------------------------------------------------------ */
+/* ceil(n bits / 8): bytes of the code buffer of n elements; 0 for bits other than 4 or 8 */
+size_t fedfr_delta_code_bytes(int bits, size_t n);
+/* ceil(n / 32): bytes of the scale buffer of n elements */
+size_t fedfr_delta_scale_bytes(size_t n);
+/* One pass over x (global parameters), xi (client parameters) and resid (e, read and updated in place to e'): each is read once, codes, scale
+ * bytes and e' are written once.  resid may be NULL: no error feedback, nothing read or written for it.  nonfinite_blocks may be NULL;
+ * otherwise a DEVICE int the caller has zeroed, to which every non-finite block adds 1 (an integer atomic: order-free).  codes holds
+ * fedfr_delta_code_bytes(bits, n), scales fedfr_delta_scale_bytes(n) bytes.  x, xi, resid, codes and scales 16-byte aligned (the scale
+ * bytes of 512 elements leave as one 16-byte store).  FEDFR_ERR_ARG, before anything is launched, for bits other than 4 or 8, a NULL x, xi,
+ * codes or scales, or a misaligned buffer; n = 0 with valid arguments is a no-op. */
+int fedfr_delta_quantize(const float* x, const float* xi, float* resid, void* codes, unsigned char* scales, int bits, size_t n,
+                         int* nonfinite_blocks, void* stream);
+/* The weighted sum of k <= 8 uploads in one pass (HOST arrays of k device pointers codes / scales and k weights ws, as fedfr_fedavg_multi):
+ *   s = accumulate ? dst[j] + ws[0] dq_0[j] : ws[0] dq_0[j];   s = s + ws[i] dq_i[j] for ascending i;   dst[j] = base ? base[j] + s : s
+ * Each product is one fp32 multiply and each sum one fp32 add, nothing contracted: the roundings of k axpy launches on the dequantised
+ * uploads.  More than 8 uploads chain calls with accumulate = 1 and pass base (the global parameters x) to the last one only.  dst may
+ * equal base.  dst, base and every code buffer 16-byte aligned.  FEDFR_ERR_ARG, before anything is launched, for bits other than 4 or 8,
+ * k outside 1..8, a NULL dst, codes, scales, ws or array entry, or a misaligned buffer; n = 0 with valid arguments is a no-op. */
+int fedfr_delta_aggregate(float* dst, const float* base, const void* const* codes, const unsigned char* const* scales, const float* ws, int k,
+                          int bits, size_t n, int accumulate, void* stream);
+
 int fedfr_pfc_rand(float* perm, int n, unsigned long long seed, unsigned long long step, void* stream);
 int fedfr_pfc_localize(long long* label, int n, long long class_start, int num_local, float* perm, void* stream);
 int fedfr_pfc_topk(const float* perm, int n, int k, long long* index, int* npos_out, void* stream);
