@@ -67,6 +67,12 @@ SIGNATURES = {
     "fedfr_weight_shadows": (i32, [vp, vp, vp, i32, i32, i32, vp]),
     "fedfr_gemm_nt": (i32, [vp, vp, vp, vp, sz, i32, i32, i32, vp]),
     "fedfr_gemm_tn": (i32, [vp, vp, vp, i32, i32, i32, vp]),
+    "fedfr_bn1d_fwd": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, f32, f32, i32, vp, vp, vp]),
+    "fedfr_bn1d_bwd": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]),
+    "fedfr_reduce_slabs": (i32, [vp, vp, i32, sz, vp, i32, vp, vp, vp]),
+    "fedfr_dropout_fwd": (i32, [vp, vp, sz, f32, u64, u64, vp]),
+    "fedfr_dropout_bwd": (i32, [vp, vp, sz, f32, vp]),
+    "fedfr_nchw_to_nhwc16": (i32, [vp, vp, i32, i32, i32, vp]),
     "fedfr_stem_stat_rows": (i32, [i32, i32]),
     "fedfr_stem_fwd": (i32, [vp, vp, vp, vp, i32, i32, vp]),
     "fedfr_stem_wgrad_ws_bytes": (sz, [i32, i32]),

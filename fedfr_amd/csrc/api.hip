@@ -505,6 +505,30 @@ int fedfr_gemm_tn(const uint16_t* P, const uint16_t* Q, float* C, int Kp, int NI
   p.P = BF(P); p.Q = BF(Q); p.Kp = Kp; p.NI = NI; p.NJ = NJ; p.mode = 0; p.ldp = NI; p.ldq = NJ; p.out = C; p.use_tr = g_tn_use_tr;
   return gemm_tn_launch(p, 1, ST(stream));
 }
+// the network tail one kernel at a time (tests/test_tail_kernels_gpu.py): thin wrappers, every pointer the launcher takes as nullable stays so
+int fedfr_bn1d_fwd(const float* x, float* y, int B, int C, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                   float momentum, float eps, int training, float* save_mean, float* save_rstd, void* stream) {
+  FEDFR_REQUIRE((save_mean != nullptr) == (save_rstd != nullptr), "bn1d_fwd: save_mean and save_rstd go together");
+  return ew_bn1d_fwd(x, y, B, C, gamma, beta, running_mean, running_var, momentum, eps, training, save_mean, save_rstd, ST(stream));
+}
+int fedfr_bn1d_bwd(const float* dy, const float* x, float* dx, int B, int C, const float* gamma, const float* save_mean, const float* save_rstd,
+                   float* dbeta, float* dx_colsum, uint16_t* dx_h16, uint16_t* dx_h16_t, int ldt, int frozen, void* stream) {
+  FEDFR_REQUIRE(!dx_h16_t || ldt >= B, "bn1d_bwd: ldt=%d is smaller than B=%d", ldt, B);
+  return ew_bn1d_bwd(dy, x, dx, B, C, gamma, save_mean, save_rstd, dbeta, dx_colsum, BFM(dx_h16), BFM(dx_h16_t), ldt, ST(stream), frozen);
+}
+int fedfr_reduce_slabs(float* dst, const float* slabs, int nsplit, size_t n, const float* bias, int bias_n, float* dst1, const float* slabs1,
+                       void* stream) {
+  if (!dst1 && !slabs1) return ew_reduce_slabs(dst, slabs, nsplit, n, bias, bias_n, ST(stream));
+  FEDFR_REQUIRE(dst1 && slabs1 && !bias, "reduce_slabs: the pair launch needs both dst1 and slabs1 and takes no bias");
+  return ew_reduce_slabs2(dst, slabs, dst1, slabs1, nsplit, n, ST(stream));
+}
+int fedfr_dropout_fwd(uint16_t* t, unsigned char* mask, size_t n, float p, unsigned long long seed, unsigned long long step, void* stream) {
+  return ew_dropout_fwd(BFM(t), mask, n, p, seed, step, ST(stream));
+}
+int fedfr_dropout_bwd(float* dx, const unsigned char* mask, size_t n, float p, void* stream) { return ew_dropout_bwd(dx, mask, n, p, ST(stream)); }
+int fedfr_nchw_to_nhwc16(const float* src, uint16_t* dst, int B, int C, int HW, void* stream) {
+  return ew_nchw_f32_to_nhwc_bf16(src, BFM(dst), B, C, HW, ST(stream));
+}
 int fedfr_stem_stat_rows(int batch, int hw) { return ew_stem_stat_rows(batch, hw, hw); }
 int fedfr_stem_fwd(const float* x, const float* w, uint16_t* y, float* stats, int batch, int hw, void* stream) {
   return ew_stem_fwd(x, w, BFM(y), stats, batch, hw, hw, ST(stream));

@@ -222,6 +222,30 @@ int fedfr_weight_shadows(const float* w_krsc, uint16_t* w_h16, uint16_t* wd_h16,
 int fedfr_gemm_nt(const uint16_t* A, const uint16_t* B, float* C, void* ws, size_t ws_bytes, int M, int N, int K,
                   void* stream);
 int fedfr_gemm_tn(const uint16_t* P, const uint16_t* Q, float* C, int Kp, int NI, int NJ, void* stream);
+/* The network tail (between the last residual block and the embedding) one kernel launch at a time (tests/test_tail_kernels_gpu.py); what
+ * fedfr_net_forward / _backward run there.
+ * fedfr_bn1d_fwd: BatchNorm1d on fp32 x [B][C] -> y.  training: batch statistics (fp64 sums), running_mean / running_var updated with
+ *   `momentum` (running_var from the unbiased variance; B = 1: the biased one); else the running statistics normalise and nothing is
+ *   updated.  gamma NULL: 1, beta NULL: 0; save_mean / save_rstd [C] (both or neither) receive what the backward pass reads.
+ * fedfr_bn1d_bwd: its backward from the saved statistics: dx [B][C], dbeta [C] = column sums of dy, dx_colsum [C] = column sums of dx
+ *   (the bias gradient of the Linear in front), dx_h16 [B][C] and dx_h16_t [C][ldt] (ldt >= B; columns >= B are not written) = dx rounded
+ *   to the 16-bit storage type; each of the five may be NULL.  frozen: the statistics were constants, dx = gamma rstd dy.
+ * fedfr_reduce_slabs: dst[i] = sum_s slabs[s * n + i] (+ bias[i % bias_n]) in a fixed order; n % 4 == 0, bias_n % 4 == 0.  A second pair
+ *   (dst1, slabs1: both or neither, same nsplit and n, no bias) is reduced by the same launch.
+ * fedfr_dropout_fwd: in place on 16-bit t [n] (n % 8 == 0), 0 < p < 1: element e is kept iff the 16-bit field e % 4 of
+ *   splitmix64(key ^ (e / 4)) is >= (unsigned)(p * 65536), key = seed * 0x100000001B3 + step * 0x9E3779B1 (mod 2^64); kept values are
+ *   scaled by 1 / (1 - p), mask [n] receives one byte (1 kept / 0 dropped) per element.  fedfr_dropout_bwd: dx [n] fp32 (n % 4 == 0) in
+ *   place through the same bytes.
+ * fedfr_nchw_to_nhwc16: fp32 [B][C][HW] -> 16-bit [B][HW][C], C even. */
+int fedfr_bn1d_fwd(const float* x, float* y, int B, int C, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                   float momentum, float eps, int training, float* save_mean, float* save_rstd, void* stream);
+int fedfr_bn1d_bwd(const float* dy, const float* x, float* dx, int B, int C, const float* gamma, const float* save_mean, const float* save_rstd,
+                   float* dbeta, float* dx_colsum, uint16_t* dx_h16, uint16_t* dx_h16_t, int ldt, int frozen, void* stream);
+int fedfr_reduce_slabs(float* dst, const float* slabs, int nsplit, size_t n, const float* bias, int bias_n, float* dst1, const float* slabs1,
+                       void* stream);
+int fedfr_dropout_fwd(uint16_t* t, unsigned char* mask, size_t n, float p, unsigned long long seed, unsigned long long step, void* stream);
+int fedfr_dropout_bwd(float* dx, const unsigned char* mask, size_t n, float p, void* stream);
+int fedfr_nchw_to_nhwc16(const float* src, uint16_t* dst, int B, int C, int HW, void* stream);
 /* stem conv 3->64 (iresnet.py:76) on fp32 NCHW input */
 int fedfr_stem_stat_rows(int batch, int hw);
 int fedfr_stem_fwd(const float* x, const float* w_krsc, uint16_t* y, float* stats, int batch, int hw, void* stream);
