@@ -1,7 +1,8 @@
 // The BatchNorm algebra, written once: every kernel that derives coefficients from statistics or applies them per element (the finalize kernels and
 // row-slab passes of bn_rowslab.hip, the channel-sliced passes of bn_sliced.hip, the fused stem weight gradient of stem.hip) calls these helpers, so
 // fused and unfused passes agree bit for bit because they run the same expressions, not copies of them (tests/test_kernels_gpu.py:
-// test_sliced_and_finalize_coefficients_agree_bitwise, tests/test_stem_chain_gpu.py).  The library is built with -ffp-contract=on: which products fuse
+// test_sliced_and_finalize_coefficients_agree_bitwise, tests/test_stem_chain_gpu.py; tests/test_bn_sliced_gpu.py holds every sliced pass to the fp64
+// value of these expressions on the partial rows it is given, tests/bn_sliced_cases.py restates them).  The library is built with -ffp-contract=on: which products fuse
 // into an FMA is decided per source expression, so the statement structure and operand order below ARE the arithmetic.
 #pragma once
 #include "common.h"
