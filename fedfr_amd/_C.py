@@ -155,6 +155,9 @@ SIGNATURES = {
     "fedfr_delta_scale_bytes": (sz, [sz]),
     "fedfr_delta_quantize": (i32, [vp, vp, vp, vp, vp, i32, sz, vp, vp]),
     "fedfr_delta_aggregate": (i32, [vp, vp, vp, vp, vp, i32, i32, sz, i32, vp]),
+    "fedfr_topk_workspace_bytes": (sz, [sz, i32]),
+    "fedfr_topk_sparsify": (i32, [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]),
+    "fedfr_sparse_aggregate": (i32, [vp, vp, vp, vp, vp, vp, i32, sz, i32, vp]),
     "fedfr_pfc_rand": (i32, [vp, i32, u64, u64, vp]),
     "fedfr_pfc_localize": (i32, [vp, i32, i64, i32, vp, vp]),
     "fedfr_pfc_topk": (i32, [vp, i32, i32, vp, vp, vp]),

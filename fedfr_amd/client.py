@@ -1111,6 +1111,17 @@ class Client(object):
             comp = self.compressor = DeltaCompressor(bits, error_feedback)
         return comp.compress(global_state, self.backbone_state_dict)
 
+    @_C.on_device(lambda self: self.device)
+    def get_sparse_update(self, global_state, ratio, error_feedback=True):
+        """The trained state as a top-k upload against ``global_state`` (the state the round started from): ``compress.SparseDelta`` holding
+        ``compress.keep_count(n, ratio)`` entries.  The client's ``TopKCompressor`` — and with it the residual e_i of the error feedback —
+        is created on first use and again whenever ``ratio`` or ``error_feedback`` differs from the one it holds, and lives across rounds."""
+        from .compress import TopKCompressor
+        comp = getattr(self, "sparsifier", None)
+        if comp is None or comp.ratio != float(ratio) or comp.error_feedback != bool(error_feedback):
+            comp = self.sparsifier = TopKCompressor(ratio, error_feedback)
+        return comp.compress(global_state, self.backbone_state_dict)
+
     def get_global_fc(self):
         return self.fc_module.get_pretrain_fc()
 

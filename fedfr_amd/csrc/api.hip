@@ -11,6 +11,7 @@
 #include "optim.h"
 #include "robust.h"
 #include "compress.h"
+#include "sparse.h"
 
 static thread_local char g_err[512] = "";
 extern int g_tn_use_tr;
@@ -846,6 +847,15 @@ int fedfr_delta_quantize(const float* x, const float* xi, float* resid, void* co
 int fedfr_delta_aggregate(float* dst, const float* base, const void* const* codes, const unsigned char* const* scales, const float* ws, int k, int bits,
                           size_t n, int accumulate, void* stream) {
   return delta_aggregate(dst, base, codes, scales, ws, k, bits, n, accumulate, ST(stream));
+}
+size_t fedfr_topk_workspace_bytes(size_t n, int feedback) { return topk_workspace_bytes(n, feedback); }
+int fedfr_topk_sparsify(const float* x, const float* xi, float* resid, size_t n, size_t keep, unsigned* idx, float* val, int* nonfinite, void* ws,
+                        void* stream) {
+  return topk_sparsify(x, xi, resid, n, keep, idx, val, nonfinite, ws, ST(stream));
+}
+int fedfr_sparse_aggregate(float* dst, const float* base, const unsigned* const* idx, const float* const* val, const size_t* keeps, const float* ws,
+                           int k, size_t n, int accumulate, void* stream) {
+  return sparse_aggregate(dst, base, idx, val, keeps, ws, k, n, accumulate, ST(stream));
 }
 int fedfr_pfc_rand(float* perm, int n, unsigned long long seed, unsigned long long step, void* stream) {
   return optim_pfc_rand(perm, n, seed, step, ST(stream));

@@ -4,10 +4,11 @@ xGMI when every client is its own rank (one client = one MI355X); the spread-out
 (reference server.py:48-63, :340-371) on one fused HIP kernel; and the round's 1:1 verification of the global model with its
 checkpoints (reference server.py:135-148).  Build extensions beyond the reference's FedAvg: the server optimisers (``FedOpt``), the
 robust rules (``FedRobust``: coordinate-wise trimmed mean / median, Krum / Multi-Krum) and compressed client uploads (``FedCompressed``:
-8 / 4-bit block-scaled deltas with error feedback, see compress.py)."""
+8 / 4-bit block-scaled deltas with error feedback; ``FedSparse``: top-k sparsified deltas with error feedback; see compress.py)."""
 from __future__ import annotations
 
 import copy
+import ctypes
 import logging
 import random
 from collections import OrderedDict
@@ -443,6 +444,58 @@ def FedCompressed(global_state, updates, weights: Sequence[float], server_opt=No
     return FlatStateDict.from_flat((P, *stats), global_state.table, global_state.layers)
 
 
+# ---- top-k uploads: csrc/sparse.hip topk_* kernels (client side, compress.py) / sparse_aggregate_kernel
+def FedSparse(global_state, updates, weights: Sequence[float], server_opt=None):
+    """One round from top-k uploads (``compress.SparseDelta``): the PARAMETERS of the new global state are x + Σ_i (n_i/Σn)·sparse_i with
+    x = ``global_state``'s parameters and sparse_i the scattered upload of client i (fedfr_sparse_aggregate: ≤ 8 uploads per pass, x read
+    and the result written once, no float atomics; the sorted entries are walked 256 at a time, so an entry is loaded again for every
+    tile of 4096 elements its step reaches into; more clients chain passes with ``accumulate``, and x is added by the last pass only, so
+    the sum has the roundings of one ascending loop).  The uploads may hold different numbers of entries.  With ``server_opt`` (a
+    ``ServerOptimizer``) the same sum WITHOUT x is the pseudo-gradient Δ and goes through ``server_opt.apply_delta``; ``clip_norm`` > 0
+    raises ``ValueError`` (the clip needs per-client norms of the deltas: not provided).  BN running statistics and
+    ``num_batches_tracked`` arrive uncompressed and are averaged exactly as ``FedPavg`` averages them.  An element a client sent as
+    non-finite is NaN in the result, as it would be with fp32 uploads.  Only a GPU ``FlatStateDict`` is accepted as ``global_state``."""
+    from .compress import SparseDelta
+    if not isinstance(global_state, FlatStateDict) or global_state.flat is None:
+        raise RuntimeError("fedfr_amd.FedSparse: the global state must be a FlatStateDict (client.flat_state_dict)")
+    if not updates or not all(isinstance(u, SparseDelta) for u in updates):
+        raise RuntimeError("fedfr_amd.FedSparse: the client updates must be SparseDeltas (Client.get_sparse_update)")
+    if len(weights) != len(updates):
+        raise RuntimeError("fedfr_amd.FedSparse: %d weights for %d client updates" % (len(weights), len(updates)))
+    if isinstance(server_opt, RobustAggregator):
+        raise ValueError("FedSparse: a robust rule (%s) needs whole client states, not top-k uploads" % server_opt.kind)
+    if server_opt is not None and server_opt.clip_norm > 0:
+        raise ValueError("FedSparse: clip_norm > 0 needs per-client norms of the deltas, which top-k uploads do not provide; use FedOpt on "
+                         "uncompressed states")
+    tot = sum(weights)
+    ws = [w / tot for w in weights]
+    x = global_state.flat[0]
+    _check_states(x, [], "FedSparse")
+    n = x.numel()
+    for u in updates:
+        if u.n != n:
+            raise RuntimeError("fedfr_amd.FedSparse: an update for %d parameters among updates for %d parameters" % (u.n, n))
+        if not 0 <= u.keep <= n:
+            raise RuntimeError("fedfr_amd.FedSparse: an update of %d entries for %d parameters" % (u.keep, n))
+        for t, dt, what in ((u.idx, torch.int32, "idx"), (u.val, f32, "val")):
+            if t.dtype != dt or t.numel() != u.keep or t.device != x.device or not t.is_contiguous():
+                raise RuntimeError("fedfr_amd.FedSparse: %s must be a contiguous %s tensor of %d entries on %s"
+                                   % (what, str(dt).replace("torch.", ""), u.keep, x.device))
+    P = torch.empty_like(x)
+    for c0 in range(0, len(updates), 8):
+        grp = updates[c0:c0 + 8]
+        last = c0 + 8 >= len(updates)
+        wv = (_C.f32 * len(grp))(*[float(np.float32(w)) for w in ws[c0:c0 + 8]])
+        keeps = (ctypes.c_size_t * len(grp))(*[u.keep for u in grp])
+        if n:
+            _C.call("fedfr_sparse_aggregate", P.data_ptr(), x.data_ptr() if last and server_opt is None else None, _C.ptr_array([u.idx for u in grp]),
+                    _C.ptr_array([u.val for u in grp]), keeps, wv, len(grp), n, 1 if c0 > 0 else 0, _C.stream())
+    if server_opt is not None:
+        server_opt.apply_delta(P, x, P)
+    stats = _average_stats([_StatsOnly(u.stats, u.counters) for u in updates], ws)
+    return FlatStateDict.from_flat((P, *stats), global_state.table, global_state.layers)
+
+
 def FedAvg_on_FC(pretrain_fc, models, weights, p):
     """reference server.py:36-46."""
     tot = sum(weights)
@@ -656,6 +709,22 @@ class Server(object):
             if float(getattr(self.args, "clip_norm", 0.0) or 0.0) > 0:
                 raise ValueError("Server.train: compress_bits=%d cannot be combined with clip_norm=%r: the clip needs per-client norms of the "
                                  "dequantised deltas, which are not provided" % (compress_bits, self.args.clip_norm))
+        topk_ratio = getattr(self.args, "topk_ratio", 0) or 0                # top-k uploads (a build extension): absent or 0 = off
+        if topk_ratio:                                                       # the same: before anybody trains
+            from .compress import keep_count
+            try:
+                keep_count(1, topk_ratio)
+            except ValueError:
+                raise ValueError("Server.train: topk_ratio must be a number in (0, 1] (got %r)" % (topk_ratio,)) from None
+            if compress_bits:
+                raise ValueError("Server.train: topk_ratio=%r cannot be combined with compress_bits=%d: quantising the kept values is not provided"
+                                 % (topk_ratio, compress_bits))
+            if aggr_alg in ROBUST_ALG_KINDS:
+                raise ValueError("Server.train: topk_ratio=%r cannot be combined with aggr_alg=%r: a robust rule needs whole client states"
+                                 % (topk_ratio, aggr_alg))
+            if float(getattr(self.args, "clip_norm", 0.0) or 0.0) > 0:
+                raise ValueError("Server.train: topk_ratio=%r cannot be combined with clip_norm=%r: the clip needs per-client norms of the "
+                                 "deltas, which are not provided" % (topk_ratio, self.args.clip_norm))
         models, models_fc, losses_, data_sizes = [], [], [], []
         public = bool(getattr(self.args, "add_pretrained_data", False))
         return_all = bool(getattr(self.args, "return_all", False))
@@ -721,13 +790,15 @@ class Server(object):
                     t.join()
                 if errs:
                     raise errs[0]
-        if compress_bits:
+        if compress_bits or topk_ratio:
             global_state = flat_state_dict(self.federated_model)              # what the round started from: the clients trained on copies
             feedback = bool(getattr(self.args, "error_feedback", True))
         for i in order:
             losses_.append(self.clients[i].get_train_loss())
             if compress_bits:                                                 # "client sends Q(x_i - x + e_i)" and keeps e_i
                 models.append(self.clients[i].get_compressed_update(global_state, compress_bits, feedback))
+            elif topk_ratio:                                                  # "client sends the largest entries of x_i - x + e_i" and keeps the rest
+                models.append(self.clients[i].get_sparse_update(global_state, topk_ratio, feedback))
             else:
                 models.append(self.clients[i].get_model())
             if return_all:
@@ -757,6 +828,16 @@ class Server(object):
             for j, nb in enumerate(bad):
                 if nb > 0:
                     self.logger.warning('Client %s sent %d non-finite blocks (NaN in the aggregate there)'
+                                        % (getattr(self.clients[order[j]], "cid", order[j]), nb))
+        elif topk_ratio:
+            aggr_state_dict = FedSparse(global_state, models, data_sizes, self.server_opt if aggr_alg in AGGR_ALG_KINDS else None)
+            sent, dense = sum(u.nbytes for u in models), sum(u.dense_nbytes for u in models)
+            self.logger.info('Top-k uploads (ratio %g%s): %d bytes from %d clients, %.4f of the %d bytes of fp32 states'
+                             % (topk_ratio, ", error feedback" if feedback else "", sent, len(models), sent / dense, dense))
+            bad = torch.cat([u.nonfinite for u in models]).cpu().tolist()     # one small copy: the round's one read of the counters
+            for j, nb in enumerate(bad):
+                if nb > 0:
+                    self.logger.warning('Client %s sent %d non-finite elements (NaN in the aggregate there)'
                                         % (getattr(self.clients[order[j]], "cid", order[j]), nb))
         elif aggr_alg in ("FedAvg", "FedProx"):
             aggr_state_dict = FedPavg(models, data_sizes)

@@ -676,6 +676,52 @@ int fedfr_delta_quantize(const float* x, const float* xi, float* resid, void* co
 int fedfr_delta_aggregate(float* dst, const float* base, const void* const* codes, const unsigned char* const* scales, const float* ws, int k,
                           int bits, size_t n, int accumulate, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * top-k sparsified client uploads with error feedback — no reference counterpart.  A client sends the `keep` largest-magnitude entries of
+ * x_i - x + e_i as (index, value) pairs, 8 bytes per kept parameter, and keeps everything else as e_i for the next round.  The selection
+ * is EXACT (a radix select on the device: no sampling, no approximate threshold) and nothing is rounded after step 1, so every output of
+ * both kernels can be reproduced bit for bit (tests/sparse_cases.py).  1 <= keep <= n < 2^31.
+ * THE FORMAT.
+ *   1. value to send   v_j = (x_i[j] - x[j]) + e[j]: two fp32 operations in that order; without error feedback v_j = x_i[j] - x[j]
+ *                      (step 1 of fedfr_delta_quantize).
+ *   2. key             key_j = bits(v_j) & 0x7FFFFFFF, a 31-bit unsigned integer whose order is the order of |v_j|: +-0 have key 0,
+ *                      subnormals order correctly, inf (0x7F800000) and every NaN (above it) order above every finite value, so what
+ *                      a diverged client produces is always sent and the server sees it, as it would with fp32 uploads.
+ *   3. selection       S = the keep elements that come first when sorted by (key descending, index ascending).  Equivalently: T = the
+ *                      keep-th largest key, r = keep - #{key > T}, S = {key > T} and the r lowest-index elements with key == T.
+ *   4. upload          idx: uint32 [keep], strictly ascending; val: fp32 [keep], val[t] = v[idx[t]] bit for bit (NaN payloads and the
+ *                      sign of zero included).  Element j of S lands at t = #{key > T, index < j} + min(#{key == T, index < j}, r).
+ *   5. residual        e'[j] = +0 if j is in S or v_j is not finite (a diverged round must not poison the residual), otherwise
+ *                      e'[j] = v_j: scatter(idx, val) + e' == v exactly wherever v is finite and non-zero.
+ *   6. counter         nonfinite adds the number of non-finite ELEMENTS of v (an integer atomic: order-free).
+ * ------------------------------------------------------------------------------------------------ */
+/* bytes of the workspace fedfr_topk_sparsify needs: the select state and three digit histograms, one pair of counts per tile of 2048
+ * elements, and WITHOUT error feedback the n values v (with it they live in the residual buffer).  A multiple of 16, monotone in n. */
+size_t fedfr_topk_workspace_bytes(size_t n, int feedback);
+/* Stream-ordered, no host synchronisation and no device-to-host copy: T and r stay on the device.  A chain of launches on `stream`, none
+ * of which waits for another workgroup of its own launch: v and the histogram of the top 11 key bits; two more histogram passes (10 bits
+ * each) over the elements under the prefix chosen so far, each followed by a one-workgroup kernel that picks the bin; a pass that counts
+ * (#key > T, #key == T) per tile; a one-workgroup scan of those counts; the emit pass.  Histograms are integer sums (LDS atomics, then
+ * global atomics); there are no float atomics.  x (global parameters) and xi (client parameters) are read-only; resid (e) ends as e' and
+ * may be NULL: no error feedback, nothing read or written for it; idx and val receive exactly keep entries; nothing is written behind any
+ * buffer.  nonfinite may be NULL; otherwise a DEVICE int the caller has zeroed.  ws: fedfr_topk_workspace_bytes(n, resid != NULL) bytes,
+ * need not be initialised.  x, xi, resid, idx, val and ws 16-byte aligned.  FEDFR_ERR_ARG, before anything is launched, for a NULL x, xi,
+ * idx, val or ws, keep = 0 or keep > n, n >= 2^31, or a misaligned buffer; n = 0 with keep = 0 is a no-op. */
+int fedfr_topk_sparsify(const float* x, const float* xi, float* resid, size_t n, size_t keep, unsigned* idx, float* val, int* nonfinite,
+                        void* ws, void* stream);
+/* The weighted sum of k <= 8 top-k uploads in one launch (HOST arrays of k device pointers idx / val, k entry counts keeps and k weights
+ * ws, as fedfr_delta_aggregate).  Per element j:
+ *   s = accumulate ? dst[j] : +0;   for ascending i with j in idx_i: s = s + ws[i] val_i[t];   dst[j] = base ? base[j] + s : s
+ * One fp32 multiply and one fp32 add per entry, nothing contracted, no float atomics: a workgroup keeps a tile of s in LDS, adds the
+ * uploads' entries of that tile upload by upload, and writes dst once.  More than 8 uploads chain calls with accumulate = 1 and pass base
+ * (the global parameters x) to the last one only.  dst may equal base; the uploads may hold different numbers of entries.  Every idx_i
+ * must be strictly ascending and below n; for ANY index content an entry is applied only if it lies inside the tile at hand, so a
+ * malformed upload gives an unspecified sum but never an out-of-bounds access.  dst, base, idx_i and val_i 16-byte aligned.
+ * FEDFR_ERR_ARG, before anything is launched, for k outside 1..8, a NULL dst, idx, val, keeps, ws or array entry, keeps[i] > n,
+ * n >= 2^31, or a misaligned buffer; n = 0 with valid arguments is a no-op. */
+int fedfr_sparse_aggregate(float* dst, const float* base, const unsigned* const* idx, const float* const* val, const size_t* keeps,
+                           const float* ws, int k, size_t n, int accumulate, void* stream);
+
 int fedfr_pfc_rand(float* perm, int n, unsigned long long seed, unsigned long long step, void* stream);
 int fedfr_pfc_localize(long long* label, int n, long long class_start, int num_local, float* perm, void* stream);
 int fedfr_pfc_topk(const float* perm, int n, int k, long long* index, int* npos_out, void* stream);
