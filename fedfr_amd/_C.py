@@ -111,7 +111,13 @@ SIGNATURES = {
     "fedfr_sgemm_colflag": (i32, [vp, vp, i32, i32, i32, i64, i64, i64, i64, f32, f32, vp, vp]),
     "fedfr_class_accumulate": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
     "fedfr_bias_prelu_bwd": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
-    "fedfr_pad_input_nhwc": (i32, [vp, vp, i32, i32, i32, i32, vp]),
+    "fedfr_prelu_bwd_rows": (i32, [i32, i32]),
+    "fedfr_prelu_bwd_pass": (i32, [vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
+    "fedfr_prelu_bwd_finalize": (i32, [vp, i32, i32, vp, vp, vp]),
+    "fedfr_prelu_bwd_finalize_multi": (i32, [vp, vp, i32, C.POINTER(u64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i32), C.POINTER(i32),
+                                             C.POINTER(i32), vp]),
+    "fedfr_bn_eval_coeffs": (i32, [vp, vp, vp, i32] + [C.POINTER(i32)] * 6 + [f32, vp]),
+    "fedfr_pad_input_nhwc":(i32, [vp, vp, i32, i32, i32, i32, vp]),
     "fedfr_preprocess_u8": (i32, [vp, vp, vp, i32, i32, i32, vp]),
     "fedfr_roc_histogram": (i32, [vp, vp, i32, i32, i32, vp, vp]),
     "fedfr_roc_histogram_groups": (i32, [vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, vp]),

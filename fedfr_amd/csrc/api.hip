@@ -785,6 +785,43 @@ int fedfr_bias_prelu_bwd(const uint16_t* dy, const uint16_t* x, const float* bia
                          float* coef, float* dbias, float* dalpha, const uint16_t* add, uint16_t* dx, void* stream) {
   return ew_bias_prelu_bwd(BF(dy), BF(x), bias, alpha, M, C, partials, coef, dbias, dalpha, BF(add), BFM(dx), ST(stream));
 }
+// the passes of the sphnet plan (net_sph.inc) and the eval-mode coefficient launch (net.hip), argument for argument: plumbing only
+int fedfr_prelu_bwd_rows(int M, int C) { return ew_prelu_bwd_rows(M, C); }
+int fedfr_prelu_bwd_pass(const uint16_t* dy, const uint16_t* add, const uint16_t* x, const float* bias, const float* alpha, int M, int C,
+                         uint16_t* gsum, uint16_t* dz, float* rows, void* stream) {
+  return ew_prelu_bwd_pass(BF(dy), BF(add), BF(x), bias, alpha, M, C, BFM(gsum), BFM(dz), rows, ST(stream));
+}
+int fedfr_prelu_bwd_finalize(const float* rows, int P, int C, float* dbias, float* dalpha, void* stream) {
+  return ew_prelu_bwd_finalize(rows, P, C, dbias, dalpha, ST(stream));
+}
+int fedfr_prelu_bwd_finalize_multi(const void* base, float* grads, int n, const unsigned long long* rows_off, const long long* dbias_off,
+                                   const long long* dalpha_off, const int* P, const int* C, const int* nv_row, void* stream) {
+  FEDFR_REQUIRE(n >= 1 && n <= kMaxPreluFin, "prelu_bwd_finalize_multi: n=%d entries (1 ... %d)", n, kMaxPreluFin);
+  FEDFR_REQUIRE(rows_off && dbias_off && dalpha_off && P && C && nv_row, "prelu_bwd_finalize_multi: null table");
+  PreluFinTable fin{};
+  for (int i = 0; i < n; ++i) {      // net_sph.inc: fin_add
+    FEDFR_REQUIRE(C[i] > 0 && (C[i] & 7) == 0 && P[i] > 0 && (nv_row[i] == 2 || nv_row[i] == 3) && dalpha_off[i] >= 0,
+                  "prelu_bwd_finalize_multi: entry %d: C=%d (C %% 8) P=%d nv_row=%d", i, C[i], P[i], nv_row[i]);
+    PreluFinEntry& e = fin.e[fin.n++];
+    e.rows_off = rows_off[i]; e.dbias_off = dbias_off[i] >= 0 ? dbias_off[i] : -1; e.dalpha_off = dalpha_off[i];
+    e.P = P[i]; e.C = C[i]; e.blk0 = fin.blocks; e.nv_row = nv_row[i];
+    fin.blocks += C[i] / 8;
+  }
+  return ew_prelu_bwd_finalize_multi(reinterpret_cast<const unsigned char*>(base), grads, fin, ST(stream));
+}
+int fedfr_bn_eval_coeffs(const float* params, const float* bufs, float* save, int n, const int* C, const int* g_off, const int* b_off,
+                         const int* rm_off, const int* rv_off, const int* save_off, float eps, void* stream) {
+  FEDFR_REQUIRE(n >= 1 && n <= kMaxBnEvalEntries, "bn_eval_coeffs: n=%d entries (1 ... %d)", n, kMaxBnEvalEntries);
+  FEDFR_REQUIRE(C && g_off && b_off && rm_off && rv_off && save_off, "bn_eval_coeffs: null table");
+  BnEvalTable t{};
+  t.eps = eps;
+  for (int i = 0; i < n; ++i) {      // net.hip: eval_coeffs_all
+    FEDFR_REQUIRE(C[i] > 0 && b_off[i] >= 0 && rm_off[i] >= 0 && rv_off[i] >= 0 && save_off[i] >= 0, "bn_eval_coeffs: entry %d: C=%d or a negative offset", i, C[i]);
+    BnEvalEntry& e = t.e[t.n++];
+    e.C = C[i]; e.g_off = g_off[i]; e.b_off = b_off[i]; e.rm_off = rm_off[i]; e.rv_off = rv_off[i]; e.save_off = save_off[i];
+  }
+  return ew_bn_eval_coeffs_multi(params, bufs, save, t, ST(stream));
+}
 int fedfr_pad_input_nhwc(const float* src_nchw, uint16_t* dst_nhwc, int B, int C, int HW, int Cpad, void* stream) {
   return ew_pad_input_nhwc(src_nchw, BFM(dst_nhwc), B, C, HW, Cpad, ST(stream));
 }

@@ -390,6 +390,26 @@ int fedfr_class_accumulate(const float* feats, const long long* label, int B, in
  * dalpha = sum dy * z over z <= 0, dx = dz (+ add).  partials: [fedfr_bn_bwd_rows][3][C], coef: [3][C] scratch. */
 int fedfr_bias_prelu_bwd(const uint16_t* dy, const uint16_t* x, const float* bias, const float* alpha, int M, int C, float* partials,
                          float* coef, float* dbias, float* dalpha, const uint16_t* add, uint16_t* dx, void* stream);
+/* The same backward as fedfr_net_backward runs it on sphnet, one pass at a time (thin wrappers for kernel-level tests; no reference counterpart):
+ *   fedfr_prelu_bwd_pass: ONE streaming pass.  g = dy (+ add, the 16-bit rounded sum is written to gsum, required with add and is what the
+ *   PReLU sees); z = x + bias (bias may be NULL); dz = g * (z > 0 ? 1 : alpha) -> dz; rows [fedfr_prelu_bwd_rows(M, C)][2][C] =
+ *   (sum of the unrounded dz | sum g z over z <= 0) per workgroup.
+ *   fedfr_prelu_bwd_finalize: P rows [2][C] -> dbias, dalpha (either may be NULL), summed in fp64.
+ *   fedfr_prelu_bwd_finalize_multi: n = 1 ... 64 such finalizes in one launch.  Entry i: P[i] rows of nv_row[i] (2 or 3) statistics of C[i]
+ *   channels (C % 8 == 0) at BYTE offset rows_off[i] of `base` (16-byte aligned), of which the first two are read; results at FLOAT offsets
+ *   dbias_off[i] (< 0: none) and dalpha_off[i] of `grads`.  The offset arrays are host memory. */
+int fedfr_prelu_bwd_rows(int M, int C);
+int fedfr_prelu_bwd_pass(const uint16_t* dy, const uint16_t* add, const uint16_t* x, const float* bias, const float* alpha, int M, int C,
+                         uint16_t* gsum, uint16_t* dz, float* rows, void* stream);
+int fedfr_prelu_bwd_finalize(const float* rows, int P, int C, float* dbias, float* dalpha, void* stream);
+int fedfr_prelu_bwd_finalize_multi(const void* base, float* grads, int n, const unsigned long long* rows_off, const long long* dbias_off,
+                                   const long long* dalpha_off, const int* P, const int* C, const int* nv_row, void* stream);
+/* eval-mode BatchNorm coefficients of n = 1 ... 160 BatchNorms in one launch (what fedfr_net_forward runs up front when not training, and
+ * what freeze_BN training reads): entry i has C[i] channels, weight / bias at float offsets g_off[i] (< 0: weight = 1) / b_off[i] of `params`,
+ * running mean / variance at rm_off[i] / rv_off[i] of `bufs`, and writes (scale, shift, mean, rstd), [4][C[i]], at save_off[i] of `save`:
+ * rstd = 1 / sqrt(var + eps), scale = weight rstd, shift = bias - mean weight rstd, all in fp32.  The offset arrays are host memory. */
+int fedfr_bn_eval_coeffs(const float* params, const float* bufs, float* save, int n, const int* C, const int* g_off, const int* b_off,
+                         const int* rm_off, const int* rv_off, const int* save_off, float eps, void* stream);
 /* fp32 NCHW [B][C][HW] -> 16-bit NHWC [B][HW][Cpad] with zero channels C..Cpad-1 (3-channel input of sphnet's first conv) */
 int fedfr_pad_input_nhwc(const float* src_nchw, uint16_t* dst_nhwc, int B, int C, int HW, int Cpad, void* stream);
 /* input pipeline (dataset.py:81-92): uint8 [B][H][W][3] + optional per-image flip flags -> fp32 [B][3][H][W] = (x/255 - 0.5)/0.5 */

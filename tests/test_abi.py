@@ -70,6 +70,34 @@ def test_plan_layout_matches_reference_inventory(built_lib):
     assert b"bn_finalize" in msg and b"12" in msg, msg
 
 
+def test_rowslab_test_wrappers_check_their_tables_on_the_host(built_lib):
+    """The by-value tables of fedfr_prelu_bwd_finalize_multi (1 ... 64 entries, C % 8 == 0) and fedfr_bn_eval_coeffs (1 ... 160 entries) are
+    filled and checked on the host before any HIP call, and the row queries are the restated slab formula (tests/rowslab_cases.py)."""
+    import ctypes as C
+    import rowslab_cases as K
+    lib = built_lib.lib()
+    err_arg = int(re.search(r"#define FEDFR_ERR_ARG \((-?\d+)\)", open(HEADER).read()).group(1))
+    buf = (C.c_float * 64)()
+    for n, ch in ((0, 8), (K.MAX_PRELU_FIN + 1, 8), (1, 12)):
+        m = max(n, 1)
+        rc = lib.fedfr_prelu_bwd_finalize_multi(buf, buf, n, (C.c_ulonglong * m)(), (C.c_longlong * m)(), (C.c_longlong * m)(), (C.c_int * m)(*[2] * m),
+                                                (C.c_int * m)(*[ch] * m), (C.c_int * m)(*[2] * m), None)
+        assert rc == err_arg and b"prelu_bwd_finalize_multi" in lib.fedfr_last_error_string(), (n, ch)
+    one = (C.c_int * 1)(8)
+    for n in (0, K.MAX_BN_EVAL + 1):
+        assert lib.fedfr_bn_eval_coeffs(buf, buf, buf, n, one, one, one, one, one, one, 1e-5, None) == err_arg
+        assert b"bn_eval_coeffs" in lib.fedfr_last_error_string()
+    assert lib.fedfr_prelu_bwd_pass(buf, buf, buf, None, buf, 100, 64, None, buf, buf, None) == err_arg        # an addend without gsum
+    assert lib.fedfr_prelu_bwd_finalize(buf, 2, 12, buf, buf, None) == err_arg
+    for M, ch in ((1, 8), (3000, 64), (1000, 96), (777, 512), (512 * 32 + 1, 512), (100, 2048), (128 * 112 * 112, 64)):
+        assert lib.fedfr_prelu_bwd_rows(M, ch) == K.geometry(M, ch, K.PRELU_BLOCKS)["grid"]
+        assert lib.fedfr_bn_apply_stat_rows(M, ch) == K.geometry(M, ch, K.APPLY_BLOCKS)["grid"]
+    # the producers that hand fedfr_bn_finalize more than 1024 rows at the bench batch (128): the stem conv and the 128-pixel-tiled conv epilogues of the
+    # 56x56 and 28x28 maps (stride-2 3x3 and 1x1 downsample convs); bn_apply / prelu_bwd_pass rows are capped at 1024 / 512
+    assert lib.fedfr_stem_stat_rows(128, 112) == K.stem_stat_rows(128, 112, 112) == 25088
+    assert [lib.fedfr_conv2d_stat_rows(128, hw, c) for hw, c in ((56, 64), (28, 128), (14, 256), (7, 512))] == [6272, 1568, 392, 98]
+
+
 def test_documented_options_exist_and_unknown_ones_are_errors(built_lib):
     """Every switch the header's fedfr_set_option comment names is one the library accepts (host-only state: no GPU needed), an unknown
     name is an error with a message, and setting a switch to its documented default is harmless."""
