@@ -1,6 +1,8 @@
 """Per-kernel parity of the HIP library (through the C ABI) against plain fp32 PyTorch CPU references
 of the same op on identical seeded inputs.  bf16 kernels are fed bf16-rounded inputs so the only
-differences are accumulation order and the final bf16 rounding of the output (tolerances state that)."""
+differences are accumulation order and the final bf16 rounding of the output (tolerances state that).
+The spot checks of SGD, fedavg_axpy, the PartialFC selection, contrastive, colflag, class_accumulate, the ROC histogram, preprocess_u8 and
+pad_input_nhwc below are kept as they are; tests/test_step_kernels_gpu.py holds the same kernels to bit-exact restatements at edge shapes."""
 import ctypes as C
 
 import numpy as np
