@@ -80,7 +80,6 @@ class sphere(IResNet):
         self._grads_live = False
         self._fwd_generation = 0
         self._bn_frozen = False
-        self.validation_fp32 = False
         self._anchor = torch.zeros(1, requires_grad=True)
         filt = self.filters
         for L in range(4):                                      # nn.Sequential(conv, PReLU, Block, ...) per stage (sphnet.py:49-56)
@@ -105,6 +104,16 @@ class sphere(IResNet):
                     v.fill_(0.25)
                 else:
                     v.zero_()
+
+    @property
+    def validation_fp32(self):
+        """the fp32 validation path (csrc/net_f32.hip) is IResNet's alone: it has no sphnet plan, and the library refuses one"""
+        return False
+
+    @validation_fp32.setter
+    def validation_fp32(self, on):
+        if on:
+            raise NotImplementedError("fedfr_amd sphnet: there is no fp32 validation path for a sphnet (validation_fp32 is IResNet's)")
 
     def freeze_BN(self, *a, **k):                               # no BatchNorm in this network
         pass

@@ -232,6 +232,24 @@ int fedfr_net_tensor_info(const fedfr_net_t* n, int i, char* name, int name_cap,
 int fedfr_net_act_info(const fedfr_net_t* n, int block, int which, long long* offset, int* rows, int* channels) {
   FEDFR_REQUIRE(n && offset && rows && channels, "net_act_info: null");
   const int B = n->B;
+  if (n->sph_type) {        // sphnet plan: block = unit index in forward order; which: 0 unit input, 1 c (conv out), 2 t (activated out), 3 dz (workspace)
+    std::vector<const SphUnit*> units;
+    for (const auto& st : n->sph) {
+      units.push_back(&st.head);
+      for (const auto& k : st.blocks) { units.push_back(&k.u1); units.push_back(&k.u2); }
+    }
+    FEDFR_REQUIRE(block >= 0 && block < (int)units.size(), "net_act_info: a sphnet plan has units 0..%d (got %d)", (int)units.size() - 1, block);
+    FEDFR_REQUIRE(which >= 0 && which <= 3, "net_act_info: sphnet selectors are 0 input, 1 c, 2 t, 3 dz (got %d)", which);
+    const SphUnit& u = *units[block];
+    const int Mi = B * u.conv.Hin * u.conv.Hin, Mo = B * u.conv.Hout * u.conv.Hout;
+    switch (which) {
+      case 0: *offset = u.in_off; *rows = Mi; *channels = u.conv.Cin; break;
+      case 1: *offset = u.c_off; *rows = Mo; *channels = u.conv.Cout; break;
+      case 2: *offset = u.t_off; *rows = Mo; *channels = u.conv.Cout; break;
+      default: *offset = (long long)(u.dz_off / 2); *rows = Mo; *channels = u.conv.Cout; break;
+    }
+    return FEDFR_OK;
+  }
   if (block < 0) {          // which: 0 stem conv out (c0), 1 stem activation (a0), 2 flattened bn2 output t [B][fc_in]
     FEDFR_REQUIRE(which >= 0 && which <= 2 && !n->block_only, "net_act_info: bad stem selector");
     if (which == 2) { *offset = n->t_off; *rows = B; *channels = n->fc_in; return FEDFR_OK; }

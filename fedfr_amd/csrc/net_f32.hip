@@ -328,11 +328,13 @@ int bn_backward(const Cx& c, const BnD& b, const float* alpha, long long alpha_o
 }
 }  // namespace
 
-size_t net_f32_arena_floats(const FedfrNet* n) { return make_layout(n).total; }
-size_t net_f32_ws_floats(const FedfrNet* n) { return ws_floats(make_layout(n)); }
+// a sphnet plan (net_create_sphere) has no fp32 validation path: its iresnet fields are unset, so it is refused before any layout is computed
+size_t net_f32_arena_floats(const FedfrNet* n) { return n->sph_type ? 0 : make_layout(n).total; }
+size_t net_f32_ws_floats(const FedfrNet* n) { return n->sph_type ? 0 : ws_floats(make_layout(n)); }
 
 int net_f32_forward(const FedfrNet* n, const float* x, const float* params, float* bufs, float* arena, float* ws, float* feats, int training,
                     hipStream_t st) {
+  FEDFR_REQUIRE(!(n && n->sph_type), "net_f32_forward: the fp32 validation path has no sphnet plan (iresnet plans only)");
   FEDFR_REQUIRE(n && x && params && bufs && arena && ws && feats, "net_f32_forward: null buffer");
   FEDFR_REQUIRE(!n->block_only, "net_f32_forward: whole-network plans only");
   FEDFR_REQUIRE(training == 0 || training == 1, "net_f32_forward: training must be 0 or 1");
@@ -374,6 +376,7 @@ int net_f32_forward(const FedfrNet* n, const float* x, const float* params, floa
 }
 
 int net_f32_backward(const FedfrNet* n, const float* dfeats, const float* params, float* arena, float* ws, float* grads, hipStream_t st) {
+  FEDFR_REQUIRE(!(n && n->sph_type), "net_f32_backward: the fp32 validation path has no sphnet plan (iresnet plans only)");
   FEDFR_REQUIRE(n && dfeats && params && arena && ws && grads, "net_f32_backward: null buffer");
   FEDFR_REQUIRE(!n->block_only, "net_f32_backward: whole-network plans only");
   const Layout L = make_layout(n);

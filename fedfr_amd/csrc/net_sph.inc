@@ -321,6 +321,9 @@ static int sph_backward(const FedfrNet* n, const float* dfeats, const float* par
   };
   // `g` = gradient wrt the current activation (G(cur)); `pend` = a dgrad output still to be added to it (folded into the next PReLU pass)
   const bf16_t* pend = nullptr;
+  // debug capture (fedfr_net_debug_capture): the gradient every block's u2 PReLU backward and every stage head's PReLU backward differentiates
+  // (16-bit NHWC, the pending branch gradient folded in), back to back in backward order; nothing is enqueued while the pointer is null
+  size_t dbg_off = 0;
   for (int s = (int)n->sph.size() - 1; s >= 0; --s) {
     const auto& stg = n->sph[s];
     for (int i = (int)stg.blocks.size() - 1; i >= 0; --i) {
@@ -328,6 +331,7 @@ static int sph_backward(const FedfrNet* n, const float* dfeats, const float* par
       // a_out = prelu2(conv2(t1)) + a_in: the block's output gradient g (+ the pending branch gradient of the block after it)
       if (pend) { FEDFR_TRY(prelu_bwd(k.u2, pend, G(cur), G(cur ^ 1))); cur ^= 1; pend = nullptr; }
       else FEDFR_TRY(prelu_bwd(k.u2, G(cur), nullptr, nullptr));
+      FEDFR_TRY(dbg_capture(G(cur), (size_t)B * stg.H * stg.H * stg.C, &dbg_off, st));      // the gradient u2's PReLU backward differentiated (pending branch folded in)
       bf16_t* dt1 = G(2);
       int f1 = 0;                                         // rows of u1's parameter sums when conv2's dgrad epilogue applied u1's backward itself
       if (dgrad_prelu_ok(k.u2.conv, k.u1)) FEDFR_TRY(dgrad_prelu(k.u2.conv, reinterpret_cast<const bf16_t*>(ws + k.u2.dz_off), k.u1, &f1));
@@ -354,6 +358,7 @@ static int sph_backward(const FedfrNet* n, const float* dfeats, const float* par
     // stage head: t = prelu(conv(x) + bias)
     if (pend) { FEDFR_TRY(prelu_bwd(stg.head, pend, G(cur), G(cur ^ 1))); cur ^= 1; pend = nullptr; }
     else FEDFR_TRY(prelu_bwd(stg.head, G(cur), nullptr, nullptr));
+    FEDFR_TRY(dbg_capture(G(cur), (size_t)B * stg.H * stg.H * stg.C, &dbg_off, st));
     fk.order(st, wst);
     FEDFR_TRY(unit_wgrad(stg.head));
     if (s > 0) {

@@ -102,7 +102,11 @@ int fedfr_net_set_dropout(fedfr_net_t* net, float p, unsigned long long seed, lo
 int fedfr_net_set_dropout_step(fedfr_net_t* net, unsigned long long step);
 /* debug (tests): while buf != NULL, fedfr_net_backward* copies the gradient entering every block (16-bit storage type, NHWC, last block first) and then
  * the gradient wrt the first block's input back to back into buf (caller-owned, `elems` 16-bit elements); NULL turns it off.  The one
- * exception to "no pointer is retained": clear it before freeing the buffer. */
+ * exception to "no pointer is retained": clear it before freeing the buffer.
+ * On a sphnet plan the copies are the gradient each PReLU backward pass of a block's second unit (u2) and of a stage head differentiates — 16-bit
+ * NHWC [B * H * H][C], AFTER the pending branch gradient of the block behind it has been folded in — back to back in backward order: per stage from
+ * the last to the first, its blocks from the last to the first, then its head (sphere20: 12 tensors, sphere64: 33).  With buf == NULL the pass
+ * enqueues exactly what it enqueues without the hook. */
 int fedfr_net_debug_capture(uint16_t* buf, size_t elems);
 enum {
   FEDFR_Q_PARAM_COUNT = 0,      /* fp32 elements: trainable region + frozen features.weight */
@@ -124,7 +128,12 @@ int fedfr_net_tensor_info(const fedfr_net_t* net, int i, char* name, int name_ca
  * block < 0: which = 0 stem conv output, 1 stem activation, 2 flattened bn2 output [B][fc_in] (NCHW order);
  * block >= 0: which = 0 block input, 1 bn1 out, 2 conv1 out, 3 prelu(bn2) out, 4 conv2 out, 5 downsample conv out
  * (offset -1 if the block has none), 6 block output, 7 gradient wrt the block input (fedfr_block_create plans only, after a backward).  An eval-mode forward (training = 0) applies the BatchNorms in the conv epilogues
- * where the kernel has one and then does not store the raw conv outputs (2, 4); fedfr_set_option("eval_fuse", 0) restores them. */
+ * where the kernel has one and then does not store the raw conv outputs (2, 4); fedfr_set_option("eval_fuse", 0) restores them.
+ * sphnet plan (fedfr_net_create_sphere): block = the UNIT index in forward order, 0 ... last (per stage: the stride-2 stage head, then u1, u2 of each
+ * residual block; sphere20 has 20 units, sphere64 62); which = 0 the unit's input (rows = B * Hin * Hin; unit 0: the image padded to 64 channels),
+ * 1 c, the raw conv output, 2 t = prelu(c + bias) (+ the block input for u2) — the LAST unit's t is stored NCHW-flat [B][512 * 49], the view the fc
+ * reads, not NHWC — and 3 dz, the gradient wrt c a backward pass leaves in the WORKSPACE (offset in 16-bit elements of `ws`, not of `act`);
+ * rows = B * Hout * Hout, channels = the stored width.  block < 0 and every other selector are argument errors on a sphnet plan. */
 int fedfr_net_act_info(const fedfr_net_t* net, int block, int which, long long* offset, int* rows, int* channels);
 /* refresh the 16-bit weight shadows (storage type: fp16 / bf16 per build) from fp32 params (after load_state_dict / an external optimizer step);
  * fwd_shadow_too = 0 when fedfr_sgd_step already wrote the mirror region. */
@@ -164,7 +173,9 @@ int fedfr_net_backward2_sgd_scaled(const fedfr_net_t* net, const float* x, const
  * checked with, and the yardstick that separates the product path's 16-bit storage noise from kernel error.  Slow by design (one launch per
  * operation, ~40 TFLOP/s); whole-network plans, dropout 0, training 0 / 1.  arena (fedfr_net_f32_arena_floats floats) keeps the
  * activations between forward and backward, ws (fedfr_net_f32_ws_floats floats) is scratch; params / bufs / grads are the plan's
- * ordinary fp32 buffers (grads assigned; running statistics updated by a training forward). */
+ * ordinary fp32 buffers (grads assigned; running statistics updated by a training forward).
+ * iresnet plans only: for a sphnet plan the two size queries return 0 and forward / backward are argument errors, checked before anything is
+ * laid out or launched. */
 size_t fedfr_net_f32_arena_floats(const fedfr_net_t* net);
 size_t fedfr_net_f32_ws_floats(const fedfr_net_t* net);
 int fedfr_net_f32_forward(const fedfr_net_t* net, const float* x, const float* params, float* bufs, float* arena, float* ws, float* feats,

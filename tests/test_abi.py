@@ -143,3 +143,54 @@ def test_hot_kernels_do_not_spill(built_lib):
                     bad.append((name, r))
     assert all(seen.values()), [h for h, n in seen.items() if not n]
     assert not bad, bad
+
+
+def test_sphere_plan_selectors_and_fp32_path_refusal(built_lib):
+    """Host-only: fedfr_net_act_info on a sphnet plan answers per UNIT (forward order: stage head, then u1, u2 of each block) with the selectors 0 input,
+    1 c, 2 t, 3 dz and refuses everything else with a message; the fp32 validation path has no sphnet plan — its size queries return 0 and its
+    forward / backward refuse a sphere plan before any layout computation or launch (dummy host pointers: the calls fail their checks first)."""
+    import ctypes as C
+    import sphnet_cases as SC
+    lib = built_lib.lib()
+    err_arg = int(re.search(r"#define FEDFR_ERR_ARG \((-?\d+)\)", open(HEADER).read()).group(1))
+    off, rows, ch = C.c_longlong(), C.c_int(), C.c_int()
+
+    def info(h, block, which):
+        rc = lib.fedfr_net_act_info(h, block, which, C.byref(off), C.byref(rows), C.byref(ch))
+        return rc, off.value, rows.value, ch.value
+    for type_, B in ((20, 5), (64, 1)):
+        h = lib.fedfr_net_create_sphere(type_, B)
+        assert h
+        net = SC.Net(type_, B)
+        prev_t, seen = None, set()
+        for u in net.units:
+            i0, c, t, dz = (info(h, u.idx, w) for w in range(4))
+            assert (i0[0], c[0], t[0], dz[0]) == (0, 0, 0, 0)
+            assert i0[2:] == (B * u.hin * u.hin, u.cin), (u.idx, i0)             # the stem input is the padded 64-channel image
+            assert c[2:] == t[2:] == dz[2:] == (B * u.hout * u.hout, u.cout)
+            assert i0[1] == (0 if prev_t is None else prev_t)                    # a unit reads the activation in front of it
+            assert c[1] % 8 == 0 and t[1] >= c[1] + c[2] * c[3] and dz[1] % 128 == 0
+            assert not {c[1], t[1]} & seen
+            seen |= {c[1], t[1]}
+            prev_t = t[1]
+        for block, which in ((-1, 0), (-1, 2), (len(net.units), 0), (0, 4), (0, -1), (3, 7)):
+            assert info(h, block, which)[0] == err_arg, (block, which)
+            assert b"net_act_info" in lib.fedfr_last_error_string()
+        assert lib.fedfr_net_f32_arena_floats(h) == 0 and lib.fedfr_net_f32_ws_floats(h) == 0
+        buf = (C.c_float * 64)()
+        assert lib.fedfr_net_f32_forward(h, buf, buf, buf, buf, buf, buf, 1, None) == err_arg
+        assert b"net_f32_forward" in lib.fedfr_last_error_string() and b"sphnet" in lib.fedfr_last_error_string()
+        assert lib.fedfr_net_f32_backward(h, buf, buf, buf, buf, buf, None) == err_arg
+        assert b"net_f32_backward" in lib.fedfr_last_error_string() and b"sphnet" in lib.fedfr_last_error_string()
+        lib.fedfr_net_destroy(h)
+
+
+def test_sphnet_refuses_the_fp32_validation_switch(built_lib):
+    """`validation_fp32` is IResNet's: a sphnet raises when it is set, before the library is ever called with a sphere plan."""
+    from fedfr_amd import backbones
+    m = backbones.sphnet(type=20)
+    assert m.validation_fp32 is False
+    m.validation_fp32 = False
+    with pytest.raises(NotImplementedError, match="validation"):
+        m.validation_fp32 = True
+    assert m.validation_fp32 is False
