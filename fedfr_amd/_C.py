@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(_HERE, os.environ.get("FEDFR_HIP_LIB_NAME", "libfedfr_hi
 
 _lib: Optional[C.CDLL] = None
 
-vp, i32, i64, u64, f32, f64, sz = C.c_void_p, C.c_int, C.c_longlong, C.c_ulonglong, C.c_float, C.c_double, C.c_size_t
+vp, i32, u32, i64, u64, f32, f64, sz = C.c_void_p, C.c_int, C.c_uint, C.c_longlong, C.c_ulonglong, C.c_float, C.c_double, C.c_size_t
 
 # name -> (restype, argtypes).  Must list every symbol include/fedfr_hip.h declares (tests/test_abi.py checks).
 SIGNATURES = {
@@ -153,6 +153,9 @@ SIGNATURES = {
     "fedfr_fedopt_sqnorm_workspace_bytes": (sz, [i32, sz]),
     "fedfr_fedopt_sqnorm": (i32, [vp, vp, vp, i32, sz, f32, vp, vp, vp, sz, vp]),
     "fedfr_fedopt_multi": (i32, [i32, vp, vp, vp, vp, i32, sz, vp, vp, vp, i32, i32, f32, f32, f32, f32, f32, f32, vp]),
+    "fedfr_philox_fill": (i32, [vp, sz, u64, u64, u32, u64, vp]),
+    "fedfr_gaussian_fill": (i32, [vp, sz, u64, u64, u32, u64, f32, i32, vp]),
+    "fedfr_dp_multi": (i32, [i32, vp, vp, vp, vp, i32, sz, vp, vp, vp, i32, i32, f32, f32, f32, f32, f32, f32, f32, u64, u64, u32, u64, vp]),
     "fedfr_robust_trimmed_mean": (i32, [vp, vp, i32, i32, sz, vp]),
     "fedfr_robust_pairdist_workspace_bytes": (sz, [i32, sz]),
     "fedfr_robust_pairdist": (i32, [vp, i32, sz, vp, vp, sz, vp]),

@@ -12,6 +12,7 @@
 #include "robust.h"
 #include "compress.h"
 #include "sparse.h"
+#include "dp.h"
 
 static thread_local char g_err[512] = "";
 extern int g_tn_use_tr;
@@ -882,6 +883,21 @@ int fedfr_fedopt_multi(int kind, float* x_out, const float* x, const float* cons
                        float one_minus_beta2, float tau, void* stream) {
   return optim_fedopt_multi(kind, x_out, x, xs, coef, k, n, m, v, delta_scratch, first, last, lr, beta1, one_minus_beta1, beta2, one_minus_beta2,
                             tau, ST(stream));
+}
+int fedfr_philox_fill(unsigned* dst, size_t n, unsigned long long seed, unsigned long long round, unsigned stream_id, unsigned long long offset,
+                      void* stream) {
+  return dp_philox_fill(dst, n, seed, round, stream_id, offset, ST(stream));
+}
+int fedfr_gaussian_fill(float* dst, size_t n, unsigned long long seed, unsigned long long round, unsigned stream_id, unsigned long long offset,
+                        float std, int accumulate, void* stream) {
+  return dp_gaussian_fill(dst, n, seed, round, stream_id, offset, std, accumulate, ST(stream));
+}
+int fedfr_dp_multi(int kind, float* x_out, const float* x, const float* const* xs, const float* coef, int k, size_t n, float* m, float* v,
+                   float* delta_scratch, int first, int last, float lr, float beta1, float one_minus_beta1, float beta2, float one_minus_beta2,
+                   float tau, float noise_std, unsigned long long seed, unsigned long long round, unsigned stream_id, unsigned long long offset,
+                   void* stream) {
+  return dp_multi(kind, x_out, x, xs, coef, k, n, m, v, delta_scratch, first, last, lr, beta1, one_minus_beta1, beta2, one_minus_beta2, tau,
+                  noise_std, seed, round, stream_id, offset, ST(stream));
 }
 int fedfr_robust_trimmed_mean(float* dst, const float* const* srcs, int k, int trim, size_t n, void* stream) {
   return robust_trimmed_mean(dst, srcs, k, trim, n, ST(stream));

@@ -4,6 +4,7 @@
 #include "optim.h"
 #include "gemm_dev.h"   // ProfScope
 #include "multi_state.h"
+#include "fedopt_step.h"
 
 // ---------------------------------------------------------------------------------------------------------
 // SGD: g += wd*p ; buf = first ? g : mu*buf + g ; p -= lr*buf ; optional bf16 shadow of the new p.
@@ -201,10 +202,7 @@ int optim_fedavg_i64(float* acc, const long long* src, float w, int n, int accum
 // The square root is __builtin_sqrtf, not __fsqrt_rn: this toolchain's __fsqrt_rn is the bare v_sqrt_f32 (1 ulp), while hipcc's default
 // (-fhip-fp32-correctly-rounded-divide-sqrt) expands __builtin_sqrtf and the division behind __fdiv_rn to correctly rounded sequences.
 // ---------------------------------------------------------------------------------------------------------
-enum { FEDOPT_AVGM = 0, FEDOPT_ADAGRAD = 1, FEDOPT_ADAM = 2, FEDOPT_YOGI = 3 };
-struct FedoptHyper {
-  float lr, b1, omb1, b2, omb2, tau;      // omb1 = 1 - beta1, omb2 = 1 - beta2: formed by the host in fp32
-};
+// (the kinds, FedoptHyper and the per-element step fedopt_one: fedopt_step.h, shared with dp.hip)
 
 template <int K>
 __global__ __launch_bounds__(MULTI_STATE_BLOCK) void fedopt_sqnorm_kernel(const float* __restrict__ x, StatePtrs<8> p, size_t n, double* __restrict__ part) {
@@ -275,25 +273,6 @@ int optim_fedopt_sqnorm(const float* x, const float* const* xs, const float* ws,
   hipLaunchKernelGGL(fedopt_sqnorm_final_kernel, dim3(1), dim3(512), 0, st, part, grid, k, wt, clip, sq, coef);
   FEDFR_LAUNCH_CHECK("fedopt_sqnorm_final");
   return FEDFR_OK;
-}
-
-template <int KIND>
-__device__ __forceinline__ void fedopt_one(float d, float x, float& m, float& v, float& xo, const FedoptHyper& h) {
-  if (KIND == FEDOPT_AVGM) {
-    m = __fadd_rn(__fmul_rn(h.b1, m), d);
-    xo = __fadd_rn(x, __fmul_rn(h.lr, m));
-    return;
-  }
-  m = __fadd_rn(__fmul_rn(h.b1, m), __fmul_rn(h.omb1, d));
-  const float d2 = __fmul_rn(d, d);
-  if (KIND == FEDOPT_ADAGRAD) v = __fadd_rn(v, d2);
-  if (KIND == FEDOPT_ADAM) v = __fadd_rn(__fmul_rn(h.b2, v), __fmul_rn(h.omb2, d2));
-  if (KIND == FEDOPT_YOGI) {
-    const float e = __fsub_rn(v, d2);
-    const float sg = e > 0.f ? 1.f : (e < 0.f ? -1.f : 0.f);      // sign(0) = 0
-    v = __fsub_rn(v, __fmul_rn(__fmul_rn(h.omb2, d2), sg));
-  }
-  xo = __fadd_rn(x, __fdiv_rn(__fmul_rn(h.lr, m), __fadd_rn(__builtin_sqrtf(v), h.tau)));
 }
 
 // first: Delta starts at 0 (else at scratch); last: the update is applied (else Delta goes to scratch and m, v, x are untouched).  xo may be x;

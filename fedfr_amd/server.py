@@ -4,7 +4,8 @@ xGMI when every client is its own rank (one client = one MI355X); the spread-out
 (reference server.py:48-63, :340-371) on one fused HIP kernel; and the round's 1:1 verification of the global model with its
 checkpoints (reference server.py:135-148).  Build extensions beyond the reference's FedAvg: the server optimisers (``FedOpt``), the
 robust rules (``FedRobust``: coordinate-wise trimmed mean / median, Krum / Multi-Krum) and compressed client uploads (``FedCompressed``:
-8 / 4-bit block-scaled deltas with error feedback; ``FedSparse``: top-k sparsified deltas with error feedback; see compress.py)."""
+8 / 4-bit block-scaled deltas with error feedback; ``FedSparse``: top-k sparsified deltas with error feedback; see compress.py) and
+client-level differential privacy (``FedDP``: clipped updates and Gaussian noise drawn on the device; see privacy.py)."""
 from __future__ import annotations
 
 import copy
@@ -265,6 +266,51 @@ def FedOpt(global_state, models: List[dict], weights: Sequence[float], opt: Serv
     _check_states(x, xs, "FedOpt")
     P = torch.empty_like(x)
     opt.apply(P, x, xs, opt.coefficients(x, xs, ws))
+    return FlatStateDict.from_flat((P, *_average_stats(models, ws)), models[0].table, models[0].layers)
+
+
+# ---- client-level differential privacy: csrc/dp.hip dp_multi_kernel (the clip: fedopt_sqnorm_kernel; mechanism and accounting: privacy.py)
+FEDOPT_PLAIN = 4
+
+
+def FedDP(global_state, models: List[dict], weights: Sequence[float], mech, opt: ServerOptimizer = None):
+    """One DP-FedAvg round: the PARAMETERS of the new global state are x + step(Σ_i c_i (x_i - x) + noise_std z) with x = ``global_state``'s
+    parameters, c_i = w_i min(1, clip_norm / ||x_i - x||) (``ServerOptimizer.coefficients``, as ``FedOpt``), w_i = ``weights[i]`` / Σ weights,
+    noise_std = ``mech.noise_std(w)`` and z the standard normal values of ``mech``'s device stream at its current round
+    (``privacy.GaussianMechanism``; the round counter advances by one per call).  ``opt=None``: step(Δ) = Δ, DP-FedAvg proper, no moments;
+    otherwise the step and the moments of ``opt`` (its ``clip_norm`` must be the mechanism's).  One streaming kernel, fedfr_dp_multi: the
+    noise is drawn and added inside the pass that reads the client states, ≤ 8 per pass; more chain through a scratch Δ buffer and the last
+    pass alone adds the noise.  BN running statistics and ``num_batches_tracked`` are averaged exactly as ``FedOpt`` averages them,
+    UN-NOISED: they are outside the mechanism.  Only GPU ``FlatStateDict``s are accepted."""
+    ws = _client_weights("FedDP", models, weights, also=[global_state])
+    x, xs = global_state.flat[0], [m.flat[0] for m in models]
+    _check_states(x, xs, "FedDP")
+    if opt is not None and np.float32(opt.clip_norm) != np.float32(mech.clip_norm):
+        raise ValueError("FedDP: the server optimiser clips at %r, the mechanism's sensitivity bound is clip_norm=%r" % (opt.clip_norm, mech.clip_norm))
+    clipper = opt
+    if clipper is None:                                # the clip's workspace and the chain's scratch live with the mechanism
+        clipper = getattr(mech, "_clipper", None)
+        if clipper is None or clipper.clip_norm != mech.clip_norm:
+            clipper = mech._clipper = ServerOptimizer("AVGM", clip_norm=mech.clip_norm)
+    coef = clipper.coefficients(x, xs, ws)
+    n = x.numel()
+    P = torch.empty_like(x)
+    if opt is not None:
+        opt._ensure(x)
+    if len(xs) > 8 and (clipper._scratch is None or clipper._scratch.numel() != n or clipper._scratch.device != x.device):
+        clipper._scratch = torch.empty(n, dtype=f32, device=x.device)
+    kind = FEDOPT_PLAIN if opt is None else FEDOPT_KINDS[opt.kind]
+    hyper = clipper.hyper()
+    std = mech.noise_std([float(np.float32(w)) for w in ws])
+    for c0 in range(0, len(xs), 8):
+        grp = xs[c0:c0 + 8]
+        _C.call("fedfr_dp_multi", kind, P.data_ptr(), x.data_ptr(), _C.ptr_array(grp), coef.data_ptr() + 4 * c0, len(grp), n,
+                None if opt is None else opt.m.data_ptr(), opt.v.data_ptr() if opt is not None and opt.adaptive else None,
+                clipper._scratch.data_ptr() if len(xs) > 8 else None, 1 if c0 == 0 else 0, 1 if c0 + 8 >= len(xs) else 0, *hyper,
+                std, mech.seed, mech.round, mech.stream_id, 0, _C.stream())
+    if opt is not None:
+        opt.rounds += 1
+    mech.advance()
     return FlatStateDict.from_flat((P, *_average_stats(models, ws)), models[0].table, models[0].layers)
 
 
@@ -533,7 +579,7 @@ def exchange_data_sizes(data_size: float, comm) -> float:
 
 
 def fedavg_all_reduce(backbone, data_size: float, total_size: float, comm=None, _axpy=_axpy, _i64=_i64_scale, _trunc=_i64_trunc,
-                      server_opt=None, prev_params=None):
+                      server_opt=None, prev_params=None, dp=None):
     """One client per rank: the FedAvg of a round as ONE collective (replaces the CPU loop of server.py:25-34 and the state_dict
     hand-offs of server.py:286,311).  The local state — parameters, BN running statistics and a float image of the
     ``num_batches_tracked`` counters, which are slices of one fp32 tensor (``IResNet.exchange_buffer``) — is scaled in place by the
@@ -550,8 +596,12 @@ def fedavg_all_reduce(backbone, data_size: float, total_size: float, comm=None, 
     the moments.  Still ONE collective.  Under a communicator that adds in ascending rank order the result is ``FedOpt`` of the same client
     states bit for bit, otherwise to the fp32 rounding of the collective's order.  ``server_opt.clip_norm > 0`` raises ``ValueError``: on
     this path the clip would have to be applied by every rank to its OWN delta before the exchange (one more norm pass per rank) — a
-    different algorithm from the clip ``FedOpt`` applies inside one aggregation, and not provided here."""
+    different algorithm from the clip ``FedOpt`` applies inside one aggregation, and not provided here.  ``dp`` (a
+    ``privacy.GaussianMechanism``) raises ``ValueError`` for the same reason: the mechanism needs that clip; use ``FedDP``."""
     from .comm import TorchDistComm
+    if dp is not None:
+        raise ValueError("fedavg_all_reduce: differential privacy is not supported on the all-reduce path (it needs every rank's own delta "
+                         "clipped before the exchange, a different algorithm); use FedDP")
     if isinstance(server_opt, RobustAggregator):
         raise ValueError("fedavg_all_reduce: a robust rule (%s) is not a sum and cannot ride a sum-all-reduce (every rank would need every "
                          "state: an all-gather, not provided here); use FedRobust" % server_opt.kind)
@@ -647,6 +697,8 @@ class Server(object):
         self.local_candidates = []
         self.server_opt = None                       # ServerOptimizer of aggr_alg FedAvgM / FedAdagrad / FedAdam / FedYogi (built in train())
         self.robust_agg = None                       # RobustAggregator of aggr_alg TrimmedMean / CoordMedian / Krum / MultiKrum (built in train())
+        self.dp_mech = self.dp_accountant = None     # privacy.GaussianMechanism / RDPAccountant of dp_noise_multiplier > 0 (built in train())
+        self.dp_epsilon = None                       # the (epsilon, dp_delta) guarantee after the rounds aggregated so far
 
     def enable_local_verification(self, callback, candidates=None):
         """reference server.py:105-108: ``callback`` (``eval_local.CallBack_LocalVerifi``) is handed to the clients whose ``cid`` is a
@@ -693,6 +745,32 @@ class Server(object):
         if aggr_alg not in ("FedAvg", "FedProx") and aggr_alg not in AGGR_ALG_KINDS and aggr_alg not in ROBUST_ALG_KINDS:      # before a round of client training is spent on it
             raise ValueError("Server.train: unknown aggr_alg %r (FedAvg, FedProx, %s, %s)"
                              % (aggr_alg, ", ".join(AGGR_ALG_KINDS), ", ".join(sorted(ROBUST_ALG_KINDS))))
+        dp_sigma = float(getattr(self.args, "dp_noise_multiplier", 0) or 0)      # client-level differential privacy (a build extension): absent or 0 = off
+        if dp_sigma:                                                         # what cannot be served: before anybody trains
+            clip_norm = float(getattr(self.args, "clip_norm", 0.0) or 0.0)
+            if not (dp_sigma > 0 and np.isfinite(dp_sigma)):
+                raise ValueError("Server.train: dp_noise_multiplier must be a finite number >= 0 (got %r)" % (self.args.dp_noise_multiplier,))
+            if not clip_norm > 0:
+                raise ValueError("Server.train: dp_noise_multiplier=%r needs clip_norm > 0: the clip is the sensitivity bound of the mechanism"
+                                 % (dp_sigma,))
+            if aggr_alg in ROBUST_ALG_KINDS:
+                raise ValueError("Server.train: dp_noise_multiplier=%r cannot be combined with aggr_alg=%r: a robust rule provides no per-client "
+                                 "norms to clip" % (dp_sigma, aggr_alg))
+            if getattr(self.args, "compress_bits", 0):
+                raise ValueError("Server.train: dp_noise_multiplier=%r cannot be combined with compress_bits=%d: the clip needs per-client norms "
+                                 "of the dequantised deltas, which are not provided" % (dp_sigma, self.args.compress_bits))
+            if getattr(self.args, "topk_ratio", 0):
+                raise ValueError("Server.train: dp_noise_multiplier=%r cannot be combined with topk_ratio=%r: the clip needs per-client norms of "
+                                 "the deltas, which are not provided" % (dp_sigma, self.args.topk_ratio))
+            if getattr(self.args, "return_all", False):
+                raise ValueError("Server.train: dp_noise_multiplier=%r cannot be combined with return_all: the averaged public class centres "
+                                 "would be released un-noised" % (dp_sigma,))
+            if self.dp_accountant is not None and self.dp_accountant.sigma != dp_sigma:
+                raise ValueError("Server.train: dp_noise_multiplier=%r after rounds accounted at %r: the accountant composes rounds of one noise "
+                                 "multiplier (set server.dp_accountant yourself to continue)" % (dp_sigma, self.dp_accountant.sigma))
+            dp_delta = float(getattr(self.args, "dp_delta", 1e-5))
+            if not 0.0 < dp_delta < 1.0:
+                raise ValueError("Server.train: dp_delta must be in (0, 1) (got %r)" % (dp_delta,))
         if aggr_alg in ROBUST_ALG_KINDS:                   # a client count the rule cannot serve: also before anybody trains
             if getattr(self, "robust_agg", None) is None or self.robust_agg.kind != aggr_alg:      # one aggregator per server (it keeps the distance workspace)
                 a = self.args
@@ -839,6 +917,8 @@ class Server(object):
                 if nb > 0:
                     self.logger.warning('Client %s sent %d non-finite elements (NaN in the aggregate there)'
                                         % (getattr(self.clients[order[j]], "cid", order[j]), nb))
+        elif dp_sigma:
+            aggr_state_dict = self._aggregate_dp(models, data_sizes, aggr_alg, dp_sigma, clip_norm, dp_delta)
         elif aggr_alg in ("FedAvg", "FedProx"):
             aggr_state_dict = FedPavg(models, data_sizes)
         elif aggr_alg in AGGR_ALG_KINDS:
@@ -855,6 +935,37 @@ class Server(object):
         self.federated_model.load_state_dict(aggr_state_dict)
         # the round / epoch counters belong to the driver, as in the reference (train.py:87-88): call step_round() after train()
         return self.avg_loss
+
+    def _aggregate_dp(self, models, data_sizes, aggr_alg, sigma, clip_norm, delta):
+        """the round's aggregation under ``dp_noise_multiplier`` > 0: ``FedDP`` with the server's mechanism (one per server: it holds the
+        round counter of the noise stream), then the accountant's step and the (epsilon, delta) after the rounds so far, on
+        ``self.dp_epsilon``.  q = len(current_client_list) / num_client; the rate only ever grows in the accountant (rdp is monotone in q,
+        so the largest rate of the run bounds every round)."""
+        import secrets
+        from .privacy import GaussianMechanism, RDPAccountant
+        if self.dp_mech is None or (self.dp_mech.noise_multiplier, self.dp_mech.clip_norm) != (sigma, clip_norm):
+            seed = getattr(self.args, "dp_seed", None)
+            rnd = 0 if self.dp_mech is None else self.dp_mech.round
+            self.dp_mech = GaussianMechanism(sigma, clip_norm, secrets.randbits(64) if seed is None else seed)
+            self.dp_mech.round = rnd
+        uniform = bool(getattr(self.args, "dp_uniform_weights", True))
+        if not uniform:
+            self.logger.warning('dp_uniform_weights is off: data-size weights are client-reported; the sensitivity bound clip_norm * max w_i '
+                                'holds for the weights of this round only')
+        weights = [1.0] * len(models) if uniform else data_sizes
+        opt = self.server_opt if aggr_alg in AGGR_ALG_KINDS else None
+        out = FedDP(flat_state_dict(self.federated_model), models, weights, self.dp_mech, opt)
+        q = len(self.current_client_list) / float(self.num_client)
+        acc = self.dp_accountant
+        if acc is None or q > acc.q:
+            steps = 0 if acc is None else acc.steps
+            acc = self.dp_accountant = RDPAccountant(q, sigma)
+            acc.steps = steps
+        acc.step()
+        self.dp_epsilon = acc.epsilon(delta)
+        self.logger.info('Differential privacy: (epsilon, delta) = (%.4f, %g) after %d rounds (noise multiplier %g, clip_norm %g, q = %g)'
+                         % (self.dp_epsilon, delta, acc.steps, sigma, clip_norm, acc.q))
+        return out
 
     @torch.no_grad()
     @_C.on_device(lambda self: self.device)

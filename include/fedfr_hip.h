@@ -635,6 +635,42 @@ int fedfr_fedopt_multi(int kind, float* x_out, const float* x, const float* cons
                        float one_minus_beta2, float tau, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * client-level differential privacy (DP-FedAvg, McMahan et al. 2018) — no reference counterpart.  fedfr_fedopt_sqnorm's clip bounds every
+ * client's contribution to clip (the sensitivity); here are the Gaussian noise, generated on the device, and the server step that adds it
+ * in the pass that already streams the client states.
+ * THE NOISE STREAM.  Element e = offset + j of the logical stream (seed, round, stream_id) is lane e % 4 of the Philox4x32-10 block
+ * (Salmon et al. 2011; multipliers 0xD2511F53 / 0xCD9E8D57, Weyl increments 0x9E3779B9 / 0xBB67AE85) with
+ *   key = (seed low 32 bits, seed high 32 bits),   counter = (blk low 32, blk high 32, round low 32, stream_id),   blk = e / 4 (64 bits)
+ * so a value depends on (seed, round, stream_id, e) only: not on the grid, on k, or on the number of passes of a chain.  Lanes (0, 1) and
+ * (2, 3) of a block (words r_a, r_b) are Box-Muller pairs, in fp32:
+ *   u1 = float((r_a >> 8) + 1) 2^-24 in (0, 1],  u2 = float(r_b >> 8) 2^-24 in [0, 1)   (both exact)
+ *   rad = sqrt(-2 log(u1));   z_even = rad cospi(2 u2);   z_odd = rad sinpi(2 u2)         (|z| <= sqrt(48 ln 2) = 5.77)
+ * offset must be a multiple of 4; with it a sharded or chunked buffer draws from one logical stream.  The n % 4 trailing elements take
+ * the leading lanes of the block behind the last whole one (the same indexing).  tests/dp_cases.py restates the words bit for bit and
+ * the Gaussian formula in fp64.
+ * ------------------------------------------------------------------------------------------------ */
+/* dst[j] = word (offset + j) of the stream, j < n.  dst 16-byte aligned; nothing is written behind n. */
+int fedfr_philox_fill(unsigned* dst, size_t n, unsigned long long seed, unsigned long long round, unsigned stream_id,
+                      unsigned long long offset, void* stream);
+/* dst[j] = (accumulate ? dst[j] : 0) + std * z(offset + j): one fp32 multiply and one fp32 add, nothing contracted.  std finite. */
+int fedfr_gaussian_fill(float* dst, size_t n, unsigned long long seed, unsigned long long round, unsigned stream_id,
+                        unsigned long long offset, float std, int accumulate, void* stream);
+/* fedfr_fedopt_multi with the Gaussian mechanism: on the LAST pass, after the sum over the clients and before the step,
+ *   D = D + noise_std * z(offset + j)                                                       (multiply, add)
+ * and one more kind, 4 = plain (DP-FedAvg proper):  x' = x + D, m and v neither read nor written (may be NULL).  Everything else —
+ * arguments, chaining through delta_scratch, aliasing, alignment, the order of operations — is fedfr_fedopt_multi's.  noise_std must be
+ * finite and >= 0; with noise_std = 0 nothing is drawn or added (no 0 * z), and kinds 0..3 ARE fedfr_fedopt_multi (the call is handed to
+ * it: its bits, its messages).  Every pass of a chain must be given the chain's (noise_std, seed, round, stream_id, offset); only the
+ * last pass uses them, so the noise is added exactly once (the entry point keeps no state: holding the earlier passes to it is the
+ * caller's part).  z is the value fedfr_gaussian_fill writes for the same (seed, round, stream_id, offset + j), bit for bit.
+ * FEDFR_ERR_ARG before anything is launched for what fedfr_fedopt_multi refuses, a noise_std that is negative or not finite, or an
+ * offset that is not a multiple of 4. */
+int fedfr_dp_multi(int kind, float* x_out, const float* x, const float* const* xs, const float* coef, int k, size_t n, float* m, float* v,
+                   float* delta_scratch, int first, int last, float lr, float beta1, float one_minus_beta1, float beta2,
+                   float one_minus_beta2, float tau, float noise_std, unsigned long long seed, unsigned long long round,
+                   unsigned stream_id, unsigned long long offset, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * robust aggregation — no reference counterpart: every rule above is a weighted sum, so one client that returns a poisoned, diverged or NaN
  * state moves (or wipes out) the global model.  Coordinate-wise trimmed mean / median (Yin et al., 2018) and Krum / Multi-Krum (Blanchard
  * et al., 2017) over k <= 32 flat fp32 client states (HOST arrays of k device pointers, as fedfr_fedavg_multi), as streaming passes.
