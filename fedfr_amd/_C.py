@@ -59,6 +59,7 @@ SIGNATURES = {
     "fedfr_conv2d_dgrad_bnbwd": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i32), vp]),
     "fedfr_conv2d_fwd_epilogue": (i32, [vp] * 10 + [i32, i32, i32, i32, vp]),
     "fedfr_conv2d_dgrad_papply": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, C.POINTER(i32), vp]),
+    "fedfr_conv2d_plan": (i32, [i32] * 8 + [C.POINTER(i32)] * 5),
     "fedfr_stream_create_low_priority": (i32, [vp]),
     "fedfr_stream_destroy": (i32, [vp]),
     "fedfr_conv2d_wgrad_ws_bytes": (sz, [i32, i32, i32, i32, i32, i32]),

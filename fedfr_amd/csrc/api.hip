@@ -338,25 +338,19 @@ int fedfr_conv2d_fwd(const uint16_t* x, const uint16_t* w, uint16_t* y, float* s
                      int ksize, int stride, void* stream) {
   FEDFR_TRY(conv_args_ok(batch, hin, cin, cout, ksize, stride));
   FEDFR_REQUIRE(x && w && y, "conv2d_fwd: null tensor");
-  const int hout = hin / stride;
-  GemmNT p{};
-  p.A = BF(x); p.B = BF(w); p.M = batch * hout * hout; p.N = cout; p.K = ksize * ksize * cin;
-  p.mode = 1; p.H = hin; p.W = hin; p.C = cin; p.Ho = hout; p.Wo = hout; p.S = ksize; p.stride = stride;
-  p.pad = ksize == 3 ? 1 : 0; p.up = 1; p.Cb = BFM(y); p.ldc = cout; p.stats = stats;
+  GemmNT p = conv_fwd_problem(batch, hin, cin, cout, ksize, stride);
+  p.A = BF(x); p.B = BF(w); p.Cb = BFM(y); p.stats = stats;
   return gemm_nt_launch(p, 1, ST(stream));
 }
 int fedfr_conv2d_fwd_moments(const uint16_t* x, const uint16_t* w, uint16_t* y, int batch, int hin, int cin, int cout, const uint16_t* other,
                              float* partials, int* rows, void* stream) {
   FEDFR_TRY(conv_args_ok(batch, hin, cin, cout, 3, 1));
   FEDFR_REQUIRE(x && w && y && other && partials && rows, "conv2d_fwd_moments: null argument");
-  GemmNT p{};
-  p.A = BF(x); p.B = BF(w); p.M = batch * hin * hin; p.N = cout; p.K = 9 * cin;
-  p.mode = 1; p.H = hin; p.W = hin; p.C = cin; p.Ho = hin; p.Wo = hin; p.S = 3; p.stride = 1; p.pad = 1; p.up = 1;
-  p.Cb = BFM(y); p.ldc = cout;
+  GemmNT p = conv_fwd_problem(batch, hin, cin, cout, 3, 1);
+  p.A = BF(x); p.B = BF(w); p.Cb = BFM(y);
   p.bx = BF(other); p.bmean = partials; p.brstd = partials;   // (any readable fp32 array of >= cout elements: read, never used in this mode)
   p.bpart = partials; p.bmom = 1;
-  *rows = 0;
-  p.bwd_fused = rows;
+  *rows = gemm_nt_plan(p, 1).part_rows;
   return gemm_nt_launch(p, 1, ST(stream));
 }
 int fedfr_bn_apply2_sliced_ok(int M, int C, int rows) { return ew_bn_apply2_sliced_ok(M, C, rows) ? 1 : 0; }
@@ -379,15 +373,8 @@ int fedfr_conv2d_dgrad(const uint16_t* dy, const uint16_t* wd, uint16_t* dx, int
                        int stride, void* stream) {
   FEDFR_TRY(conv_args_ok(batch, hin, cin, cout, ksize, stride));
   FEDFR_REQUIRE(dy && wd && dx, "conv2d_dgrad: null tensor");
-  const int hout = hin / stride;
-  GemmNT p{};
-  p.A = BF(dy); p.B = BF(wd); p.N = cin; p.K = ksize * ksize * cout; p.Cb = BFM(dx); p.ldc = cin;
-  if (ksize == 1) {   // compact result at the OUTPUT resolution: dx[m_out][cin]
-    p.mode = 0; p.M = batch * hout * hout; p.lda = cout;
-  } else {
-    p.mode = 1; p.M = batch * hin * hin; p.H = hout; p.W = hout; p.C = cout; p.Ho = hin; p.Wo = hin; p.S = 3;
-    p.stride = 1; p.pad = 1; p.up = stride;
-  }
+  GemmNT p = conv_dgrad_problem(batch, hin, cin, cout, ksize, stride);      // (1x1: compact result at the OUTPUT resolution, dx[m_out][cin])
+  p.A = BF(dy); p.B = BF(wd); p.Cb = BFM(dx);
   return gemm_nt_launch(p, 1, ST(stream));
 }
 int fedfr_conv2d_dgrad_bnbwd(const uint16_t* dy, const uint16_t* wd, uint16_t* dx, int batch, int hin, int cin, int cout, int ksize,
@@ -395,14 +382,10 @@ int fedfr_conv2d_dgrad_bnbwd(const uint16_t* dy, const uint16_t* wd, uint16_t* d
                              const float* beta, const float* alpha, float* partials, int* fused_rows, void* stream) {
   FEDFR_TRY(conv_args_ok(batch, hin, cin, cout, ksize, stride));
   FEDFR_REQUIRE(dy && wd && dx && bn_x && mean && rstd && partials && fused_rows && ksize == 3, "conv2d_dgrad_bnbwd: bad args");
-  const int hout = hin / stride;
-  GemmNT p{};
-  p.A = BF(dy); p.B = BF(wd); p.N = cin; p.K = 9 * cout; p.Cb = BFM(dx); p.ldc = cin;
-  p.mode = 1; p.M = batch * hin * hin; p.H = hout; p.W = hout; p.C = cout; p.Ho = hin; p.Wo = hin; p.S = 3;
-  p.stride = 1; p.pad = 1; p.up = stride;
+  GemmNT p = conv_dgrad_problem(batch, hin, cin, cout, 3, stride);
+  p.A = BF(dy); p.B = BF(wd); p.Cb = BFM(dx);
   p.bx = BF(bn_x); p.bmean = mean; p.brstd = rstd; p.bgamma = gamma; p.bbeta = beta; p.balpha = alpha; p.bpart = partials;
-  *fused_rows = 0;
-  p.bwd_fused = fused_rows;
+  *fused_rows = gemm_nt_plan(p, 1).part_rows;
   return gemm_nt_launch(p, 1, ST(stream));
 }
 // the eval-mode output epilogue of the LDS-DMA conv kernels, one launch (the GemmNT of net.hip: conv_fwd_ep)
@@ -411,16 +394,14 @@ int fedfr_conv2d_fwd_epilogue(const uint16_t* x, const uint16_t* w, uint16_t* y,
                               int cout, void* stream) {
   FEDFR_TRY(conv_args_ok(batch, hin, cin, cout, 3, 1));
   FEDFR_REQUIRE(x && w && y && scale && shift && (!y2 || (scale2 && shift2)), "conv2d_fwd_epilogue: null argument");
-  if (!gemm_nt_conv_epilogue_ok(hin, cin, cout, batch * hin * hin, 3, 1)) {
+  GemmNT p = conv_fwd_problem(batch, hin, cin, cout, 3, 1);
+  p.A = BF(x); p.B = BF(w); p.Cb = BFM(y);
+  p.esc = scale; p.esh = shift; p.ealpha = alpha; p.eadd = BF(add);
+  if (y2) { p.Cb2 = BFM(y2); p.esc2 = scale2; p.esh2 = shift2; }
+  if (!gemm_nt_plan(p, 1).out_epilogue) {
     fedfr_set_error("conv2d_fwd_epilogue: no kernel with the output epilogue serves batch=%d hin=%d cin=%d cout=%d", batch, hin, cin, cout);
     return FEDFR_ERR_UNSUPPORTED;
   }
-  GemmNT p{};
-  p.A = BF(x); p.B = BF(w); p.M = batch * hin * hin; p.N = cout; p.K = 9 * cin;
-  p.mode = 1; p.H = hin; p.W = hin; p.C = cin; p.Ho = hin; p.Wo = hin; p.S = 3; p.stride = 1; p.pad = 1; p.up = 1;
-  p.Cb = BFM(y); p.ldc = cout;
-  p.esc = scale; p.esh = shift; p.ealpha = alpha; p.eadd = BF(add);
-  if (y2) { p.Cb2 = BFM(y2); p.esc2 = scale2; p.esh2 = shift2; }
   return gemm_nt_launch(p, 1, ST(stream));
 }
 // the PReLU-apply dgrad (GemmNT::bmom == 2), one launch (the GemmNT of net_sph.inc: dgrad_prelu)
@@ -428,18 +409,35 @@ int fedfr_conv2d_dgrad_papply(const uint16_t* dy, const uint16_t* wd, uint16_t* 
                               const float* bias, const float* alpha, float* partials, int* rows, void* stream) {
   FEDFR_TRY(conv_args_ok(batch, hin, cin, cout, 3, 1));
   FEDFR_REQUIRE(dy && wd && dz && act_x && alpha && partials && rows, "conv2d_dgrad_papply: null argument");
-  *rows = 0;
-  if (!((hin == 14 || hin == 28) && gemm_nt_conv_epilogue_ok(hin, cout, cin, batch * hin * hin, 3, 1))) {
+  GemmNT p = conv_dgrad_problem(batch, hin, cin, cout, 3, 1);
+  p.A = BF(dy); p.B = BF(wd); p.Cb = BFM(dz);
+  p.bx = BF(act_x); p.bbeta = bias; p.balpha = alpha;
+  p.bmean = alpha; p.brstd = alpha;                     // (read, never used in this mode)
+  p.bpart = partials; p.bmom = 2;
+  *rows = gemm_nt_plan(p, 1).part_rows;
+  if (*rows == 0) {
     fedfr_set_error("conv2d_dgrad_papply: no kernel with the PReLU-apply epilogue serves batch=%d hin=%d cin=%d cout=%d", batch, hin, cin, cout);
     return FEDFR_ERR_UNSUPPORTED;
   }
-  GemmNT p{};
-  p.A = BF(dy); p.B = BF(wd); p.N = cin; p.K = 9 * cout; p.Cb = BFM(dz); p.ldc = cin;
-  p.mode = 1; p.M = batch * hin * hin; p.H = hin; p.W = hin; p.C = cout; p.Ho = hin; p.Wo = hin; p.S = 3; p.stride = 1; p.pad = 1; p.up = 1;
-  p.bx = BF(act_x); p.bbeta = bias; p.balpha = alpha;
-  p.bmean = alpha; p.brstd = alpha;                     // (read, never used in this mode)
-  p.bpart = partials; p.bmom = 2; p.bwd_fused = rows;
   return gemm_nt_launch(p, 1, ST(stream));
+}
+// host-only: what gemm_nt_plan answers for a conv forward / dgrad problem with the wanted epilogues (include/fedfr_hip.h)
+int fedfr_conv2d_plan(int batch, int hin, int cin, int cout, int ksize, int stride, int dgrad, int want, int* profile_slot, int* stat_rows,
+                      int* stat_rows_live, int* part_rows, int* out_epilogue) {
+  FEDFR_TRY(conv_args_ok(batch, hin, cin, cout, ksize, stride));
+  FEDFR_REQUIRE(profile_slot && stat_rows && stat_rows_live && part_rows && out_epilogue, "conv2d_plan: null argument");
+  FEDFR_REQUIRE(want >= 0 && want < 32 && !(want & (dgrad ? 1 | 4 | 16 : 2 | 8)) && !((want & 2) && (want & 8)) && (!(want & (2 | 4 | 8)) || ksize == 3),
+                "conv2d_plan: want=%d is not a set of epilogues a %s of this filter has", want, dgrad ? "dgrad" : "forward conv");
+  GemmNT p = dgrad ? conv_dgrad_problem(batch, hin, cin, cout, ksize, stride) : conv_fwd_problem(batch, hin, cin, cout, ksize, stride);
+  static float f32s[1];                                 // placeholders: the plan reads which pointers are set, never through them
+  static bf16_t h16s[1];
+  p.A = p.B = p.Cb = h16s;
+  if (want & 1) p.stats = f32s;
+  if (want & (2 | 4 | 8)) { p.bx = h16s; p.bmean = p.brstd = p.balpha = p.bpart = f32s; p.bmom = (want & 4) ? 1 : (want & 8) ? 2 : 0; }
+  if (want & 16) p.esc = p.esh = f32s;
+  const NtPlan pl = gemm_nt_plan(p, 1);
+  *profile_slot = pl.profile_slot; *stat_rows = pl.stat_rows; *stat_rows_live = pl.stat_rows_live; *part_rows = pl.part_rows; *out_epilogue = pl.out_epilogue;
+  return FEDFR_OK;
 }
 size_t fedfr_conv2d_wgrad_ws_bytes(int batch, int hin, int cin, int cout, int ksize, int stride) {
   const int hout = hin / (stride > 0 ? stride : 1);
@@ -450,35 +448,15 @@ int fedfr_conv2d_wgrad(const uint16_t* x, const uint16_t* dy, float* dw, void* w
                        int cout, int ksize, int stride, void* stream) {
   FEDFR_TRY(conv_args_ok(batch, hin, cin, cout, ksize, stride));
   FEDFR_REQUIRE(x && dy && dw, "conv2d_wgrad: null tensor");
-  const int hout = hin / stride;
-  GemmTN p{};
-  p.P = BF(dy); p.Q = BF(x); p.Kp = batch * hout * hout; p.NI = cout; p.NJ = ksize * ksize * cin;
-  p.mode = 1; p.H = hin; p.W = hin; p.C = cin; p.Ho = hout; p.Wo = hout; p.S = ksize; p.stride = stride;
-  p.pad = ksize == 3 ? 1 : 0; p.ldp = cout; p.use_tr = g_tn_use_tr;
-  const int splits = gemm_tn_pick_splits(p.Kp, p.NI, p.NJ, p.C, p.Wo, p.stride);
-  if (splits == 1) {
-    p.out = dw;
-    return gemm_tn_launch(p, 1, ST(stream));
-  }
-  if (!ws || ws_bytes < (size_t)splits * p.NI * p.NJ * sizeof(float)) {
-    fedfr_set_error("conv2d_wgrad: workspace too small (%zu bytes)", ws_bytes);
-    return FEDFR_ERR_WORKSPACE;
-  }
-  p.out = (float*)ws;
-  FEDFR_TRY(gemm_tn_launch(p, splits, ST(stream)));
-  return ew_reduce_slabs(dw, (const float*)ws, splits, (size_t)p.NI * p.NJ, nullptr, 0, ST(stream));
+  GemmTN p = conv_wgrad_problem(batch, hin, cin, cout, ksize, stride);
+  p.P = BF(dy); p.Q = BF(x);
+  return conv_wgrad_run(p, dw, (float*)ws, ws_bytes / sizeof(float), ST(stream));
 }
 int fedfr_conv2d_wgrad_pair(const uint16_t* xa, const uint16_t* dya, float* dwa, const uint16_t* xb, const uint16_t* dyb, float* dwb,
                             void* ws, size_t ws_bytes, int batch, int hin, int cin, int cout, int ksize, int stride, void* stream) {
   FEDFR_TRY(conv_args_ok(batch, hin, cin, cout, ksize, stride));
   FEDFR_REQUIRE(xa && dya && dwa && xb && dyb && dwb, "conv2d_wgrad_pair: null tensor");
-  const int hout = hin / stride;
-  GemmTN p{};
-  p.Kp = batch * hout * hout; p.NI = cout; p.NJ = ksize * ksize * cin;
-  p.mode = 1; p.H = hin; p.W = hin; p.C = cin; p.Ho = hout; p.Wo = hout; p.S = ksize; p.stride = stride;
-  p.pad = ksize == 3 ? 1 : 0; p.ldp = cout; p.use_tr = g_tn_use_tr;
-  const int splits = gemm_tn_pick_splits(p.Kp, p.NI, p.NJ, p.C, p.Wo, p.stride);
-  const size_t one = (size_t)splits * p.NI * p.NJ * sizeof(float);
+  GemmTN p = conv_wgrad_problem(batch, hin, cin, cout, ksize, stride);
   GemmTN a = p, b = p;
   a.P = BF(dya); a.Q = BF(xa); b.P = BF(dyb); b.Q = BF(xb);
   if (gemm_tn_w9pair_ok(a, b)) {                            // 3x3 / stride-1 layers the paired nine-tap kernel takes (wgrad9p.hip)

@@ -451,25 +451,33 @@ __global__ __launch_bounds__(256) void conv3x3_c64p_kernel(GemmNT p, int ntiles,
   }
 }
 
-template <int W_, int R_, bool STATS, int BWD>
-int launch_c64p(GemmNT p, hipStream_t st) {
-  constexpr int PT = R_ * W_, PWL = (W_ + 2 + 7) & ~7, NPA = ((R_ + 2) * PWL + 7) / 8;
-  constexpr size_t lds = 2 * (size_t)NPA * 1024 + (size_t)PT * (64 * 2 + 16);
-  const int ntiles = p.M / PT;
+// 224-pixel tiles dealt out evenly to at most one workgroup per CU (256 CUs when there is no device to ask): tiles per workgroup -> *per_wg, workgroups returned
+static int c64p_deal(int ntiles, int* per_wg = nullptr) {
   int dev = 0, cus = 256;
   if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const int per_wg = ceil_div(ntiles, std::min(ntiles, cus));
-  const int grid = ceil_div(ntiles, per_wg);
+  const int per = ceil_div(ntiles, std::min(ntiles, cus));
+  if (per_wg) *per_wg = per;
+  return ceil_div(ntiles, per);
+}
+
+template <int W_, int R_, bool STATS, int BWD>
+int launch_c64p(GemmNT p, const NtPlan& plan, hipStream_t st) {
+  constexpr int PT = R_ * W_, PWL = (W_ + 2 + 7) & ~7, NPA = ((R_ + 2) * PWL + 7) / 8;
+  static_assert(PT == 224, "c64p_deal and conv_c64p_grid count 224-pixel tiles");
+  constexpr size_t lds = 2 * (size_t)NPA * 1024 + (size_t)PT * (64 * 2 + 16);
+  const int ntiles = p.M / PT;
+  int per_wg;
+  const int grid = c64p_deal(ntiles, &per_wg);
   const int stat_rows = gemm_nt_stat_rows(p.M, p.N);
   FEDFR_REQUIRE(!p.stats || 2 * grid <= stat_rows, "conv3x3_c64p: %d partial rows do not fit gemm_nt_stat_rows = %d", 2 * grid, stat_rows);
+  FEDFR_REQUIRE(plan.stat_rows_live == 2 * grid && plan.part_rows == (BWD ? grid : 0), "conv3x3_c64p: the plan counts %d statistics / %d partial rows, the launch has %d workgroups",
+                plan.stat_rows_live, plan.part_rows, grid);
   static PerDeviceOnce attr_once;     // hipFuncSetAttribute is per device (a Server process may drive several)
   attr_once.run([&] {
     hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_c64p_kernel<W_, R_, STATS, BWD>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   });
-  if (BWD) {
+  if (BWD)                                                // one partial row [3][64] per workgroup
     FEDFR_REQUIRE(p.bx && p.bmean && p.brstd && (BWD == 1 || (p.bgamma && p.bbeta && p.balpha)), "conv3x3_c64p: the fused BatchNorm-backward reduction needs bx / mean / rstd (and gamma / beta / alpha with PReLU)");
-    if (p.bwd_fused) *p.bwd_fused = grid;                  // one partial row [3][64] per workgroup
-  }
   ProfScope prof(15, 2.0 * p.M * p.N * (double)p.K, st, gemm_nt_alg_bytes(p, 1));           // slot 15: the 64-channel 3x3 layers (56x56, 112x112)
   hipLaunchKernelGGL((conv3x3_c64p_kernel<W_, R_, STATS, BWD>), dim3(grid), dim3(256), lds, st, p, ntiles, per_wg, stat_rows);
   FEDFR_LAUNCH_CHECK("conv3x3_c64p");
@@ -477,24 +485,18 @@ int launch_c64p(GemmNT p, hipStream_t st) {
 }
 }  // namespace
 
-int conv_c64p_grid(int M) {                 // workgroups of a launch over M output pixels (224-pixel tiles dealt out evenly, at most one workgroup per CU)
-  const int ntiles = M / 224;
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const int per_wg = ceil_div(ntiles, std::min(ntiles, cus));
-  return ceil_div(ntiles, per_wg);
-}
+int conv_c64p_grid(const GemmNT& p) { return c64p_deal(p.M / 224); }
 bool conv_c64p_applies(const GemmNT& p) {
   return g_conv_c64p && p.mode == 1 && p.S == 3 && p.C == 64 && p.N == 64 && p.K == 576 && p.stride == 1 && p.pad == 1 && p.up == 1 && p.H == p.W &&
          (p.W == 112 || p.W == 56) && p.Ho == p.H && p.Wo == p.W && p.M % (p.W * p.W) == 0 && p.Cb && p.ldc == 64 && !p.Cf && !(p.bpart && p.stats) &&
          !p.esc && !p.eadd && !p.Cb2 && !p.par_on && !p.bmom;
 }
-int launch_conv_c64p(GemmNT p, hipStream_t st) {
+int launch_conv_c64p(GemmNT p, const NtPlan& plan, hipStream_t st) {
   FEDFR_REQUIRE(conv_c64p_applies(p), "conv3x3_c64p: unsupported shape");
   if (p.bpart) {
-    if (p.balpha) return p.W == 112 ? launch_c64p<112, 2, false, 2>(p, st) : launch_c64p<56, 4, false, 2>(p, st);
-    return p.W == 112 ? launch_c64p<112, 2, false, 1>(p, st) : launch_c64p<56, 4, false, 1>(p, st);
+    if (p.balpha) return p.W == 112 ? launch_c64p<112, 2, false, 2>(p, plan, st) : launch_c64p<56, 4, false, 2>(p, plan, st);
+    return p.W == 112 ? launch_c64p<112, 2, false, 1>(p, plan, st) : launch_c64p<56, 4, false, 1>(p, plan, st);
   }
-  if (p.stats) return p.W == 112 ? launch_c64p<112, 2, true, 0>(p, st) : launch_c64p<56, 4, true, 0>(p, st);
-  return p.W == 112 ? launch_c64p<112, 2, false, 0>(p, st) : launch_c64p<56, 4, false, 0>(p, st);
+  if (p.stats) return p.W == 112 ? launch_c64p<112, 2, true, 0>(p, plan, st) : launch_c64p<56, 4, true, 0>(p, plan, st);
+  return p.W == 112 ? launch_c64p<112, 2, false, 0>(p, plan, st) : launch_c64p<56, 4, false, 0>(p, plan, st);
 }

@@ -1020,7 +1020,7 @@ __global__ __launch_bounds__(128 * WN) void conv3x3_glds_kernel(GemmNT p, int st
 }
 
 template <int W_, int R_, int NPA, int WN, bool FUSED, int BN_ = 128, bool ONECHUNK = false, int TPW = 1, bool PAPPLY = false>
-static int launch_glds(GemmNT p, hipStream_t st) {
+static int launch_glds(GemmNT p, const NtPlan& plan, hipStream_t st) {
   constexpr int PT = R_ * W_;
   FEDFR_REQUIRE(p.N % BN_ == 0 && (ONECHUNK ? p.C == 64 : p.C % 128 == 0) && p.H == W_ && p.W == W_ && p.M % (W_ * W_) == 0 && p.K == 9 * p.C && p.ldc % 8 == 0,
                 "conv3x3_glds: unsupported shape (N=%d C=%d H=%d W=%d M=%d)", p.N, p.C, p.H, p.W, p.M);
@@ -1031,7 +1031,7 @@ static int launch_glds(GemmNT p, hipStream_t st) {
     FEDFR_REQUIRE(!p.stats, "conv3x3_glds: a fused-epilogue launch leaves reduction rows (bpart), not forward statistics");
     FEDFR_REQUIRE(p.bmom != 2 || p.balpha, "conv3x3_glds: the PReLU-apply epilogue needs the slopes");
     FEDFR_REQUIRE(p.bmom != 2 || PAPPLY, "conv3x3_glds: the PReLU-apply epilogue lives in the PAPPLY instantiations");
-    if (p.bwd_fused) *p.bwd_fused = p.M / PT / TPW;
+    FEDFR_REQUIRE(plan.part_rows == p.M / PT / TPW, "conv3x3_glds: the plan counts %d partial rows, the launch leaves %d", plan.part_rows, p.M / PT / TPW);
   }
   p.nbn = p.N / BN_;
   FEDFR_REQUIRE((p.M / PT) % TPW == 0, "conv3x3_glds: %d tiles do not split into groups of %d", p.M / PT, TPW);

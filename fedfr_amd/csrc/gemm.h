@@ -27,18 +27,17 @@ struct GemmNT {
   unsigned a_bytes, b_bytes;   // buffer-descriptor ranges (filled by the launcher)
   // optional fused BatchNorm-backward reduction on the OUTPUT tile (dgrad launches): with dy = this GEMM's bf16
   // output and x = the BN input [M][N], writes per-M-tile partials [ceil(M/128)][3][N] of (sum dz, sum dz*xhat,
-  // sum dy*min(z,0)) exactly like ew_bn_bwd_reduce.  Only the halo2 kernel implements it: *bwd_fused (host) is set
-  // to the number of partial rows when it did, left untouched otherwise.
+  // sum dy*min(z,0)) exactly like ew_bn_bwd_reduce.  Only some kernels implement it: NtPlan::part_rows (below) is the number of
+  // partial rows the chosen one leaves, 0 if it has no such epilogue.
   const bf16_t* bx;
   const float *bmean, *brstd, *bgamma, *bbeta, *balpha;
   float* bpart;
-  int* bwd_fused;
   // bmom != 0 (forward launches, round 3): the same epilogue leaves RAW moments of the output y against a same-shape tensor bx instead —
   // rows [3][N] of (sum y, sum y * bx, sum y * y) — from which the pass that follows derives the statistics of y AND of
   // bn(y) + bx (the next block's bn1) without a pass over that sum (net.hip, conv2 of a residual block).  bmean / brstd: any readable [N].
   int bmom;               // 2 (dgrad launches, sphnet): a bare PReLU(+bias) precedes the conv — the OUTPUT becomes dz = dy * prelu'(bx + bias) (bias in
                           // bbeta or null, slopes in balpha), rows [3][N] = (sum dz, sum dy z over z <= 0, same): the PReLU's backward pass disappears
-  // stride-2 dgrad by output-parity class (gemm.hip: nt_launch_parity): this launch computes the output pixels (2 h2 + par_h, 2 w2 + par_w)
+  // stride-2 dgrad by output-parity class (gemm.hip: nt_parity_problem): this launch computes the output pixels (2 h2 + par_h, 2 w2 + par_w)
   // of a [img][outH][outW] map with only the filter taps that reach a real (non-inserted-zero) input: 1, 2, 2 or 4 of the 9
   int par_on, par_h, par_w, outH, outW;
   // optional OUTPUT epilogue of the LDS-DMA conv kernels (eval-mode forward, where the BatchNorm that follows a conv is a known
@@ -73,10 +72,64 @@ struct GemmTN {
 
 // rows of partial stats the NT kernel writes for a given M (needed to size / finalize)
 int gemm_nt_stat_rows(int M, int N);
-bool gemm_nt_fused28_two_tiles(int M);   // a fused (BatchNorm-backward reduction) 28x28 dgrad of M output pixels leaves M / 392 partial rows
-int gemm_nt_stat_rows_live(int M, int N, int C, int W, int ksize, int stride);   // leading rows that are not zero filler
-// shapes whose conv runs on an LDS-DMA kernel that implements the output epilogue (esc / eadd / Cb2)
-bool gemm_nt_conv_epilogue_ok(int W, int C, int N, int M, int ksize, int stride);
+
+// Which kernel serves an NT problem and what callers must know before they launch it.  gemm_nt_plan is the ONLY place that decides:
+// gemm_nt_launch switches on its answer, and the launchers that know their own row count check it against the plan's.
+enum class NtKernel {
+  c64p,                                                  // conv_c64p.hip: persistent 64 -> 64 channel kernel (56x56, 112x112)
+  glds_w112, glds_w56, glds_w56_c64_n128, glds_w56_c128_n64, glds8_w14, glds8_w28, glds8_w28_stats,      // plain LDS-DMA instantiations
+  glds8_fused_w14, glds8_fused_w28, glds8_fused_w28s,    // ... with the BatchNorm-backward / raw-moment reduction epilogue (bpart)
+  glds8_papply_w14, glds8_papply_w28, glds8_papply_w28s, // ... with sphnet's PReLU-apply epilogue (bmom == 2)
+  ring,                                                  // gemm_nt_glds.hip: LDS-DMA ring GEMM
+  nt_128x128, nt_128x64, nt_64x128, nt_64x64,            // the generic gather GEMM
+};
+struct NtPlan {
+  NtKernel kernel;
+  int profile_slot;       // slot the chosen launcher records under (gemm.hip)
+  int stat_rows;          // rows a statistics buffer / finalize is sized for (gemm_nt_stat_rows)
+  int stat_rows_live;     // leading rows of those that carry data when the launch writes statistics (the rest are zero filler)
+  int part_rows;          // rows the bpart epilogue writes; 0: the chosen kernel has no such epilogue for the requested mode (bmom)
+  bool out_epilogue;      // the chosen kernel implements the output epilogue (esc / eadd / Cb2)
+};
+// pure host function; a stride-2 3x3 dgrad by output-parity class (option "dgrad_parity") is planned as the per-class problem it is launched as
+NtPlan gemm_nt_plan(const GemmNT& p, int splits);
+
+// conv problems from geometry alone; callers set the operand, output and epilogue pointers on the result
+inline GemmNT conv_fwd_problem(int batch, int hin, int cin, int cout, int ksize, int stride) {
+  const int hout = hin / stride;
+  GemmNT p{};
+  p.M = batch * hout * hout; p.N = cout; p.K = ksize * ksize * cin;
+  p.mode = 1; p.H = hin; p.W = hin; p.C = cin; p.Ho = hout; p.Wo = hout; p.S = ksize;
+  p.stride = stride; p.pad = ksize == 3 ? 1 : 0; p.up = 1; p.ldc = cout;
+  return p;
+}
+// dx (at the conv's INPUT resolution) = conv_transpose(dy) with the flipped / transposed weight shadow
+inline GemmNT conv_dgrad_problem(int batch, int hin, int cin, int cout, int ksize, int stride) {
+  const int hout = hin / stride;
+  GemmNT p{};
+  p.N = cin; p.K = ksize * ksize * cout; p.ldc = cin;
+  if (ksize == 1) {          // 1x1 stride-s: plain GEMM at the OUTPUT resolution (compact result; caller up-samples)
+    p.mode = 0; p.M = batch * hout * hout; p.lda = cout;
+  } else {
+    p.mode = 1; p.M = batch * hin * hin;
+    p.H = hout; p.W = hout; p.C = cout; p.Ho = hin; p.Wo = hin; p.S = 3;
+    p.stride = 1; p.pad = 1; p.up = stride;
+  }
+  return p;
+}
+extern int g_tn_use_tr;
+inline GemmTN conv_wgrad_problem(int batch, int hin, int cin, int cout, int ksize, int stride) {
+  const int hout = hin / stride;
+  GemmTN p{};
+  p.Kp = batch * hout * hout; p.NI = cout; p.NJ = ksize * ksize * cin;
+  p.mode = 1; p.H = hin; p.W = hin; p.C = cin; p.Ho = hout; p.Wo = hout; p.S = ksize;
+  p.stride = stride; p.pad = ksize == 3 ? 1 : 0;
+  p.ldp = cout; p.ldq = 0; p.use_tr = g_tn_use_tr;
+  return p;
+}
+// weight gradient of p (P / Q set) into dst: picks the K-splits; several of them go to `slab` (slab_floats floats, FEDFR_ERR_WORKSPACE if
+// they do not fit) and are summed into dst by ew_reduce_slabs
+int conv_wgrad_run(GemmTN p, float* dst, float* slab, size_t slab_floats, hipStream_t st);
 // number of splits / workspace helpers
 int gemm_nt_pick_splits(int M, int N, int K);
 int gemm_nt_launch(GemmNT p, int splits, hipStream_t st);

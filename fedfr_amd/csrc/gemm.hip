@@ -4,6 +4,7 @@
 #include "gemm_dev.h"
 #include "gemm_tn_dev.h"
 #include "nt_epilogue.h"
+#include "ew.h"
 
 #include <algorithm>
 #include <vector>
@@ -255,19 +256,9 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmNT p_) {
   nt_epilogue<BM, BN, WM, WN, 256>(p, acc, smem, bm, m0, n0, split, wm, wn, tid, lane);   // all waves are past the last barrier of the K loop
 }
 
-// (the single-stage variant of the NT kernel, option "nt_nbuf" = 1, lost every sweep of rounds 2-5 and was removed in round 6: two LDS stages, one
-// barrier per K-step)
-
-template <int BM, int BN, int WM, int WN, int NBUF>
-static int launch_nt_impl(const GemmNT& p0, int splits, hipStream_t st);
-
-template <int BM, int BN, int WM, int WN>
+// (the single-stage variant, option "nt_nbuf" = 1, lost every sweep of rounds 2-5 and was removed in round 6: two LDS stages, one barrier per K-step)
+template <int BM, int BN, int WM, int WN, int NBUF = 2>
 static int launch_nt(const GemmNT& p0, int splits, hipStream_t st) {
-  return launch_nt_impl<BM, BN, WM, WN, 2>(p0, splits, st);
-}
-
-template <int BM, int BN, int WM, int WN, int NBUF>
-static int launch_nt_impl(const GemmNT& p0, int splits, hipStream_t st) {
   GemmNT p = p0;
   const int nbm = ceil_div(p.M, BM);
   p.nbn = ceil_div(p.N, BN);
@@ -309,65 +300,80 @@ int gemm_nt_pick_splits(int M, int N, int K) {
 }
 
 int gemm_nt_stat_rows(int M, int N) {
-  // must mirror the tile choice in gemm_nt_launch: rows = ceil(M/BM) * WM
+  // the generic kernel's tile choice: rows = ceil(M/BM) * WM
   const int BM = nt_bm(M, N);
   const int WM = (BM == 128) ? 2 : ((N <= 64) ? 2 : 1);
   return ceil_div(M, BM) * WM;
 }
 
-// rows of gemm_nt_stat_rows that carry data for a conv with BatchNorm statistics in its epilogue (the rest are zero rows the kernel
-// writes so that a finalize over the 128-pixel-tile row count stays right): the 196-pixel-tile LDS-DMA kernels leave 2 per tile
-bool gemm_nt_conv_epilogue_ok(int W, int C, int N, int M, int ksize, int stride);
 int g_conv28_tpw2 = 2;   // option "conv28_tpw2": 28x28 convs run two image tiles per workgroup -- 1: the forward launches (one BatchNorm partial row per workgroup: 256 instead of 1024), 2: the dgrad launches too (256 workgroups that stay instead of 512 that are dispatched in two rounds between the weight-gradient workgroups: 17.72 -> 17.54 ms/step same-box)
-static bool glds28_two_tiles_shape(int M) { return g_conv28_tpw2 && (M / 196) % 2 == 0; }
-// the 28x28 dgrad with the BatchNorm-backward reduction in its epilogue runs two tiles per workgroup as well (one partial row each)
-bool gemm_nt_fused28_two_tiles(int M) { return g_conv28_tpw2 >= 2 && glds28_two_tiles_shape(M); }
-static bool glds28_two_tiles(const GemmNT& p) {          // option value 2: the dgrad launches (no statistics) too
-  return (p.stats || g_conv28_tpw2 >= 2) && p.W == 28 && !p.esc && !p.eadd && !p.Cb2 && glds28_two_tiles_shape(p.M);
-}
-int gemm_nt_stat_rows_live(int M, int N, int C, int W, int ksize, int stride) {
-  if ((W == 14 || W == 28) && gemm_nt_conv_epilogue_ok(W, C, N, M, ksize, stride))
-    return (W == 28 && glds28_two_tiles_shape(M)) ? M / 196 / 2 : M / 196 * 2;
-  // the persistent 64-channel kernel: two rows per workgroup, at most one workgroup per CU (conv_c64p.hip: launch_c64p) — 512 rows instead
-  // of 6 272 / 25 088, few enough for the finalize kernel to take without the staging launch in front of it
-  if (g_conv_c64p && ksize == 3 && stride == 1 && C == 64 && N == 64 && (W == 56 || W == 112) && M % (W * W) == 0) return 2 * conv_c64p_grid(M);
-  return gemm_nt_stat_rows(M, N);
-}
-
 int g_dgrad_parity = 2;   // option "dgrad_parity": stride-2 3x3 dgrad as 4 output-parity classes (9/4 instead of 9 taps per output pixel); 2: the four classes in one launch
 
-// shapes whose conv runs on a plain LDS-DMA kernel instantiation (mirrors the dispatch in gemm_nt_launch_one): those implement the
-// eval-mode output epilogue (GemmNT::esc / eadd / Cb2)
-bool gemm_nt_conv_epilogue_ok(int W, int C, int N, int M, int ksize, int stride) {
-  if (ksize != 3 || stride != 1 || W <= 0 || M % (W * W) != 0 || nt_bm(M, N) != 128) return false;
-  if (W == 112) return C == 64 && N == 64;
-  if (W == 56) return (C == 64 && (N == 64 || N == 128)) || (C == 128 && N == 64);
-  if (W == 14 || W == 28) return N % 128 == 0 && C % 128 == 0;
-  return false;
+static void nt_derive(GemmNT& p) {                        // the fields every kernel derives from the problem (no checks)
+  p.cpt = p.mode == 1 ? p.C / 64 : 1 << 30;
+  if (p.mode != 1) p.S = 1;
+  p.ksteps_total = p.par_on ? (1 + p.par_h) * (1 + p.par_w) * p.cpt : ceil_div(p.K, 64);
 }
 
-static int gemm_nt_launch_one(GemmNT p, int splits, hipStream_t st);
-int gemm_nt_launch(GemmNT p, int splits, hipStream_t st) {
-  if (g_dgrad_parity && p.mode == 1 && p.up == 2 && p.S == 3 && p.pad == 1 && p.stride == 1 && p.Cb && !p.stats && splits == 1 &&
-      !(p.Ho & 1) && !(p.Wo & 1) && p.Ho == 2 * p.H && p.Wo == 2 * p.W && p.M % (p.Ho * p.Wo) == 0 && !p.par_on) {
-    if (g_dgrad_parity >= 2) {                          // one launch, class = blockIdx.z
-      GemmNT q = p;
-      q.par_on = 2; q.par_h = 1; q.par_w = 1;           // (the largest class sizes the checks; the kernel sets its own)
-      q.outH = p.Ho; q.outW = p.Wo;
-      q.Ho = p.Ho / 2; q.Wo = p.Wo / 2; q.M = p.M / 4;
-      return gemm_nt_launch_one(q, 1, st);
-    }
-    for (int cls = 0; cls < 4; ++cls) {
-      GemmNT q = p;
-      q.par_on = 1; q.par_h = cls >> 1; q.par_w = cls & 1;
-      q.outH = p.Ho; q.outW = p.Wo;
-      q.Ho = p.Ho / 2; q.Wo = p.Wo / 2; q.M = p.M / 4;
-      FEDFR_TRY(gemm_nt_launch_one(q, 1, st));
-    }
-    return FEDFR_OK;
-  }
-  return gemm_nt_launch_one(p, splits, st);
+// a stride-2 3x3 dgrad by output-parity class: *q = the per-class problem (par_on 2: the four classes in one launch, class = blockIdx.z,
+// the kernel sets its own; 1: one launch per class, the caller sets par_h / par_w).  The largest class sizes the checks.
+static bool nt_parity_problem(const GemmNT& p, int splits, GemmNT* q) {
+  if (!(g_dgrad_parity && p.mode == 1 && p.up == 2 && p.S == 3 && p.pad == 1 && p.stride == 1 && p.Cb && !p.stats && splits == 1 &&
+        !(p.Ho & 1) && !(p.Wo & 1) && p.Ho == 2 * p.H && p.Wo == 2 * p.W && p.M % (p.Ho * p.Wo) == 0 && !p.par_on))
+    return false;
+  *q = p;
+  q->par_on = g_dgrad_parity >= 2 ? 2 : 1; q->par_h = 1; q->par_w = 1;
+  q->outH = p.Ho; q->outW = p.Wo;
+  q->Ho = p.Ho / 2; q->Wo = p.Wo / 2; q->M = p.M / 4;
+  return true;
 }
+
+// the kernel that serves p (nt_derive applied) and the rows it leaves: the ONE place that decides
+static NtPlan nt_plan_one(const GemmNT& p, int splits) {
+  using K = NtKernel;
+  const int rows = gemm_nt_stat_rows(p.M, p.N), tiles = p.M / 196;      // tiles of the 14x14 / 28x28 kernels: one image, or 7 rows of one
+  auto plan = [&](K k, int slot, int live, int part, bool epi) { return NtPlan{k, slot, rows, live, part, epi}; };
+  if (splits == 1 && conv_c64p_applies(p)) {              // two statistics rows / one partial row per workgroup
+    const int grid = conv_c64p_grid(p);
+    return plan(K::c64p, 15, 2 * grid, p.bpart ? grid : 0, false);
+  }
+  const int BM = nt_bm(p.M, p.N), BN = p.N <= 64 ? 64 : 128;
+  // 3x3 / stride-1 / pad-1 layers on the LDS-DMA kernels (conv_glds_impl.h: one translation unit per instantiation); every other shape — odd map
+  // sizes, channel counts that are not multiples of 128 on the 14x14 / 28x28 maps — takes the ring or the generic gather GEMM below
+  if (BM == 128 && p.mode == 1 && p.S == 3 && p.K == 9 * p.C && p.stride == 1 && p.pad == 1 && p.up == 1 &&
+      p.H == p.Ho && p.W == p.Wo && p.Cb && splits == 1 && p.W <= 126) {
+    if (p.H == 112 && p.W == 112 && !p.bpart && p.M % (112 * 112) == 0 && p.C == 64 && p.N == 64) return plan(K::glds_w112, 15, rows, 0, true);
+    if (p.H == 56 && p.W == 56 && !p.bpart && p.M % (56 * 56) == 0) {
+      if (p.C == 64 && p.N == 64) return plan(K::glds_w56, 15, rows, 0, true);
+      if (p.C == 64 && p.N == 128) return plan(K::glds_w56_c64_n128, 15, rows, 0, true);
+      if (p.C == 128 && p.N == 64) return plan(K::glds_w56_c128_n64, 15, rows, 0, true);
+    }
+    if (p.H == p.W && (p.W == 14 || p.W == 28) && p.N % 128 == 0 && p.C % 128 == 0 && p.M % (p.H * p.W) == 0) {
+      // 28x28: two image tiles per workgroup where the tile count is even — the launches with statistics (option value 1), every launch
+      // without an output epilogue (2).  Two statistics rows per tile, one per workgroup of two tiles; one partial row per workgroup.
+      const bool even28 = p.W == 28 && g_conv28_tpw2 && tiles % 2 == 0, pa = p.bmom == 2;      // pa: sphnet's PReLU-apply epilogue
+      if (p.bpart && p.ldc == p.N) {
+        if (p.W == 14) return plan(pa ? K::glds8_papply_w14 : K::glds8_fused_w14, 12, rows, tiles, false);
+        if (even28 && g_conv28_tpw2 >= 2 && !p.stats) return plan(pa ? K::glds8_papply_w28s : K::glds8_fused_w28s, 13, rows, tiles / 2, false);
+        return plan(pa ? K::glds8_papply_w28 : K::glds8_fused_w28, 13, rows, tiles, false);
+      }
+      if (!p.bpart) {
+        if (even28 && (p.stats || g_conv28_tpw2 >= 2) && !p.esc && !p.eadd && !p.Cb2) return plan(K::glds8_w28_stats, 13, tiles / 2, 0, false);
+        return p.W == 14 ? plan(K::glds8_w14, 12, 2 * tiles, 0, true) : plan(K::glds8_w28, 13, 2 * tiles, 0, true);
+      }
+    }
+  }
+  if (gemm_nt_glds_applies(p, BM, splits)) return plan(K::ring, 17, rows, 0, false);
+  return plan(BM == 128 ? (BN == 64 ? K::nt_128x64 : K::nt_128x128) : (BN == 64 ? K::nt_64x64 : K::nt_64x128), prof_slot(false, BM, BN), rows, 0, false);
+}
+
+NtPlan gemm_nt_plan(const GemmNT& p0, int splits) {
+  GemmNT p = p0;
+  (void)nt_parity_problem(p0, splits, &p);
+  nt_derive(p);
+  return nt_plan_one(p, splits);
+}
+
 static int gemm_nt_launch_one(GemmNT p, int splits, hipStream_t st) {
   FEDFR_REQUIRE(p.A && p.B && p.M > 0 && p.N > 0 && p.K > 0, "gemm_nt: null/empty operand");
   FEDFR_REQUIRE((p.K & 7) == 0, "gemm_nt: K=%d must be a multiple of 8", p.K);
@@ -376,15 +382,12 @@ static int gemm_nt_launch_one(GemmNT p, int splits, hipStream_t st) {
   if (p.Cf) FEDFR_REQUIRE((p.N & 3) == 0, "gemm_nt: fp32 output needs N%%4==0");
   if (p.mode == 1) {
     FEDFR_REQUIRE((p.C & 63) == 0, "gemm_nt: gather needs C%%64==0 (C=%d)", p.C);
-    p.cpt = p.C / 64;
     FEDFR_REQUIRE(p.K % p.C == 0 && p.S > 0 && (p.K / p.C) % p.S == 0, "gemm_nt: K must be taps*C");
     FEDFR_REQUIRE(p.up == 1 || p.up == 2, "gemm_nt: up must be 1 or 2");
   } else {
     FEDFR_REQUIRE((p.lda & 7) == 0, "gemm_nt: lda%%8");
-    p.cpt = 1 << 30;
-    p.S = 1;
   }
-  p.ksteps_total = p.par_on ? (1 + p.par_h) * (1 + p.par_w) * p.cpt : ceil_div(p.K, 64);
+  nt_derive(p);
   {
     const unsigned long long ab = p.mode == 1 ? 2ull * ((unsigned long long)ceil_div(p.M, p.Ho * p.Wo)) * p.H * p.W * p.C
                                               : 2ull * (unsigned long long)p.M * p.lda;
@@ -393,39 +396,56 @@ static int gemm_nt_launch_one(GemmNT p, int splits, hipStream_t st) {
     p.a_bytes = (unsigned)ab;
     p.b_bytes = (unsigned)bb;
   }
+  const NtPlan plan = nt_plan_one(p, splits);
   if (p.esc || p.eadd || p.Cb2)
-    FEDFR_REQUIRE(p.mode == 1 && p.up == 1 && p.pad == 1 && p.H == p.W && p.H == p.Ho && p.W == p.Wo && p.Cb && splits == 1 && !p.bpart &&
-                  !p.stats && !p.par_on && gemm_nt_conv_epilogue_ok(p.W, p.C, p.N, p.M, p.S, p.stride), "gemm_nt: output epilogue is not available for this convolution");
-  if (splits == 1 && conv_c64p_applies(p)) return launch_conv_c64p(p, st);
-  const int BM = nt_bm(p.M, p.N);
-  // 3x3 / stride-1 / pad-1 layers on the LDS-DMA kernels (conv_glds_impl.h: one translation unit per instantiation); every other shape — odd map
-  // sizes, channel counts that are not multiples of 128 on the 14x14 / 28x28 maps — takes the generic gather GEMM below
-  if (BM == 128 && p.mode == 1 && p.S == 3 && p.K == 9 * p.C && p.stride == 1 && p.pad == 1 && p.up == 1 &&
-      p.H == p.Ho && p.W == p.Wo && p.Cb && splits == 1 && p.W <= 126) {
-    if (p.H == 112 && p.W == 112 && !p.bpart && p.M % (112 * 112) == 0 && p.C == 64 && p.N == 64) return launch_conv_glds_w112(p, st);
-    if (p.H == 56 && p.W == 56 && !p.bpart && p.M % (56 * 56) == 0) {
-      if (p.C == 64 && p.N == 64) return launch_conv_glds_w56(p, st);
-      if (p.C == 64 && p.N == 128) return launch_conv_glds_w56_c64_n128(p, st);
-      if (p.C == 128 && p.N == 64) return launch_conv_glds_w56_c128_n64(p, st);
-    }
-    if (p.H == p.W && (p.W == 14 || p.W == 28) && p.N % 128 == 0 && p.C % 128 == 0 && p.M % (p.H * p.W) == 0) {
-      if (p.bpart && p.ldc == p.N && p.bmom == 2)         // sphnet: PReLU-apply epilogue
-        return p.W == 14 ? launch_conv_glds8_fused_w14_papply(p, st)
-                         : (gemm_nt_fused28_two_tiles(p.M) && !p.stats ? launch_conv_glds8_fused_w28s_papply(p, st) : launch_conv_glds8_fused_w28_papply(p, st));
-      if (p.bpart && p.ldc == p.N)
-        return p.W == 14 ? launch_conv_glds8_fused_w14(p, st)
-                         : (gemm_nt_fused28_two_tiles(p.M) && !p.stats ? launch_conv_glds8_fused_w28s(p, st) : launch_conv_glds8_fused_w28(p, st));
-      if (!p.bpart)
-        return p.W == 14 ? launch_conv_glds8_w14(p, st) : (glds28_two_tiles(p) ? launch_conv_glds8_w28_stats(p, st) : launch_conv_glds8_w28(p, st));
-    }
+    FEDFR_REQUIRE(!p.stats && !p.par_on && plan.out_epilogue, "gemm_nt: output epilogue is not available for this convolution");
+  switch (plan.kernel) {
+    case NtKernel::c64p: return launch_conv_c64p(p, plan, st);
+    case NtKernel::glds_w112: return launch_conv_glds_w112(p, plan, st);
+    case NtKernel::glds_w56: return launch_conv_glds_w56(p, plan, st);
+    case NtKernel::glds_w56_c64_n128: return launch_conv_glds_w56_c64_n128(p, plan, st);
+    case NtKernel::glds_w56_c128_n64: return launch_conv_glds_w56_c128_n64(p, plan, st);
+    case NtKernel::glds8_w14: return launch_conv_glds8_w14(p, plan, st);
+    case NtKernel::glds8_w28: return launch_conv_glds8_w28(p, plan, st);
+    case NtKernel::glds8_w28_stats: return launch_conv_glds8_w28_stats(p, plan, st);
+    case NtKernel::glds8_fused_w14: return launch_conv_glds8_fused_w14(p, plan, st);
+    case NtKernel::glds8_fused_w28: return launch_conv_glds8_fused_w28(p, plan, st);
+    case NtKernel::glds8_fused_w28s: return launch_conv_glds8_fused_w28s(p, plan, st);
+    case NtKernel::glds8_papply_w14: return launch_conv_glds8_fused_w14_papply(p, plan, st);
+    case NtKernel::glds8_papply_w28: return launch_conv_glds8_fused_w28_papply(p, plan, st);
+    case NtKernel::glds8_papply_w28s: return launch_conv_glds8_fused_w28s_papply(p, plan, st);
+    case NtKernel::ring: return launch_nt_glds(p, nt_bm(p.M, p.N), splits, plan.profile_slot, st);
+    case NtKernel::nt_128x128: return launch_nt<128, 128, 2, 2>(p, splits, st);
+    case NtKernel::nt_128x64: return launch_nt<128, 64, 2, 2>(p, splits, st);
+    case NtKernel::nt_64x128: return launch_nt<64, 128, 1, 4>(p, splits, st);
+    case NtKernel::nt_64x64: return launch_nt<64, 64, 2, 2>(p, splits, st);
   }
-  if (gemm_nt_glds_applies(p, BM, splits)) return launch_nt_glds(p, BM, splits, 17, st);
-  if (BM == 128) {
-    if (p.N <= 64) return launch_nt<128, 64, 2, 2>(p, splits, st);
-    return launch_nt<128, 128, 2, 2>(p, splits, st);
+  return FEDFR_ERR_UNSUPPORTED;
+}
+int gemm_nt_launch(GemmNT p, int splits, hipStream_t st) {
+  GemmNT q;
+  if (!nt_parity_problem(p, splits, &q)) return gemm_nt_launch_one(p, splits, st);
+  if (q.par_on == 2) return gemm_nt_launch_one(q, 1, st);
+  for (int cls = 0; cls < 4; ++cls) {
+    q.par_h = cls >> 1; q.par_w = cls & 1;
+    FEDFR_TRY(gemm_nt_launch_one(q, 1, st));
   }
-  if (p.N <= 64) return launch_nt<64, 64, 2, 2>(p, splits, st);
-  return launch_nt<64, 128, 1, 4>(p, splits, st);
+  return FEDFR_OK;
+}
+
+int conv_wgrad_run(GemmTN p, float* dst, float* slab, size_t slab_floats, hipStream_t st) {
+  const int splits = gemm_tn_pick_splits(p.Kp, p.NI, p.NJ, p.C, p.Wo, p.stride);
+  if (splits == 1) {
+    p.out = dst;
+    return gemm_tn_launch(p, 1, st);
+  }
+  if (!slab || slab_floats < (size_t)splits * p.NI * p.NJ) {
+    fedfr_set_error("conv2d_wgrad: workspace too small (%zu bytes)", slab_floats * sizeof(float));
+    return FEDFR_ERR_WORKSPACE;
+  }
+  p.out = slab;
+  FEDFR_TRY(gemm_tn_launch(p, splits, st));
+  return ew_reduce_slabs(dst, slab, splits, (size_t)p.NI * p.NJ, nullptr, 0, st);
 }
 
 // =====================================================================================================

@@ -47,25 +47,25 @@ struct ProfScope {
 double gemm_nt_alg_bytes(const GemmNT& p, int splits);      // algorithmic HBM bytes of a launch (gemm.hip)
 double gemm_tn_alg_bytes(const GemmTN& p, int splits);
 extern int g_tn_glds;
-int launch_conv_glds8_w14(GemmNT p, hipStream_t st);       // conv_glds8_w14.hip  same, 8 waves per tile
-int launch_conv_glds8_w28(GemmNT p, hipStream_t st);       // conv_glds8_w28.hip
-int launch_conv_glds8_w28_stats(GemmNT p, hipStream_t st); // conv_glds8_w28s.hip  two image tiles per workgroup, one BatchNorm partial row each
+int launch_conv_glds8_w14(GemmNT p, const NtPlan& plan, hipStream_t st);       // conv_glds8_w14.hip  same, 8 waves per tile
+int launch_conv_glds8_w28(GemmNT p, const NtPlan& plan, hipStream_t st);       // conv_glds8_w28.hip
+int launch_conv_glds8_w28_stats(GemmNT p, const NtPlan& plan, hipStream_t st); // conv_glds8_w28s.hip  two image tiles per workgroup, one BatchNorm partial row each
 extern int g_conv28_tpw2;
-int launch_conv_glds_w56(GemmNT p, hipStream_t st);        // conv_glds_w56.hip  56x56, C = N = 64
-int launch_conv_glds_w112(GemmNT p, hipStream_t st);       // conv_glds_w112.hip 112x112, C = N = 64
-int launch_conv_glds_w56_c64_n128(GemmNT p, hipStream_t st);   // conv_glds_w56b.hip
-int launch_conv_glds_w56_c128_n64(GemmNT p, hipStream_t st);
+int launch_conv_glds_w56(GemmNT p, const NtPlan& plan, hipStream_t st);        // conv_glds_w56.hip  56x56, C = N = 64
+int launch_conv_glds_w112(GemmNT p, const NtPlan& plan, hipStream_t st);       // conv_glds_w112.hip 112x112, C = N = 64
+int launch_conv_glds_w56_c64_n128(GemmNT p, const NtPlan& plan, hipStream_t st);   // conv_glds_w56b.hip
+int launch_conv_glds_w56_c128_n64(GemmNT p, const NtPlan& plan, hipStream_t st);
 // conv_c64p.hip: persistent 3x3 conv for the 64 -> 64 channel layers (112x112 / 56x56), filter bank in registers
 extern int g_conv_c64p;
 bool conv_c64p_applies(const GemmNT& p);
-int conv_c64p_grid(int M);
-int launch_conv_c64p(GemmNT p, hipStream_t st);
-int launch_conv_glds8_fused_w14(GemmNT p, hipStream_t st); // conv_glds8_fused_w14.hip  + BN-backward reduction epilogue
-int launch_conv_glds8_fused_w28(GemmNT p, hipStream_t st); // conv_glds8_fused_w28.hip
-int launch_conv_glds8_fused_w28s(GemmNT p, hipStream_t st); // conv_glds8_fused_w28s.hip
-int launch_conv_glds8_fused_w14_papply(GemmNT p, hipStream_t st);    // conv_glds8_fused_papply.hip: the three above with sphnet's PReLU-apply epilogue (bmom == 2)
-int launch_conv_glds8_fused_w28_papply(GemmNT p, hipStream_t st);
-int launch_conv_glds8_fused_w28s_papply(GemmNT p, hipStream_t st);
+int conv_c64p_grid(const GemmNT& p);   // workgroups of its launch
+int launch_conv_c64p(GemmNT p, const NtPlan& plan, hipStream_t st);
+int launch_conv_glds8_fused_w14(GemmNT p, const NtPlan& plan, hipStream_t st); // conv_glds8_fused_w14.hip  + BN-backward reduction epilogue
+int launch_conv_glds8_fused_w28(GemmNT p, const NtPlan& plan, hipStream_t st); // conv_glds8_fused_w28.hip
+int launch_conv_glds8_fused_w28s(GemmNT p, const NtPlan& plan, hipStream_t st); // conv_glds8_fused_w28s.hip
+int launch_conv_glds8_fused_w14_papply(GemmNT p, const NtPlan& plan, hipStream_t st);    // conv_glds8_fused_papply.hip: the three above with sphnet's PReLU-apply epilogue (bmom == 2)
+int launch_conv_glds8_fused_w28_papply(GemmNT p, const NtPlan& plan, hipStream_t st);
+int launch_conv_glds8_fused_w28s_papply(GemmNT p, const NtPlan& plan, hipStream_t st);
 // gemm_nt_glds.hip: the register-staged NT kernel's shapes with both operands fetched by LDS-DMA into a ring of stages
 extern int g_nt_glds;
 bool gemm_nt_glds_applies(const GemmNT& p, int BM, int splits);

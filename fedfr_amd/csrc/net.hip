@@ -261,37 +261,34 @@ struct Ctx {
   const float* beta(const BnD& b) const { return params + b.b_off; }
 };
 
-static int conv_fwd(const Ctx& c, const ConvD& cv, const bf16_t* in, bf16_t* out, bool stats) {
-  GemmNT p{};
-  p.A = in; p.B = c.shadow + cv.w_off;
-  p.M = c.n->B * cv.Hout * cv.Hout; p.N = cv.Cout; p.K = cv.R * cv.R * cv.Cin;
-  p.mode = 1; p.H = cv.Hin; p.W = cv.Hin; p.C = cv.Cin; p.Ho = cv.Hout; p.Wo = cv.Hout; p.S = cv.R;
-  p.stride = cv.stride; p.pad = (cv.R == 3) ? 1 : 0; p.up = 1;
-  p.Cb = out; p.ldc = cv.Cout; p.Cf = nullptr; p.stats = stats ? c.part() : nullptr;
+static GemmNT fwd_problem(const Ctx& c, const ConvD& cv, const bf16_t* in, bf16_t* out) {
+  GemmNT p = conv_fwd_problem(c.n->B, cv.Hin, cv.Cin, cv.Cout, cv.R, cv.stride);
+  p.A = in; p.B = c.shadow + cv.w_off; p.Cb = out;
+  return p;
+}
+// *live_rows (optional): the leading rows of the statistics that carry data (the rest are zero filler)
+static int conv_fwd(const Ctx& c, const ConvD& cv, const bf16_t* in, bf16_t* out, bool stats, int* live_rows = nullptr) {
+  GemmNT p = fwd_problem(c, cv, in, out);
+  p.stats = stats ? c.part() : nullptr;
+  if (live_rows) *live_rows = gemm_nt_plan(p, 1).stat_rows_live;
   return gemm_nt_launch(p, 1, c.st);
 }
-// eval mode: the BatchNorm (+PReLU, + identity, + the next block's bn1 as a second output) that follows a conv applied in the conv
-// kernel's epilogue (GemmNT::esc ...), for the layers whose kernel implements it
+// eval mode: the problem of a conv with the BatchNorm (+PReLU, + identity, + the next block's bn1 as a second output) that follows it applied
+// in the kernel's epilogue (GemmNT::esc ...), for the layers whose kernel implements it
 int g_eval_fuse = 1;   // option "eval_fuse"
-static bool conv_epilogue_ok(const Ctx& c, const ConvD& cv) {
-  return g_eval_fuse && gemm_nt_conv_epilogue_ok(cv.Hin, cv.Cin, cv.Cout, c.n->B * cv.Hout * cv.Hout, cv.R, cv.stride);
-}
-static int conv_fwd_ep(const Ctx& c, const ConvD& cv, const bf16_t* in, bf16_t* out, const BnD& bn, const float* alpha, const bf16_t* add,
-                       bf16_t* out2, const BnD* bn2) {
-  GemmNT p{};
-  p.A = in; p.B = c.shadow + cv.w_off;
-  p.M = c.n->B * cv.Hout * cv.Hout; p.N = cv.Cout; p.K = cv.R * cv.R * cv.Cin;
-  p.mode = 1; p.H = cv.Hin; p.W = cv.Hin; p.C = cv.Cin; p.Ho = cv.Hout; p.Wo = cv.Hout; p.S = cv.R;
-  p.stride = cv.stride; p.pad = 1; p.up = 1;
-  p.Cb = out; p.ldc = cv.Cout; p.Cf = nullptr; p.stats = nullptr;
+static GemmNT conv_fwd_ep(const Ctx& c, const ConvD& cv, const bf16_t* in, bf16_t* out, const BnD& bn, const float* alpha, const bf16_t* add,
+                             bf16_t* out2, const BnD* bn2) {
+  GemmNT p = fwd_problem(c, cv, in, out);
   p.esc = c.save(bn, 0); p.esh = c.save(bn, 1); p.ealpha = alpha; p.eadd = add;
   if (out2) { p.Cb2 = out2; p.esc2 = c.save(*bn2, 0); p.esh2 = c.save(*bn2, 1); }
-  return gemm_nt_launch(p, 1, c.st);
+  return p;
+}
+static bool conv_epilogue_ok(const Ctx& c, const ConvD& cv, const BnD& bn) {      // (the plan reads which pointers are set, never through them)
+  return g_eval_fuse && gemm_nt_plan(conv_fwd_ep(c, cv, c.actb, c.actb, bn, nullptr, nullptr, nullptr, nullptr), 1).out_epilogue;
 }
 int g_fwd_xmom = 1;       // option "fwd_xmom": bn3 + identity + the next block's bn1 as one pass from conv2's raw moments (14x14 / 28x28 blocks)
 int g_fuse_bnbwd28 = 1;   // option "fuse_bnbwd28": ... and in the two-tiles 28x28 dgrad (with fuse_bnbwd != 0)
 int g_c64p_bnbwd = 1;   // option "c64p_bnbwd": BN-backward reduction in the epilogue of the persistent 64-channel dgrad kernel (with fuse_bnbwd != 0)
-extern int g_conv_c64p;
 int g_fuse_bnbwd = 2;   // (round 3: 2 is the default, together with wgrad9p = 1 — see the end of this comment)  option "fuse_bnbwd": BN-backward reduction in the 3x3 dgrad epilogue (1: every layer a fused kernel serves; 2: the 14x14
                         // layers only, whose 128 partial rows the channel-sliced apply pass reduces itself).  LDS-DMA kernel: the x tile rides
                         // through the K loop in registers, the coefficients are requested in front of the drain: +3.7 us on a 28.6 us dgrad
@@ -307,52 +304,28 @@ int g_fuse_bnbwd = 2;   // (round 3: 2 is the default, together with wgrad9p = 1
 // BN-backward partial sums of (dx, bn_x) in its epilogue; *fused_rows > 0 then (else run ew_bn_bwd_reduce).
 static int conv_dgrad(const Ctx& c, const ConvD& cv, const bf16_t* dy, bf16_t* dx, const BnD* bn = nullptr,
                       const bf16_t* bn_x = nullptr, const float* alpha = nullptr, int* fused_rows = nullptr) {
-  GemmNT p{};
-  // option value 2: only the 14x14 layers (one partial row per image: few enough for the channel-sliced apply pass to reduce itself)
-  // ... and (round 3) the 64 -> 64 layers of the 56x56 / 112x112 maps on the persistent kernel: one row per workgroup (conv_c64p.hip)
-  const bool c64 = g_c64p_bnbwd && g_conv_c64p && cv.R == 3 && cv.stride == 1 && cv.Cin == 64 && cv.Cout == 64 && (cv.Hin == 56 || cv.Hin == 112);
-  // ... and the 28x28 layers on the two-tiles LDS-DMA kernel: one row per workgroup = 256 at B = 128, which the sliced apply pass takes
-  const bool w28 = g_fuse_bnbwd28 && cv.R == 3 && cv.stride == 1 && cv.Hin == 28 && cv.Cin % 128 == 0 && cv.Cout % 128 == 0 &&
-                   gemm_nt_fused28_two_tiles(c.n->B * 28 * 28) && ew_bn_sliced_ok(c.n->B * 28 * 28, cv.Cin, c.n->B * 28 * 28 / 392, true);
-  if (bn && fused_rows && g_fuse_bnbwd && (g_fuse_bnbwd == 1 || c64 || w28 || (cv.R == 3 && cv.stride == 1 && cv.Hin == 14 && cv.Cin % 128 == 0 && cv.Cout % 128 == 0))) {
-    p.bx = bn_x; p.bmean = c.save(*bn, 2); p.brstd = c.save(*bn, 3); p.bgamma = c.gamma(*bn); p.bbeta = c.beta(*bn);
-    p.balpha = alpha; p.bpart = c.part(); p.bwd_fused = fused_rows;
-  }
-  p.B = c.shadow + cv.wd_off; p.A = dy;
-  p.N = cv.Cin; p.K = cv.R * cv.R * cv.Cout;
-  p.Cb = dx; p.ldc = cv.Cin; p.Cf = nullptr; p.stats = nullptr;
-  if (cv.R == 1) {          // 1x1 stride-s: plain GEMM at the OUTPUT resolution (compact result; caller up-samples)
-    p.mode = 0; p.M = c.n->B * cv.Hout * cv.Hout; p.lda = cv.Cout;
-  } else {
-    p.mode = 1; p.M = c.n->B * cv.Hin * cv.Hin;
-    p.H = cv.Hout; p.W = cv.Hout; p.C = cv.Cout; p.Ho = cv.Hin; p.Wo = cv.Hin; p.S = 3;
-    p.stride = 1; p.pad = 1; p.up = cv.stride;
+  GemmNT p = conv_dgrad_problem(c.n->B, cv.Hin, cv.Cin, cv.Cout, cv.R, cv.stride);
+  p.A = dy; p.B = c.shadow + cv.wd_off; p.Cb = dx;
+  if (bn && fused_rows && g_fuse_bnbwd) {
+    GemmNT f = p;
+    f.bx = bn_x; f.bmean = c.save(*bn, 2); f.brstd = c.save(*bn, 3); f.bgamma = c.gamma(*bn); f.bbeta = c.beta(*bn); f.balpha = alpha; f.bpart = c.part();
+    const NtPlan pl = gemm_nt_plan(f, 1);
+    // option value 2: only the kernels that leave one partial row per workgroup, few enough for the channel-sliced apply pass to reduce itself —
+    // 14x14 (one per image), the persistent 64 -> 64 kernel (conv_c64p.hip), the two-tiles 28x28 kernel (256 at B = 128) where that pass takes them
+    const bool want = g_fuse_bnbwd == 1 || pl.kernel == NtKernel::glds8_fused_w14 || (g_c64p_bnbwd && pl.kernel == NtKernel::c64p) ||
+                      (g_fuse_bnbwd28 && pl.kernel == NtKernel::glds8_fused_w28s && ew_bn_sliced_ok(f.M, f.N, pl.part_rows, true));
+    if (pl.part_rows > 0 && want) { p = f; *fused_rows = pl.part_rows; }
   }
   return gemm_nt_launch(p, 1, c.st);
 }
 static GemmTN wgrad_problem(const Ctx& c, const ConvD& cv, const bf16_t* in, const bf16_t* dy) {
-  GemmTN p{};
+  GemmTN p = conv_wgrad_problem(c.n->B, cv.Hin, cv.Cin, cv.Cout, cv.R, cv.stride);
   p.P = dy; p.Q = in;
-  p.Kp = c.n->B * cv.Hout * cv.Hout; p.NI = cv.Cout; p.NJ = cv.R * cv.R * cv.Cin;
-  p.mode = 1; p.H = cv.Hin; p.W = cv.Hin; p.C = cv.Cin; p.Ho = cv.Hout; p.Wo = cv.Hout; p.S = cv.R;
-  p.stride = cv.stride; p.pad = (cv.R == 3) ? 1 : 0;
-  p.ldp = cv.Cout; p.ldq = 0; p.use_tr = g_tn_use_tr;
   return p;
 }
+// (the slab workspace was sized at plan creation: gemm_tn_max_splits over every kernel choice)
 static int conv_wgrad(const Ctx& c, const ConvD& cv, const bf16_t* in, const bf16_t* dy, hipStream_t st) {
-  GemmTN p = wgrad_problem(c, cv, in, dy);
-  const int splits = gemm_tn_pick_splits(p.Kp, p.NI, p.NJ, p.C, p.Wo, p.stride);
-  float* dst = c.grads + cv.w_off;
-  if (splits == 1) {
-    p.out = dst;
-    return gemm_tn_launch(p, 1, st);
-  }
-  // the slab workspace was sized at plan creation (gemm_tn_max_splits over every kernel choice)
-  FEDFR_REQUIRE((size_t)splits * p.NI * p.NJ <= c.n->slab_floats, "conv_wgrad: %d split-K slabs of %d x %d exceed the plan's slab workspace "
-                "(%zu floats)", splits, p.NI, p.NJ, c.n->slab_floats);
-  p.out = c.slab();
-  FEDFR_TRY(gemm_tn_launch(p, splits, st));
-  return ew_reduce_slabs(dst, c.slab(), splits, (size_t)p.NI * p.NJ, nullptr, 0, st);
+  return conv_wgrad_run(wgrad_problem(c, cv, in, dy), c.grads + cv.w_off, c.slab(), c.n->slab_floats, st);
 }
 // Slab sets of a paired nine-tap launch whose reduction has not been issued yet: the NEXT paired launch on the stream carries it out beside its own
 // work (wgrad9p.hip, W9PJob), or wgrad_flush() issues the stand-alone launches — before anything else uses the slab workspace or reads the
@@ -549,21 +522,21 @@ int net_forward(const FedfrNet* n, const float* x, const float* params, float* b
       // ---- eval mode: BatchNorms are known affines -> they ride in the conv epilogues where the kernel has one
       if (!a1_ready) FEDFR_TRY(apply(c, A + k.x_off, k.bn1, nullptr, nullptr, nullptr, A + k.a1_off, Mi, false));
       a1_ready = false;
-      if (conv_epilogue_ok(c, k.conv1)) {
-        FEDFR_TRY(conv_fwd_ep(c, k.conv1, A + k.a1_off, A + k.a2_off, k.bn2, params + k.alpha_off, nullptr, nullptr, nullptr));
+      if (conv_epilogue_ok(c, k.conv1, k.bn2)) {
+        FEDFR_TRY(gemm_nt_launch(conv_fwd_ep(c, k.conv1, A + k.a1_off, A + k.a2_off, k.bn2, params + k.alpha_off, nullptr, nullptr, nullptr), 1, st));
       } else {
         FEDFR_TRY(conv_fwd(c, k.conv1, A + k.a1_off, A + k.c1_off, false));
         FEDFR_TRY(apply(c, A + k.c1_off, k.bn2, params + k.alpha_off, nullptr, nullptr, A + k.a2_off, Mi, false));
       }
       if (k.has_ds) FEDFR_TRY(conv_fwd(c, k.ds, A + k.x_off, A + k.d_off, false));
-      if (conv_epilogue_ok(c, k.conv2)) {
+      if (conv_epilogue_ok(c, k.conv2, k.bn3)) {
         const bf16_t* idn = A + k.x_off;
         if (k.has_ds) {                                                 // identity = bnds(ds(x)), materialised in the (unused) c2 slot
           FEDFR_TRY(apply(c, A + k.d_off, k.bnds, nullptr, nullptr, nullptr, A + k.c2_off, Mo, false));
           idn = A + k.c2_off;
         }
         const BlockD* nx = bi + 1 < n->blocks.size() ? &n->blocks[bi + 1] : nullptr;
-        FEDFR_TRY(conv_fwd_ep(c, k.conv2, A + k.a2_off, A + k.out_off, k.bn3, nullptr, idn, nx ? A + nx->a1_off : nullptr, nx ? &nx->bn1 : nullptr));
+        FEDFR_TRY(gemm_nt_launch(conv_fwd_ep(c, k.conv2, A + k.a2_off, A + k.out_off, k.bn3, nullptr, idn, nx ? A + nx->a1_off : nullptr, nx ? &nx->bn1 : nullptr), 1, st));
         a1_ready = nx != nullptr;
       } else {
         FEDFR_TRY(conv_fwd(c, k.conv2, A + k.a2_off, A + k.c2_off, false));
@@ -591,34 +564,22 @@ int net_forward(const FedfrNet* n, const float* x, const float* params, float* b
     // bn1(out) leave ONE pass (bn_apply2, ew.h): conv2 also sums c2 * x, and the statistics of `out` follow from those moments and the
     // statistics of x this block's bn1 saved — the next block's bn1 pass disappears
     const BlockD* nxb = bi + 1 < n->blocks.size() ? &n->blocks[bi + 1] : nullptr;
-    const int xm_rows = k.Hout == 14 ? Mo / 196 : Mo / 392;
-    const bool xmom = g_fwd_xmom && nxb && !k.has_ds && k.conv2.R == 3 && k.conv2.stride == 1 && (k.Hout == 14 || k.Hout == 28) &&
-                      k.conv2.Cin % 128 == 0 && k.Cout % 128 == 0 && k.conv2.Cin == k.Cout && nxb->bn1.C == k.Cout &&
-                      gemm_nt_conv_epilogue_ok(k.Hout, k.conv2.Cin, k.Cout, Mo, 3, 1) &&          // (mirrors the dispatch: small problems take the generic kernel)
-                      (k.Hout == 14 || gemm_nt_fused28_two_tiles(Mo)) && ew_bn_apply2_sliced_ok(Mo, k.Cout, xm_rows);
-    if (a1_ready) {                             // the previous block's output pass wrote a1 = bn1(x) and bn1's statistics
-      FEDFR_TRY(conv_fwd(c, k.conv1, A + k.a1_off, A + k.c1_off, true));
-      a1_ready = false;
-    } else {
-      FEDFR_TRY(bn_apply_train(c, k.bn1, prev, A + k.x_off, nullptr, nullptr, A + k.a1_off, Mi, nullptr));
-      FEDFR_TRY(conv_fwd(c, k.conv1, A + k.a1_off, A + k.c1_off, true));
-    }
-    const Rows r1{c.part(), gemm_nt_stat_rows_live(Mi, k.Cout, k.conv1.Cin, k.conv1.Hin, k.conv1.R, k.conv1.stride)};
+    int live = 0;                               // leading statistics rows of the conv just launched that carry data
+    if (!a1_ready) FEDFR_TRY(bn_apply_train(c, k.bn1, prev, A + k.x_off, nullptr, nullptr, A + k.a1_off, Mi, nullptr));
+    a1_ready = false;                           // (else: the previous block's output pass wrote a1 = bn1(x) and bn1's statistics)
+    FEDFR_TRY(conv_fwd(c, k.conv1, A + k.a1_off, A + k.c1_off, true, &live));
+    FEDFR_TRY(bn_apply_train(c, k.bn2, Rows{c.part(), live}, A + k.c1_off, params + k.alpha_off, nullptr, A + k.a2_off, Mi, nullptr));
+    GemmNT pm = fwd_problem(c, k.conv2, A + k.a2_off, A + k.c2_off);      // conv2 with the moment epilogue
+    pm.bx = A + k.x_off; pm.bmean = c.save(k.bn3, 2); pm.brstd = c.save(k.bn3, 3); pm.bpart = c.part(); pm.bmom = 1;
+    const NtPlan plm = gemm_nt_plan(pm, 1);
+    // (x must have the output's shape; one partial row per workgroup, which the sliced pass reduces itself)
+    const bool xmom = g_fwd_xmom && nxb && !k.has_ds && k.conv2.Cin == k.Cout && nxb->bn1.C == k.Cout && plm.part_rows > 0 &&
+                      (plm.kernel == NtKernel::glds8_fused_w14 || plm.kernel == NtKernel::glds8_fused_w28s) &&
+                      ew_bn_apply2_sliced_ok(Mo, k.Cout, plm.part_rows);
     if (xmom) {
-      FEDFR_TRY(bn_apply_train(c, k.bn2, r1, A + k.c1_off, params + k.alpha_off, nullptr, A + k.a2_off, Mi, nullptr));
-      GemmNT p{};
-      const ConvD& cv = k.conv2;
-      p.A = A + k.a2_off; p.B = c.shadow + cv.w_off;
-      p.M = Mo; p.N = cv.Cout; p.K = 9 * cv.Cin;
-      p.mode = 1; p.H = cv.Hin; p.W = cv.Hin; p.C = cv.Cin; p.Ho = cv.Hout; p.Wo = cv.Hout; p.S = 3;
-      p.stride = 1; p.pad = 1; p.up = 1;
-      p.Cb = A + k.c2_off; p.ldc = cv.Cout;
-      int rows = 0;
-      p.bx = A + k.x_off; p.bmean = c.save(k.bn3, 2); p.brstd = c.save(k.bn3, 3); p.bpart = c.part(); p.bmom = 1; p.bwd_fused = &rows;
-      FEDFR_TRY(gemm_nt_launch(p, 1, c.st));
-      FEDFR_REQUIRE(rows == xm_rows, "net_forward: the moment epilogue left %d rows, %d expected", rows, xm_rows);
+      FEDFR_TRY(gemm_nt_launch(pm, 1, c.st));
       BnApply2S a{};
-      a.part = c.part(); a.P = rows; a.count = (double)Mo; a.momentum = kBnMomentum; a.eps = kBnEps;
+      a.part = c.part(); a.P = plm.part_rows; a.count = (double)Mo; a.momentum = kBnMomentum; a.eps = kBnEps;
       a.gamma = c.gamma(k.bn3); a.beta = c.beta(k.bn3); a.rm = c.bufs + k.bn3.rm_off; a.rv = c.bufs + k.bn3.rv_off;
       a.scale = c.save(k.bn3, 0); a.shift = c.save(k.bn3, 1); a.mean = c.save(k.bn3, 2); a.rstd = c.save(k.bn3, 3);
       a.xmean = c.save(k.bn1, 2); a.xrstd = c.save(k.bn1, 3);
@@ -630,11 +591,9 @@ int net_forward(const FedfrNet* n, const float* x, const float* params, float* b
       a1_ready = true;
       prev = Rows{c.part(), 0};
       continue;
-    } else {
-      FEDFR_TRY(bn_apply_train(c, k.bn2, r1, A + k.c1_off, params + k.alpha_off, nullptr, A + k.a2_off, Mi, nullptr));
-      FEDFR_TRY(conv_fwd(c, k.conv2, A + k.a2_off, A + k.c2_off, true));
     }
-    const Rows r2{c.part(), gemm_nt_stat_rows_live(Mo, k.Cout, k.conv2.Cin, k.conv2.Hin, k.conv2.R, k.conv2.stride)};
+    FEDFR_TRY(conv_fwd(c, k.conv2, A + k.a2_off, A + k.c2_off, true, &live));
+    const Rows r2{c.part(), live};
     if (k.has_ds) {
       FEDFR_TRY(bn_coeffs(c, k.bn3, r2, (double)Mo, true));
       FEDFR_TRY(conv_fwd(c, k.ds, A + k.x_off, A + k.d_off, true));

@@ -275,42 +275,28 @@ static int sph_backward(const FedfrNet* n, const float* dfeats, const float* par
     return FEDFR_OK;
   };
   // dgrad of `cv` whose epilogue also applies the backward of the PReLU(+bias) unit `pu` in FRONT of the conv: output = pu's dz, rows = pu's
-  // parameter sums (GemmNT::bmom = 2).  *fused = rows written, 0 if no kernel with that epilogue serves the shape (then nothing was applied).
+  // parameter sums (GemmNT::bmom = 2).  *fused = rows written; 0, and nothing launched, where no kernel with that epilogue and one row per
+  // workgroup (14x14, two-tiles 28x28) serves the shape, or the unit's row buffer does not hold its rows
   auto dgrad_prelu = [&](const ConvD& cv, const bf16_t* dy, const SphUnit& pu, int* fused) -> int {
     *fused = 0;
-    GemmNT p{};
-    p.B = c.shadow + cv.wd_off; p.A = dy; p.N = cv.Cin; p.K = 9 * cv.Cout;
-    p.Cb = reinterpret_cast<bf16_t*>(ws + pu.dz_off); p.ldc = cv.Cin;
-    p.mode = 1; p.M = B * cv.Hin * cv.Hin; p.H = cv.Hout; p.W = cv.Hout; p.C = cv.Cout; p.Ho = cv.Hin; p.Wo = cv.Hin; p.S = 3;
-    p.stride = 1; p.pad = 1; p.up = 1;
+    GemmNT p = conv_dgrad_problem(B, cv.Hin, cv.Cin, cv.Cout, cv.R, cv.stride);
+    p.A = dy; p.B = c.shadow + cv.wd_off; p.Cb = reinterpret_cast<bf16_t*>(ws + pu.dz_off);
     p.bx = A + pu.c_off; p.bbeta = pu.b_off >= 0 ? params + pu.b_off : nullptr; p.balpha = params + pu.a_off;
     p.bmean = params + pu.a_off; p.brstd = params + pu.a_off;      // (read, never used in this mode)
-    p.bpart = reinterpret_cast<float*>(ws + pu.rows_off); p.bmom = 2; p.bwd_fused = fused;
+    p.bpart = reinterpret_cast<float*>(ws + pu.rows_off); p.bmom = 2;
+    const NtPlan pl = gemm_nt_plan(p, 1);
+    if (!g_sph_fuse_prelu_bwd || p.N != pu.conv.Cout || (pl.kernel != NtKernel::glds8_papply_w14 && pl.kernel != NtKernel::glds8_papply_w28s) ||
+        (size_t)pl.part_rows * 3 > (size_t)ew_prelu_bwd_rows(p.M, pu.conv.Cout) * 2) return FEDFR_OK;
+    *fused = pl.part_rows;
     return gemm_nt_launch(p, 1, st);
-  };
-  auto dgrad_prelu_ok = [&](const ConvD& cv, const SphUnit& pu) -> bool {
-    const int M = B * cv.Hin * cv.Hin;
-    if (!g_sph_fuse_prelu_bwd || cv.R != 3 || cv.stride != 1 || cv.Cin != pu.conv.Cout || cv.Cin % 128 != 0 || cv.Cout % 128 != 0) return false;
-    if (!gemm_nt_conv_epilogue_ok(cv.Hin, cv.Cout, cv.Cin, M, 3, 1)) return false;                         // (mirrors the dispatch of gemm_nt_launch)
-    const size_t rows = (size_t)(cv.Hin == 14 ? M / 196 : M / 392);
-    return (cv.Hin == 14 || (cv.Hin == 28 && gemm_nt_fused28_two_tiles(M))) &&
-           rows * 3 <= (size_t)ew_prelu_bwd_rows(M, pu.conv.Cout) * 2;                                     // the unit's row buffer holds them
   };
   WgradPending pend_w;                                  // a paired weight-gradient launch whose slabs the next one sums (wgrad9p.hip, W9PJob)
   auto unit_wgrad = [&](const SphUnit& u) -> int {      // on the weight-gradient stream
     FEDFR_TRY(wgrad_flush(c, &pend_w, wst));            // (uses the slab workspace itself)
     FEDFR_TRY(fin_add(u));
     if (u.cin_real != u.conv.Cin) {                     // the stem: gradient of the padded weights, then its 3 real input channels
-      GemmTN p = wgrad_problem(c, u.conv, A + u.in_off, reinterpret_cast<const bf16_t*>(ws + u.dz_off));
-      const int splits = gemm_tn_pick_splits(p.Kp, p.NI, p.NJ, p.C, p.Wo, p.stride);
       float* g0 = reinterpret_cast<float*>(ws + n->sph_ws_w0g);
-      if (splits == 1) { p.out = g0; FEDFR_TRY(gemm_tn_launch(p, 1, wst)); }
-      else {
-        FEDFR_REQUIRE((size_t)splits * p.NI * p.NJ <= n->slab_floats, "sph_backward: stem split-K slabs exceed the slab workspace");
-        p.out = c.slab();
-        FEDFR_TRY(gemm_tn_launch(p, splits, wst));
-        FEDFR_TRY(ew_reduce_slabs(g0, c.slab(), splits, (size_t)p.NI * p.NJ, nullptr, 0, wst));
-      }
+      FEDFR_TRY(conv_wgrad_run(wgrad_problem(c, u.conv, A + u.in_off, reinterpret_cast<const bf16_t*>(ws + u.dz_off)), g0, c.slab(), n->slab_floats, wst));
       hipLaunchKernelGGL(sph_unpad_g0_kernel, dim3(ceil_div(64 * 9 * 3, 256)), dim3(256), 0, wst, g0, grads + u.w_param_off);
       FEDFR_LAUNCH_CHECK("sph_unpad_g0");
       return FEDFR_OK;
@@ -334,7 +320,7 @@ static int sph_backward(const FedfrNet* n, const float* dfeats, const float* par
       FEDFR_TRY(dbg_capture(G(cur), (size_t)B * stg.H * stg.H * stg.C, &dbg_off, st));      // the gradient u2's PReLU backward differentiated (pending branch folded in)
       bf16_t* dt1 = G(2);
       int f1 = 0;                                         // rows of u1's parameter sums when conv2's dgrad epilogue applied u1's backward itself
-      if (dgrad_prelu_ok(k.u2.conv, k.u1)) FEDFR_TRY(dgrad_prelu(k.u2.conv, reinterpret_cast<const bf16_t*>(ws + k.u2.dz_off), k.u1, &f1));
+      FEDFR_TRY(dgrad_prelu(k.u2.conv, reinterpret_cast<const bf16_t*>(ws + k.u2.dz_off), k.u1, &f1));
       if (f1 == 0) {
         FEDFR_TRY(conv_dgrad(c, k.u2.conv, reinterpret_cast<const bf16_t*>(ws + k.u2.dz_off), dt1));
         FEDFR_TRY(prelu_bwd(k.u1, dt1, nullptr, nullptr));

@@ -215,6 +215,15 @@ int fedfr_conv2d_fwd_epilogue(const uint16_t* x, const uint16_t* w, uint16_t* y,
                               int cout, void* stream);
 int fedfr_conv2d_dgrad_papply(const uint16_t* dy, const uint16_t* wd, uint16_t* dz, int batch, int hin, int cin, int cout,
                               const uint16_t* act_x, const float* bias, const float* alpha, float* partials, int* rows, void* stream);
+/* Host-only query of the kernel selector (no device is touched, nothing is launched): which kernel the forward conv (dgrad = 0) or the
+ * dgrad (dgrad = 1) of this geometry runs on under the current options when it is asked for the epilogues in `want` — a bit set of
+ * 1 forward statistics, 2 BatchNorm-backward rows, 4 raw moments, 8 PReLU-apply, 16 output epilogue (1, 4, 16: forward; 2, 8: dgrad; 2, 4, 8:
+ * 3x3 only) — and what a caller has to know before the launch.  *profile_slot: the fedfr_profile_read slot of that kernel (a stride-2 3x3
+ * dgrad under option "dgrad_parity": of its per-class launches); *stat_rows = fedfr_conv2d_stat_rows of the launch, *stat_rows_live the
+ * leading rows of those that carry data; *part_rows: rows the reduction epilogue leaves, 0 if the kernel has none; *out_epilogue: 1 if
+ * the kernel implements the output epilogue.  Without a device the persistent 64-channel kernel is planned for 256 compute units. */
+int fedfr_conv2d_plan(int batch, int hin, int cin, int cout, int ksize, int stride, int dgrad, int want, int* profile_slot, int* stat_rows,
+                      int* stat_rows_live, int* part_rows, int* out_epilogue);
 /* lowest-priority HIP stream for the aux_stream argument of fedfr_net_backward2 (no reference counterpart; the reference trains on
  * one stream).  Destroy with fedfr_stream_destroy. */
 int fedfr_stream_create_low_priority(void** stream);

@@ -80,7 +80,7 @@ def nt_glds_up(M, stats, nt_glds=4):
 
 
 def conv_epilogue_ok(W, C, N, M, ksize, stride):
-    """gemm.hip: gemm_nt_conv_epilogue_ok — the 3x3 / stride-1 shapes on a plain LDS-DMA instantiation"""
+    """gemm.hip: gemm_nt_plan, out_epilogue of a launch that asks for it — the 3x3 / stride-1 shapes on a plain LDS-DMA instantiation"""
     if ksize != 3 or stride != 1 or W <= 0 or M % (W * W) or nt_bm(M, N) != 128:
         return False
     if W == 112:
@@ -93,7 +93,7 @@ def conv_epilogue_ok(W, C, N, M, ksize, stride):
 
 
 def conv_c64p_grid(M, cus):
-    """conv_c64p.hip: conv_c64p_grid — 224-pixel tiles dealt out evenly to at most one workgroup per CU"""
+    """conv_c64p.hip: c64p_deal — 224-pixel tiles dealt out evenly to at most one workgroup per CU"""
     ntiles = M // 224
     per_wg = cdiv(ntiles, min(ntiles, cus))
     return cdiv(ntiles, per_wg)
@@ -107,7 +107,7 @@ def nt_stat_rows(M, N):
 
 
 def nt_stat_rows_live(M, N, C, W, ksize, stride, cus, conv_c64p=1, conv28_tpw2=2):
-    """gemm.hip: gemm_nt_stat_rows_live — the leading rows that carry data (the rest are zero filler)"""
+    """gemm.hip: gemm_nt_plan, stat_rows_live of a forward launch with statistics — the leading rows that carry data (the rest are zero filler)"""
     if W in (14, 28) and conv_epilogue_ok(W, C, N, M, ksize, stride):
         return M // 196 // 2 if (W == 28 and conv28_tpw2 and (M // 196) % 2 == 0) else M // 196 * 2
     if conv_c64p and ksize == 3 and stride == 1 and C == 64 and N == 64 and W in (56, 112) and M % (W * W) == 0:
@@ -115,10 +115,11 @@ def nt_stat_rows_live(M, N, C, W, ksize, stride, cus, conv_c64p=1, conv28_tpw2=2
     return nt_stat_rows(M, N)
 
 
-def conv3x3_slot(M, W, C, N, fused=False, stats=False, epilogue=False, conv_c64p=1, nt_glds=4):
-    """gemm.hip: gemm_nt_launch_one for a 3x3 / stride-1 / pad-1 conv whose GEMM has K = 9 C and N output columns (forward: C = cin, N = cout;
-    dgrad: C = cout, N = cin).  fused: a BatchNorm-backward / moment / PReLU-apply reduction is asked for (bpart).  Returns the profile slot."""
-    if conv_c64p and C == 64 and N == 64 and W in (56, 112) and not (fused and stats) and not epilogue:
+def conv3x3_slot(M, W, C, N, fused=False, stats=False, epilogue=False, conv_c64p=1, nt_glds=4, bmom=False):
+    """gemm.hip: nt_pick for a 3x3 / stride-1 / pad-1 conv whose GEMM has K = 9 C and N output columns (forward: C = cin, N = cout;
+    dgrad: C = cout, N = cin).  fused: a BatchNorm-backward / moment / PReLU-apply reduction is asked for (bpart); bmom: it is one of the
+    latter two (GemmNT::bmom != 0).  Returns the profile slot."""
+    if conv_c64p and C == 64 and N == 64 and W in (56, 112) and not (fused and stats) and not epilogue and not bmom:
         return 15
     if nt_bm(M, N) == 128:
         if W == 112 and C == 64 and N == 64 and not fused:
@@ -675,7 +676,7 @@ SMALL = ("sparse6", "tol")      # epilogues that multiply the result again, and 
 
 def fused_rows(M, W, conv28_tpw2=2):
     """conv_glds_impl.h: launch_glds — one partial row per 196-pixel tile, per PAIR of tiles on the two-tiles 28x28 kernel
-    (gemm.hip: gemm_nt_fused28_two_tiles)"""
+    (gemm.hip: nt_pick)"""
     return M // 392 if (W == 28 and conv28_tpw2 >= 2 and (M // 196) % 2 == 0) else M // 196
 
 
@@ -805,14 +806,63 @@ def expected_slot(row, cus=256):
     if row.op.startswith("fwd"):
         M, N, C, W = B * Ho * Ho, Cout, Cin, H
         if k == 3 and s == 1:
-            return conv3x3_slot(M, W, C, N, fused=row.op == "fwd_moments", stats=row.op == "fwd_stats", epilogue=row.op == "fwd_epi", conv_c64p=c64p, nt_glds=ntg)
+            return conv3x3_slot(M, W, C, N, fused=row.op == "fwd_moments", stats=row.op == "fwd_stats", epilogue=row.op == "fwd_epi", conv_c64p=c64p, nt_glds=ntg,
+                                bmom=row.op == "fwd_moments")
         return 17 if nt_glds_applies(N, k * k * C, nt_glds=ntg) else nt_generic_slot(M, N)
     # dgrad: GEMM over K = k k Cout with N = Cin
     if k == 1:
         return nt_generic_slot(B * Ho * Ho, Cin)
     if s == 1:
-        return conv3x3_slot(B * H * H, H, Cout, Cin, fused=row.op != "dgrad", conv_c64p=c64p, nt_glds=ntg)
+        return conv3x3_slot(B * H * H, H, Cout, Cin, fused=row.op != "dgrad", conv_c64p=c64p, nt_glds=ntg, bmom=row.op == "dgrad_papply")
     par = row.opt("dgrad_parity", 2)
     if par:
         return nt_generic_slot(B * H * H // 4, Cin)
     return 17 if nt_glds_applies(Cin, 9 * Cout, nt_glds=ntg) else nt_generic_slot(B * H * H, Cin)
+
+
+# want bits of fedfr_conv2d_plan (include/fedfr_hip.h)
+WANT_STATS, WANT_BNBWD, WANT_MOMENTS, WANT_PAPPLY, WANT_EPILOGUE = 1, 2, 4, 8, 16
+ROW_WANT = {"fwd": 0, "fwd_stats": WANT_STATS, "fwd_moments": WANT_MOMENTS, "fwd_epi": WANT_EPILOGUE, "dgrad": 0, "dgrad_bnbwd": WANT_BNBWD,
+            "dgrad_papply": WANT_PAPPLY}
+
+
+def plan_wants(dgrad, k):
+    """the `want` values fedfr_conv2d_plan admits: the reductions exist for 3x3 convs only"""
+    if dgrad:
+        return (0, WANT_BNBWD, WANT_PAPPLY) if k == 3 else (0,)
+    return (0, WANT_STATS, WANT_MOMENTS, WANT_EPILOGUE) if k == 3 else (0, WANT_STATS, WANT_EPILOGUE)
+
+
+def plan_expected(B, H, Cin, Cout, k, s, dgrad, want, cus=256, conv_c64p=1, conv28_tpw2=2, nt_glds=4, dgrad_parity=2):
+    """what fedfr_conv2d_plan must answer — (profile slot, stat_rows, stat_rows_live, part_rows, out_epilogue) — put together from the
+    restated rules above alone.  The row counts are those of the GEMM problem that is launched: a 1x1 dgrad at the output resolution, a
+    stride-2 3x3 dgrad under dgrad_parity as one output-parity class (a quarter of the pixels)."""
+    Ho = H // s
+    stats, bnbwd, mom, pap, epi = (bool(want & b) for b in (WANT_STATS, WANT_BNBWD, WANT_MOMENTS, WANT_PAPPLY, WANT_EPILOGUE))
+    fused, par = bnbwd or mom or pap, False
+    if not dgrad:
+        M, N, C, K, same = B * Ho * Ho, Cout, Cin, k * k * Cin, k == 3 and s == 1
+    elif k == 1:
+        M, N, C, K, same = B * Ho * Ho, Cin, Cout, Cout, False
+    else:
+        M, N, C, K, same = B * H * H, Cin, Cout, 9 * Cout, s == 1
+        par = s == 2 and dgrad_parity > 0
+        M = M // 4 if par else M
+    if same:
+        slot = conv3x3_slot(M, H, C, N, fused=fused, stats=stats, epilogue=epi, conv_c64p=conv_c64p, nt_glds=nt_glds, bmom=mom or pap)
+    else:
+        slot = 17 if nt_glds_applies(N, K, par=par, epilogue=epi or fused, nt_glds=nt_glds) else nt_generic_slot(M, N)
+    rows = nt_stat_rows(M, N)
+    c64p = same and slot == 15 and conv_c64p and C == 64 and N == 64 and not epi           # (with the output epilogue: the LDS-DMA kernel)
+    two28 = slot == 13 and conv28_tpw2 and (M // 196) % 2 == 0 and not epi and (conv28_tpw2 >= 2 or (stats and not fused))
+    live, part = rows, 0
+    if c64p:
+        live, part = 2 * conv_c64p_grid(M, cus), conv_c64p_grid(M, cus) if bnbwd else 0
+    elif slot in (12, 13) and fused:
+        part = M // 196 // (2 if two28 and not stats else 1)
+    elif slot in (12, 13):
+        live = M // 196 // 2 if two28 else M // 196 * 2
+    # out_epilogue is a property of the CHOSEN kernel: a launch that asks for the epilogue gets conv_epilogue_ok; one that does not may run on
+    # the persistent 64-channel kernel or the two-tiles 28x28 kernel (both without it: False) — the kernels the dispatch chose for such launches before the plan existed
+    out_epi = same and conv_epilogue_ok(H, C, N, M, 3, 1) and not fused and not c64p and not two28
+    return slot, rows, live, part, out_epi

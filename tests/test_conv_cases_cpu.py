@@ -5,7 +5,12 @@ the GPU test builds, and its epilogue is exact in fp32 in both orders of the aff
 evaluation in plausible kernel orders (per tap, 64-channel chunks, split-K slabs added last, one partial row per tile, the kernels' algebraic form
 of the BatchNorm-backward rows) stays within a quarter of EVERY tolerance formula.  (5) Mutants: each corruption of the reference differs from it in
 at least one bit in the exact tier, and those that move a conv output also exceed the tolerance tier's bound; a 16-bit store that truncates
-exceeds it too, and so does an eval epilogue that rounds affine + identity once instead of twice."""
+exceeds it too, and so does an eval epilogue that rounds affine + identity once instead of twice.  (6) The library's own kernel selector
+(gemm.hip: gemm_nt_plan, asked through the host-only fedfr_conv2d_plan) agrees with the restated rules on the table and on a sweep across every threshold."""
+import contextlib
+import ctypes
+import itertools
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -48,7 +53,7 @@ def test_table_slots_follow_the_dispatch_rules():
     for r in TABLE:
         assert K.expected_slot(r) == r.slot, r.id
     assert {r.slot for r in TABLE} >= {0, 1, 2, 3, 4, 5, 6, 7, 12, 13, 14, 15, 16, 17}
-    for r in TABLE:                                   # ... and so do the literal statistics / partial row counts (gemm_nt_stat_rows_live, launch_glds, conv_c64p_grid)
+    for r in TABLE:                                   # ... and so do the literal statistics / partial row counts (gemm_nt_plan, launch_glds, launch_c64p)
         assert K.expected_rows(r) == r.rows, (r.id, r.rows, K.expected_rows(r))
 
 
@@ -325,3 +330,77 @@ def test_mutants_show(s16):
     cnt = K.conv_ref(torch.zeros(1, 6, 6, 1), torch.ones(1, 3, 3, 1), 2, f64, "cpu", dy=torch.ones(1, 3, 3, 1), want=("dx",))["dx"][0, :, :, 0]
     assert cnt[0::2, 0::2].unique().tolist() == [1.0] and sorted(cnt[1::2, 1::2].unique().tolist()) == [1.0, 2.0, 4.0]
     assert sorted(cnt[0::2, 1::2].unique().tolist()) == [1.0, 2.0] and sorted(cnt[1::2, 0::2].unique().tolist()) == [1.0, 2.0]
+
+
+# ------------------------------------------------------------------------------------------------ 6. the library's selector against the restated rules
+@pytest.fixture(scope="module")
+def built_lib():
+    import __graft_entry__ as ge
+    ge.build()
+    from fedfr_amd import _C
+    return _C
+
+
+def _plan(lib, B, H, Cin, Cout, k, s, dgrad, want):
+    out = [ctypes.c_int(-1) for _ in range(5)]
+    rc = lib.fedfr_conv2d_plan(B, H, Cin, Cout, k, s, dgrad, want, *[ctypes.byref(v) for v in out])
+    assert rc == 0, (rc, lib.fedfr_last_error_string(), (B, H, Cin, Cout, k, s, dgrad, want))
+    return out[0].value, out[1].value, out[2].value, out[3].value, bool(out[4].value)
+
+
+def test_plan_query_agrees_with_the_restated_rules(built_lib):
+    """fedfr_conv2d_plan (no device: the persistent kernel is planned for 256 compute units) == conv_cases.plan_expected: slot, stat_rows,
+    stat_rows_live, part_rows and out_epilogue, for every NT row of the table under its options and for the sweep of the issue."""
+    _C, lib = built_lib, built_lib.lib()
+    names = ("conv_c64p", "conv28_tpw2", "nt_glds", "dgrad_parity")
+
+    def scope(vals):
+        st = contextlib.ExitStack()
+        for n, v in zip(names, vals):
+            st.enter_context(_C.option_scope(n, v))
+        return st
+
+    # ---- the table: the plan gives each row's literal slot and row count
+    nrows = 0
+    for r in TABLE:
+        if r.op.startswith("wgrad"):
+            continue
+        B, H, Cin, Cout, k, s = r.shape
+        dgrad, want = int(r.op.startswith("dgrad")), K.ROW_WANT[r.op]
+        opts = tuple(r.opt(n, d) for n, d in zip(names, (1, 2, 4, 2)))
+        with scope(opts):
+            got = _plan(lib, B, H, Cin, Cout, k, s, dgrad, want)
+            assert got == K.plan_expected(B, H, Cin, Cout, k, s, dgrad, want, 256, *opts), (r.id, got)
+            assert got[0] == r.slot, (r.id, got)
+            if r.op in ("fwd_moments", "dgrad_bnbwd", "dgrad_papply"):
+                assert got[3] == r.rows, (r.id, got)
+            if r.op == "fwd_epi":
+                assert got[4] and got[4] == K.conv_epilogue_ok(H, Cin, Cout, B * H * H, k, s), (r.id, got)
+            if r.rows is not None and r.op in ("fwd", "fwd_stats"):      # (a plain "fwd" row with a row count is launched once more with statistics)
+                live = _plan(lib, B, H, Cin, Cout, k, s, 0, K.WANT_STATS)
+                assert live[2] == r.rows and live[1] == K.nt_stat_rows(B * (H // s) ** 2, Cout), (r.id, live)
+        nrows += 1
+    assert nrows >= 70
+    # ---- the sweep: both sides of every batch threshold of test_batches_sit_on_the_thresholds, every option value, every want an op admits
+    batches = sorted({124, 125, 250, 251, 62, 63, 15, 16, 3, 4} | set(K.c64p_batches(56, 256)) | set(K.c64p_batches(112, 256)))
+    chans = (64, 128, 192, 256, 512)
+    ops = [(dgrad, k, w) for dgrad in (0, 1) for k in (3, 1) for w in K.plan_wants(dgrad, k)]
+    seen_slots, ncases = set(), 0
+    for opts in itertools.product((0, 1), (0, 1, 2), (0, 4, 12), (0, 2)):
+        with scope(opts):
+            for H, s in itertools.product((7, 14, 28, 56, 112), (1, 2)):
+                if H % s:                                   # (7x7 / stride 2 is no geometry of the library: conv_args_ok)
+                    continue
+                for Cin, Cout, B, (dgrad, k, want) in itertools.product(chans, chans, batches, ops):
+                    got = _plan(lib, B, H, Cin, Cout, k, s, dgrad, want)
+                    assert got == K.plan_expected(B, H, Cin, Cout, k, s, dgrad, want, 256, *opts), ((B, H, Cin, Cout, k, s, dgrad, want), opts, got)
+                    if want & K.WANT_EPILOGUE:              # a launch that asks for the output epilogue: the persistent kernel steps aside
+                        assert got[4] == K.conv_epilogue_ok(H, Cin, Cout, B * (H // s) ** 2, k, s)
+                    seen_slots.add(got[0])
+                    ncases += 1
+    assert seen_slots == {0, 1, 2, 3, 12, 13, 15, 17} and ncases > 10 ** 6
+    # what the entry point refuses: epilogues of the other direction, reductions of a 1x1 conv, a geometry the library has none of
+    out = [ctypes.byref(ctypes.c_int()) for _ in range(5)]
+    for bad in ((4, 14, 128, 128, 3, 1, 0, K.WANT_BNBWD), (4, 14, 128, 128, 3, 1, 1, K.WANT_STATS), (4, 14, 128, 128, 1, 1, 0, K.WANT_MOMENTS),
+                (4, 7, 128, 128, 3, 2, 0, 0), (4, 14, 128, 128, 3, 1, 0, 32)):
+        assert lib.fedfr_conv2d_plan(*bad, *out) == -1 and b"conv2d" in lib.fedfr_last_error_string(), bad

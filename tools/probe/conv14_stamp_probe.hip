@@ -74,11 +74,13 @@ int main(int argc, char** argv) {
   hipEvent_t e0, e1;
   CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
   const int reps = 50;
+  NtPlan plan{};                                          // (the launcher checks its partial-row count against the plan's)
+  plan.part_rows = PROBE_FUSED ? M / 196 / (PROBE_W == 14 ? 1 : 2) : 0;
   auto launch = [&]() {
 #if PROBE_W == 14
-    return launch_glds<14, 14, 32, 4, PROBE_FUSED != 0>(p, st);
+    return launch_glds<14, 14, 32, 4, PROBE_FUSED != 0>(p, plan, st);
 #else
-    return launch_glds<28, 7, 40, 4, PROBE_FUSED != 0, 128, false, 2>(p, st);
+    return launch_glds<28, 7, 40, 4, PROBE_FUSED != 0, 128, false, 2>(p, plan, st);
 #endif
   };
   for (int i = 0; i < 10; ++i) if (launch()) { printf("launch refused\n"); return 1; }
