@@ -36,6 +36,9 @@ SIGNATURES = {
     "fedfr_block_create": (vp, [i32, i32, i32, i32, i32]),
     "fedfr_net_create_sphere": (vp, [i32, i32]),
     "fedfr_net_debug_capture": (i32, [vp, sz]),
+    "fedfr_net_debug_capture_detail": (i32, [i32]),
+    "fedfr_net_debug_capture_elems": (i32, [vp, i32, C.POINTER(i64)]),
+    "fedfr_net_bn_info": (i32, [vp, i32, C.c_char_p, i32, C.POINTER(i32), C.POINTER(i64)]),
     "fedfr_net_set_dropout": (i32, [vp, f32, u64, C.POINTER(i64)]),
     "fedfr_net_set_dropout_step": (i32, [vp, u64]),
     "fedfr_net_destroy": (None, [vp]),
@@ -179,7 +182,7 @@ SIGNATURES = {
 
 # query keys (include/fedfr_hip.h)
 Q_PARAM_COUNT, Q_TRAINABLE_COUNT, Q_BUFFER_COUNT, Q_NBT_COUNT, Q_SHADOW_COUNT, Q_ACT_BYTES, Q_WS_BYTES, \
-    Q_NUM_TENSORS, Q_FC_IN = range(9)
+    Q_NUM_TENSORS, Q_FC_IN, Q_NUM_BN, Q_ACT_FLOAT_OFF_BYTES = range(11)
 
 
 def lib() -> C.CDLL:

@@ -185,6 +185,53 @@ int fedfr_net_debug_capture(uint16_t* buf, size_t elems) {
   g_dbg_grads_elems = buf ? elems : 0;
   return FEDFR_OK;
 }
+extern int g_dbg_detail;
+int fedfr_net_debug_capture_detail(int level) {
+  FEDFR_REQUIRE(level == 0 || level == 1, "net_debug_capture_detail: level is 0 (the gradient entering every block) or 1 (+ the block's intermediate gradients), got %d", level);
+  g_dbg_detail = level;
+  return FEDFR_OK;
+}
+int fedfr_net_debug_capture_elems(const fedfr_net_t* n, int level, long long* elems) {
+  FEDFR_REQUIRE(n && elems, "net_debug_capture_elems: null");
+  FEDFR_REQUIRE(!n->sph_type, "net_debug_capture_elems: iresnet plans only (a sphnet plan captures one tensor per PReLU pass, see fedfr_net_debug_capture)");
+  FEDFR_REQUIRE(level == 0 || level == 1, "net_debug_capture_elems: level is 0 or 1, got %d", level);
+  long long e = (level && !n->block_only) ? (long long)n->B * n->final_hw * n->final_hw * n->final_C : 0;      // the gradient entering bn2's backward
+  for (const auto& k : n->blocks) {
+    const long long Mi = (long long)n->B * k.Hin * k.Hin, Mo = (long long)n->B * k.Hout * k.Hout;
+    e += Mo * k.Cout;                                                    // g
+    if (level) {
+      e += Mo * k.Cout + 2 * Mi * k.Cout + Mi * k.Cin;                   // dc2, da2, dc1, da1
+      if (k.has_ds) e += Mo * k.Cout + Mo * k.Cin;                       // dd, dxd
+    }
+  }
+  *elems = e + (long long)n->B * n->HW * n->HW * n->blocks.front().Cin;  // the gradient wrt the first block's input
+  return FEDFR_OK;
+}
+int fedfr_net_bn_info(const fedfr_net_t* n, int i, char* name, int name_cap, int* C, long long* save_offset_floats) {
+  FEDFR_REQUIRE(n && name && name_cap > 0 && C && save_offset_floats, "net_bn_info: bad args");
+  FEDFR_REQUIRE(!n->sph_type, "net_bn_info: a sphnet plan has no BatchNorm");
+  // the plan's own descriptors, in the order net_create / net_create_block add them; the names are those of the running_mean entries, which the
+  // same add_bn calls appended in the same order (the features' BatchNorm1d, last in a network plan, is not among the descriptors)
+  std::vector<const BnD*> bns;
+  if (!n->block_only) bns.push_back(&n->stem_bn);
+  for (const auto& k : n->blocks) {
+    bns.push_back(&k.bn1); bns.push_back(&k.bn2); bns.push_back(&k.bn3);
+    if (k.has_ds) bns.push_back(&k.bnds);
+  }
+  if (!n->block_only) bns.push_back(&n->bn2);
+  FEDFR_REQUIRE(i >= 0 && i < (int)bns.size(), "net_bn_info: the plan has BatchNorms 0..%d (got %d)", (int)bns.size() - 1, i);
+  int seen = 0;
+  for (const auto& t : n->tensors) {
+    if (t.kind != 6 || seen++ != i) continue;
+    FEDFR_REQUIRE(t.shape[0] == bns[i]->C && t.offset == bns[i]->rm_off, "net_bn_info: tensor list and BatchNorm descriptors disagree at %d", i);
+    const std::string base = t.name.substr(0, t.name.size() - sizeof(".running_mean") + 1);
+    snprintf(name, name_cap, "%s", base.c_str());
+    *C = bns[i]->C; *save_offset_floats = bns[i]->save_off;
+    return FEDFR_OK;
+  }
+  fedfr_set_error("net_bn_info: no running_mean entry for BatchNorm %d", i);
+  return FEDFR_ERR_ARG;
+}
 int fedfr_net_set_dropout(fedfr_net_t* n, float p, unsigned long long seed, long long* mask_offset_bytes) {
   FEDFR_REQUIRE(n && !n->block_only && p >= 0.f && p < 1.f, "net_set_dropout: need a network plan and 0 <= p < 1");
   FEDFR_REQUIRE(((size_t)n->B * n->fc_in) % 8 == 0, "net_set_dropout: batch * fc_in must be a multiple of 8");
@@ -216,6 +263,13 @@ int fedfr_net_query(const fedfr_net_t* n, int what, long long* out) {
     case FEDFR_Q_WS_BYTES: *out = (long long)n->ws_bytes; break;
     case FEDFR_Q_NUM_TENSORS: *out = (long long)n->tensors.size(); break;
     case FEDFR_Q_FC_IN: *out = n->fc_in; break;
+    case FEDFR_Q_NUM_BN: {
+      long long c = 0;
+      for (const auto& t : n->tensors) c += t.kind == 6;
+      *out = n->sph_type ? 0 : c - (n->block_only ? 0 : 1);
+      break;
+    }
+    case FEDFR_Q_ACT_FLOAT_OFF_BYTES: *out = n->act_float_off_bytes; break;
     default: fedfr_set_error("net_query: unknown key %d", what); return FEDFR_ERR_ARG;
   }
   return FEDFR_OK;

@@ -631,6 +631,9 @@ int net_forward(const FedfrNet* n, const float* x, const float* params, float* b
 // and finally the gradient wrt the first block's input, back to back into this caller-owned device buffer
 bf16_t* g_dbg_grads = nullptr;
 size_t g_dbg_grads_elems = 0;
+// detail level 1: in front of everything the gradient wrt the network's bn2 output (NHWC [B*hw][C]), and behind every block's entering gradient g also dc2, da2, dc1, (dd, dxd of a downsample block,) da1, each copied on the main stream
+// right behind the kernel that produced it (dxd is the compact [B*Hout*Hout][Cin] result the bn1 pass up-samples).  Level 0: g alone
+int g_dbg_detail = 0;
 static int dbg_capture(const bf16_t* src, size_t elems, size_t* off, hipStream_t st) {
   if (!g_dbg_grads) return FEDFR_OK;
   FEDFR_REQUIRE(*off + elems <= g_dbg_grads_elems, "net_backward: debug gradient buffer too small (%zu + %zu > %zu elements)", *off, elems,
@@ -750,6 +753,7 @@ int net_backward(const FedfrNet* n, const float* x, const float* dfeats, const f
   const hipStream_t wst = aux ? aux : st;          // stream of the weight-gradient GEMMs
   if (n->block_only) fk.order(st, wst);             // aux starts after everything already queued on main (forward pass); the full net forks below
   Rows pend{nullptr, 0};                           // partial rows of the next bn3 already reduced by the apply pass that produced its dy
+  size_t dbg_off = 0;
   if (n->block_only) {
     const BlockD& k0 = n->blocks.front();
     FEDFR_TRY(ew_nchw_f32_to_nhwc_bf16(dfeats, c.g(1), B, k0.Cout, k0.Hout * k0.Hout, st));      // dy of the block, fp32 NCHW like the reference's
@@ -782,10 +786,10 @@ int net_backward(const FedfrNet* n, const float* x, const float* dfeats, const f
   const int hw = n->final_hw * n->final_hw, Mf = B * hw;
   if (n->dropout_p > 0.f) FEDFR_TRY(ew_dropout_bwd(dxfc, act + n->mask_off_bytes, (size_t)B * n->fc_in, n->dropout_p, st));
   FEDFR_TRY(ew_nchw_f32_to_nhwc_bf16(dxfc, c.g(0), B, n->final_C, hw, st));
+  if (g_dbg_grads && g_dbg_detail) FEDFR_TRY(dbg_capture(c.g(0), (size_t)Mf * n->final_C, &dbg_off, st));      // detail: the gradient entering bn2's backward, first
   FEDFR_TRY(bn_bwd(c, n->bn2, nullptr, c.g(0), A + last.out_off, Mf, nullptr, nullptr, 0, c.g(1), 0, Rows{nullptr, 0}, &last.bn3, A + last.c2_off, &pend));
   }
   int cur = 1;
-  size_t dbg_off = 0;
   // fused SGD (NetSgd): [sgd_lo, sgd_hi) = parameter range whose gradients are complete on the main stream and whose weight gradients are
   // all queued on the weight-gradient stream; it is updated there behind the next fork (which orders it after everything queued on main).
   // Nothing reads those parameters again in this pass: dgrad uses the bf16 shadows, BatchNorm backward its own layer's gamma / slope.
@@ -814,18 +818,25 @@ int net_backward(const FedfrNet* n, const float* x, const float* dfeats, const f
     bf16_t* gin = c.g(cur ^ 1);
     FEDFR_TRY(dbg_capture(g, (size_t)Mo * k.Cout, &dbg_off, st));
     bf16_t *dc2 = c.tw(0, par), *da2 = c.t(1), *dc1 = c.tw(1, par), *da1 = c.t(3), *dd = c.tw(2, par), *dxd = c.t(5);
+    auto detail = [&](const bf16_t* src, size_t elems) -> int {      // (no capture buffer or level 0: no launch)
+      return g_dbg_grads && g_dbg_detail ? dbg_capture(src, elems, &dbg_off, st) : FEDFR_OK;
+    };
     fk.wait(st, wdone[par]);                         // the weight GEMMs kWgradDepth blocks ago were the last readers of dc2/dc1/dd[par]
     // out = bn3(c2) + identity
     FEDFR_TRY(bn_bwd(c, k.bn3, nullptr, g, A + k.c2_off, Mo, nullptr, nullptr, 0, dc2, 0, pend));
+    FEDFR_TRY(detail(dc2, (size_t)Mo * k.Cout));
     pend = Rows{nullptr, 0};
     int f2 = 0, f1 = 0;
     FEDFR_TRY(conv_dgrad(c, k.conv2, dc2, da2, &k.bn2, A + k.c1_off, params + k.alpha_off, &f2));
+    FEDFR_TRY(detail(da2, (size_t)Mi * k.Cout));
     // a2 = prelu(bn2(c1))
     FEDFR_TRY(bn_bwd(c, k.bn2, params + k.alpha_off, da2, A + k.c1_off, Mi, nullptr, nullptr, 0, dc1, k.alpha_off, Rows{c.part(), f2}));
+    FEDFR_TRY(detail(dc1, (size_t)Mi * k.Cout));
     // identity path first (its BN reduction uses the shared partial buffer), then conv1's dgrad whose epilogue may
     // leave bn1's partial sums there for the bn_bwd that follows immediately
     if (k.has_ds) {
       FEDFR_TRY(bn_bwd(c, k.bnds, nullptr, g, A + k.d_off, Mo, nullptr, nullptr, 0, dd, 0));
+      FEDFR_TRY(detail(dd, (size_t)Mo * k.Cout));
     }
     // ONE fork per block: every event record costs the main stream a ~8 us bubble (kernel trace), so the block's two or three
     // weight-gradient GEMMs are released together once their last operand (dc2, dc1, dd) exists
@@ -837,9 +848,11 @@ int net_backward(const FedfrNet* n, const float* x, const float* dfeats, const f
       FEDFR_TRY(wgrad_flush(c, &pend_w, wst));
       FEDFR_TRY(conv_wgrad(c, k.ds, A + k.x_off, dd, wst));
       FEDFR_TRY(conv_dgrad(c, k.ds, dd, dxd));
+      FEDFR_TRY(detail(dxd, (size_t)Mo * k.Cin));
     }
     wdone[par] = fk.mark(wst);
     FEDFR_TRY(conv_dgrad(c, k.conv1, dc1, da1, &k.bn1, A + k.x_off, nullptr, &f1));
+    FEDFR_TRY(detail(da1, (size_t)Mi * k.Cin));
     // a1 = bn1(x)
     const BlockD* prev = bi > 0 ? &n->blocks[bi - 1] : nullptr;      // its bn3 consumes gin next
     if (k.has_ds && !prev && !n->block_only && g_stem_bnred) {

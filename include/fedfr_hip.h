@@ -108,6 +108,21 @@ int fedfr_net_set_dropout_step(fedfr_net_t* net, unsigned long long step);
  * the last to the first, its blocks from the last to the first, then its head (sphere20: 12 tensors, sphere64: 33).  With buf == NULL the pass
  * enqueues exactly what it enqueues without the hook. */
 int fedfr_net_debug_capture(uint16_t* buf, size_t elems);
+/* debug (tests), iresnet plans: what fedfr_net_debug_capture copies.  Level 0 (the default): as above.  Level 1: directly behind every block's
+ * entering gradient also the block's intermediate gradients, each copied right behind the kernel that produced it: dc2 [B*Ho*Ho][Cout] (wrt conv2's
+ * output), da2 [B*Hi*Hi][Cout] (wrt prelu(bn2)), dc1 [B*Hi*Hi][Cout] (wrt conv1's output), for a downsample block dd [B*Ho*Ho][Cout] (wrt the
+ * downsample conv's output) and dxd [B*Ho*Ho][Cin] (its dgrad: compact, the bn1 backward pass places it at the even pixels), then da1
+ * [B*Hi*Hi][Cin] (wrt bn1's output); and in FRONT of everything the gradient wrt the network's bn2 output, NHWC [B*hw][final_C], final_C the last
+ * stage's planes (what the fc's input gradient becomes before bn2's backward).  Process-global like the buffer; without a buffer no level enqueues anything. */
+int fedfr_net_debug_capture_detail(int level);
+/* host-only: the 16-bit elements a backward pass of `net` captures at `level` (the size fedfr_net_debug_capture's buffer needs) */
+int fedfr_net_debug_capture_elems(const fedfr_net_t* net, int level, long long* elems);
+/* host-only, iresnet plans: the i-th 2-D BatchNorm in state_dict order (FEDFR_Q_NUM_BN of them: the stem's, per block bn1, bn2, bn3 and the
+ * downsample's, the network's bn2) — its state_dict prefix, channel count, and where a training forward leaves its four rows of C floats
+ * (scale, shift, mean, rstd): a float offset from byte FEDFR_Q_ACT_FLOAT_OFF_BYTES of `act`.  Behind the last BatchNorm's rows a network plan keeps 4 * F
+ * floats for the features' BatchNorm1d, then the fc output [batch][F] and that BatchNorm1d's (mean, rstd) [2][F].  A sphnet plan has none: an
+ * argument error. */
+int fedfr_net_bn_info(const fedfr_net_t* net, int i, char* name, int name_cap, int* C, long long* save_offset_floats);
 enum {
   FEDFR_Q_PARAM_COUNT = 0,      /* fp32 elements: trainable region + frozen features.weight */
   FEDFR_Q_TRAINABLE_COUNT = 1,
@@ -117,7 +132,9 @@ enum {
   FEDFR_Q_ACT_BYTES = 5,
   FEDFR_Q_WS_BYTES = 6,
   FEDFR_Q_NUM_TENSORS = 7,
-  FEDFR_Q_FC_IN = 8
+  FEDFR_Q_FC_IN = 8,
+  FEDFR_Q_NUM_BN = 9,                /* 2-D BatchNorms fedfr_net_bn_info answers for */
+  FEDFR_Q_ACT_FLOAT_OFF_BYTES = 10   /* byte offset of the float region (BatchNorm save rows first) inside `act` */
 };
 int fedfr_net_query(const fedfr_net_t* net, int what, long long* out);
 /* state_dict entry i (reference key order).  kind: 0 conv 1 bn.weight 2 bn.bias 3 prelu 4 fc.weight

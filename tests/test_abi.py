@@ -185,6 +185,51 @@ def test_sphere_plan_selectors_and_fp32_path_refusal(built_lib):
         lib.fedfr_net_destroy(h)
 
 
+def test_debug_capture_detail_and_bn_info_are_host_only_and_check_their_arguments(built_lib):
+    """Host-only: fedfr_net_debug_capture_elems sizes the capture buffer of either detail level from the block table, fedfr_net_bn_info lists the 2-D
+    BatchNorms in state_dict order with the offsets of their save rows; bad levels, indices, null pointers and sphnet plans are argument errors with a message."""
+    import ctypes as C
+    import iresnet_cases as IC
+    lib = built_lib.lib()
+    err_arg = int(re.search(r"#define FEDFR_ERR_ARG \((-?\d+)\)", open(HEADER).read()).group(1))
+    q, c, off, name = C.c_longlong(), C.c_int(), C.c_longlong(), C.create_string_buffer(64)
+    for layers, B in (((2, 2, 2, 2), 5), ((1, 1, 3, 1), 2)):
+        h = lib.fedfr_net_create((C.c_int * 4)(*layers), B, 112, 512)
+        assert h
+        net = IC.Net(layers, B)
+        want0 = sum(B * b.hout * b.hout * b.cout for b in net.blocks) + B * 112 * 112 * 64
+        want1 = want0 + B * net.hw * net.C + sum(B * (b.hout * b.hout * b.cout + 2 * b.hin * b.hin * b.cout + b.hin * b.hin * b.cin +
+                                 (b.hout * b.hout * (b.cout + b.cin) if b.has_ds else 0)) for b in net.blocks)
+        for level, want in ((0, want0), (1, want1)):
+            assert lib.fedfr_net_debug_capture_elems(h, level, C.byref(q)) == 0 and q.value == want, (level, q.value, want)
+        for level in (-1, 2):
+            assert lib.fedfr_net_debug_capture_elems(h, level, C.byref(q)) == err_arg and b"net_debug_capture_elems" in lib.fedfr_last_error_string()
+            assert lib.fedfr_net_debug_capture_detail(level) == err_arg and b"net_debug_capture_detail" in lib.fedfr_last_error_string()
+        assert lib.fedfr_net_debug_capture_elems(h, 0, None) == err_arg and lib.fedfr_net_debug_capture_elems(None, 0, C.byref(q)) == err_arg
+        assert lib.fedfr_net_debug_capture_detail(1) == 0 and lib.fedfr_net_debug_capture_detail(0) == 0
+        table = net.bn_table()
+        assert lib.fedfr_net_query(h, built_lib.Q_NUM_BN, C.byref(q)) == 0 and q.value == len(table)
+        want_off = 0
+        for i, (n, ch) in enumerate(table):
+            assert lib.fedfr_net_bn_info(h, i, name, 64, C.byref(c), C.byref(off)) == 0
+            assert (name.value.decode(), c.value, off.value) == (n, ch, want_off), (i, name.value, c.value, off.value)
+            want_off += 4 * ch
+        assert lib.fedfr_net_query(h, built_lib.Q_ACT_FLOAT_OFF_BYTES, C.byref(q)) == 0 and q.value % 256 == 0 and q.value > 0
+        assert lib.fedfr_net_query(h, built_lib.Q_ACT_BYTES, C.byref(off)) == 0 and q.value + 4 * (want_off + 4 * 512 + B * 512 + 2 * 512) <= off.value
+        for i in (-1, len(table)):
+            assert lib.fedfr_net_bn_info(h, i, name, 64, C.byref(c), C.byref(off)) == err_arg and b"net_bn_info" in lib.fedfr_last_error_string()
+        assert lib.fedfr_net_bn_info(h, 0, None, 64, C.byref(c), C.byref(off)) == err_arg
+        assert lib.fedfr_net_bn_info(h, 0, name, 0, C.byref(c), C.byref(off)) == err_arg
+        assert lib.fedfr_net_bn_info(h, 0, name, 64, None, C.byref(off)) == err_arg
+        lib.fedfr_net_destroy(h)
+    h = lib.fedfr_net_create_sphere(20, 2)
+    assert h
+    assert lib.fedfr_net_query(h, built_lib.Q_NUM_BN, C.byref(q)) == 0 and q.value == 0
+    assert lib.fedfr_net_bn_info(h, 0, name, 64, C.byref(c), C.byref(off)) == err_arg and b"sphnet" in lib.fedfr_last_error_string()
+    assert lib.fedfr_net_debug_capture_elems(h, 0, C.byref(q)) == err_arg and b"sphnet" in lib.fedfr_last_error_string()
+    lib.fedfr_net_destroy(h)
+
+
 def test_sphnet_refuses_the_fp32_validation_switch(built_lib):
     """`validation_fp32` is IResNet's: a sphnet raises when it is set, before the library is ever called with a sphere plan."""
     from fedfr_amd import backbones

@@ -1733,7 +1733,11 @@ def test_every_switch_alternative_matches_the_default(name):
     """iresnet18 at batch 128 (every map size of the step: 112 / 56 / 28 / 14 / 7, the LDS-DMA conv kernels, the persistent 64-channel kernel, paired
     and single nine-tap weight gradients, sliced and row-slab BatchNorm passes): one training step under each alternative setting of the switch
     against the default selection — the same loss and the same gradients up to what a different summation order or 16-bit rounding point may do
-    (scheduling-only switches: the same bits)."""
+    (scheduling-only switches: the same bits).
+    wgrad9p_bg is INERT on iresnet18: every stage is a downsample block and one identity block, so a paired launch's pending slab sums are always
+    flushed by the unpaired launches of the block in front of it and no paired launch is ever asked to carry a job (iresnet_cases.Net.wgrad_walk,
+    held to that at every batch by tests/test_iresnet_cases_cpu.py) — its row compares two identical launch sequences.  The carry is exercised by
+    the (1, 1, 3, 1) cases of tests/test_iresnet_units_gpu.py."""
     B, C = 128, 64
     ref = _switch_step("iresnet18", B, C)
     gn = float(ref[1].norm())
