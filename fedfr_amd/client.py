@@ -1122,6 +1122,25 @@ class Client(object):
             comp = self.sparsifier = TopKCompressor(ratio, error_feedback)
         return comp.compress(global_state, self.backbone_state_dict)
 
+    def secagg_client(self, sid, frac_bits=24, rng=None):
+        """The client's ``secagg.SecAggClient`` under the protocol id ``sid`` (the server's index of this client): created on first use
+        and again whenever ``sid`` or ``frac_bits`` differs from the one it holds; its secrets are drawn per round (``begin_round``)."""
+        from .secagg import SecAggClient
+        sa = getattr(self, "secagg", None)
+        if sa is None or sa.cid != int(sid) or sa.frac_bits != int(frac_bits) or sa.rng is not rng:
+            sa = self.secagg = SecAggClient(sid, frac_bits, rng)
+        return sa
+
+    @_C.on_device(lambda self: self.device)
+    def get_masked_update(self, global_state, weight, participants, public_keys, round):
+        """The trained state as a masked upload against ``global_state`` (the state the round started from): ``secagg.MaskedUpdate``, the
+        fixed-point update at the client's public weight ``weight`` = n_i / Σn under the pair masks with every other participant and the
+        client's self mask, from the secrets of ``secagg_client(...).begin_round(round)``.  One kernel pass."""
+        sa = getattr(self, "secagg", None)
+        if sa is None:
+            raise RuntimeError("Client.get_masked_update: secagg_client(...).begin_round(round) first")
+        return sa.mask(global_state, self.backbone_state_dict, weight, participants, public_keys, round)
+
     def get_global_fc(self):
         return self.fc_module.get_pretrain_fc()
 

@@ -13,6 +13,7 @@
 #include "compress.h"
 #include "sparse.h"
 #include "dp.h"
+#include "secagg.h"
 
 static thread_local char g_err[512] = "";
 extern int g_tn_use_tr;
@@ -930,6 +931,18 @@ int fedfr_dp_multi(int kind, float* x_out, const float* x, const float* const* x
                    void* stream) {
   return dp_multi(kind, x_out, x, xs, coef, k, n, m, v, delta_scratch, first, last, lr, beta1, one_minus_beta1, beta2, one_minus_beta2, tau,
                   noise_std, seed, round, stream_id, offset, ST(stream));
+}
+int fedfr_chacha20_fill(unsigned* dst, size_t n, const unsigned* key, unsigned counter0, const unsigned* nonce, void* stream) {
+  return secagg_chacha20_fill(dst, n, key, counter0, nonce, ST(stream));
+}
+int fedfr_secagg_mask(unsigned* y, const float* x, const float* xi, float coef, int limit, const unsigned* keys, const unsigned* nonces,
+                      const int* signs, int k, size_t n, int* counters, void* stream) {
+  return secagg_mask(y, x, xi, coef, limit, keys, nonces, signs, k, n, counters, ST(stream));
+}
+int fedfr_secagg_aggregate(float* out, const float* x, unsigned* acc, const unsigned* const* ys, int ku, const unsigned* keys,
+                           const unsigned* nonces, const int* signs, int k, int frac_bits, float rescale, size_t n, int first, int last,
+                           void* stream) {
+  return secagg_aggregate(out, x, acc, ys, ku, keys, nonces, signs, k, frac_bits, rescale, n, first, last, ST(stream));
 }
 int fedfr_robust_trimmed_mean(float* dst, const float* const* srcs, int k, int trim, size_t n, void* stream) {
   return robust_trimmed_mean(dst, srcs, k, trim, n, ST(stream));

@@ -5,7 +5,8 @@ xGMI when every client is its own rank (one client = one MI355X); the spread-out
 checkpoints (reference server.py:135-148).  Build extensions beyond the reference's FedAvg: the server optimisers (``FedOpt``), the
 robust rules (``FedRobust``: coordinate-wise trimmed mean / median, Krum / Multi-Krum) and compressed client uploads (``FedCompressed``:
 8 / 4-bit block-scaled deltas with error feedback; ``FedSparse``: top-k sparsified deltas with error feedback; see compress.py) and
-client-level differential privacy (``FedDP``: clipped updates and Gaussian noise drawn on the device; see privacy.py)."""
+client-level differential privacy (``FedDP``: clipped updates and Gaussian noise drawn on the device; see privacy.py) and secure
+aggregation (``FedSecAgg``: pairwise-masked fixed-point uploads of which the server learns only the sum; see secagg.py)."""
 from __future__ import annotations
 
 import copy
@@ -490,6 +491,61 @@ def FedCompressed(global_state, updates, weights: Sequence[float], server_opt=No
     return FlatStateDict.from_flat((P, *stats), global_state.table, global_state.layers)
 
 
+# ---- secure aggregation: csrc/secagg.hip secagg_mask_kernel (client side, secagg.py) / secagg_aggregate_kernel
+def FedSecAgg(global_state, uploads, weights: Sequence[float], recovery_streams, rescale: float = 1.0, server_opt=None):
+    """One round from masked uploads (``secagg.MaskedUpdate``, all of one ``frac_bits``): the PARAMETERS of the new global state are
+    x + float(int32(S)) 2^-f rescale with x = ``global_state``'s parameters and S = Σ_i y_i + Σ_r sign_r m_r mod 2^32 over the uploads
+    and the ``recovery_streams`` ([(8 key words, 3 nonce words, sign)], ``secagg.SecAggServer.recovery_streams``), which cancel what the
+    uploads' masks leave (fedfr_secagg_aggregate: ≤ 8 uploads and ≤ 32 streams per pass, every upload word read once; more chain passes
+    through an integer buffer, and x is added by the last pass only.  Addition mod 2^32 has one result whatever the order).  ``rescale`` is
+    fp32(1 / Σ of the survivors' public weights), 1.0 when nobody dropped (``secagg.survivor_rescale``).  With ``server_opt`` (a
+    ``ServerOptimizer``) the same sum WITHOUT x is the pseudo-gradient Δ and goes through ``server_opt.apply_delta``; ``clip_norm`` > 0
+    raises ``ValueError`` (the clip needs per-client norms, which masked uploads hide by design).  BN running statistics and
+    ``num_batches_tracked`` arrive UNMASKED and are averaged over the uploads with ``weights`` exactly as ``FedPavg`` averages them.  Only a
+    GPU ``FlatStateDict`` is accepted as ``global_state``."""
+    from .secagg import MaskedUpdate, stream_arrays
+    if not isinstance(global_state, FlatStateDict) or global_state.flat is None:
+        raise RuntimeError("fedfr_amd.FedSecAgg: the global state must be a FlatStateDict (client.flat_state_dict)")
+    if not uploads or not all(isinstance(u, MaskedUpdate) for u in uploads):
+        raise RuntimeError("fedfr_amd.FedSecAgg: the client uploads must be MaskedUpdates (Client.get_masked_update)")
+    if len(weights) != len(uploads):
+        raise RuntimeError("fedfr_amd.FedSecAgg: %d weights for %d client uploads" % (len(weights), len(uploads)))
+    if isinstance(server_opt, RobustAggregator):
+        raise ValueError("FedSecAgg: a robust rule (%s) needs whole client states, which masked uploads hide" % server_opt.kind)
+    if server_opt is not None and server_opt.clip_norm > 0:
+        raise ValueError("FedSecAgg: clip_norm > 0 needs per-client norms of the updates, which masked uploads hide by design")
+    rescale = float(np.float32(rescale))
+    if not (np.isfinite(rescale) and rescale >= 1.0):
+        raise ValueError("FedSecAgg: rescale is fp32(1 / sum of the survivors' weights), a finite number >= 1 (got %r)" % (rescale,))
+    tot = sum(weights)
+    ws = [w / tot for w in weights]
+    x = global_state.flat[0]
+    _check_states(x, [], "FedSecAgg")
+    n, frac_bits = x.numel(), uploads[0].frac_bits
+    for u in uploads:
+        if u.frac_bits != frac_bits or u.n != n:
+            raise RuntimeError("fedfr_amd.FedSecAgg: an upload of %d fraction bits and %d parameters among uploads of %d bits for %d parameters"
+                               % (u.frac_bits, u.n, frac_bits, n))
+        if u.y.dtype != torch.int32 or u.y.numel() != n or u.y.device != x.device or not u.y.is_contiguous():
+            raise RuntimeError("fedfr_amd.FedSecAgg: y must be a contiguous int32 tensor of %d words on %s" % (n, x.device))
+    streams = list(recovery_streams)
+    passes = max((len(uploads) + 7) // 8, (len(streams) + 31) // 32)
+    acc = torch.empty(n, dtype=torch.int32, device=x.device) if passes > 1 else None
+    P = torch.empty_like(x)
+    for p in range(passes):
+        grp, sgrp = uploads[8 * p:8 * p + 8], streams[32 * p:32 * p + 32]
+        last = p == passes - 1
+        keys, nonces, signs = stream_arrays(sgrp)
+        if n:
+            _C.call("fedfr_secagg_aggregate", P.data_ptr(), x.data_ptr() if last and server_opt is None else None, _C.ptr(acc),
+                    _C.ptr_array([u.y for u in grp]), len(grp), keys, nonces, signs, len(sgrp), frac_bits, rescale, n, 1 if p == 0 else 0,
+                    1 if last else 0, _C.stream())
+    if server_opt is not None:
+        server_opt.apply_delta(P, x, P)
+    stats = _average_stats([_StatsOnly(u.stats, u.counters) for u in uploads], ws)
+    return FlatStateDict.from_flat((P, *stats), global_state.table, global_state.layers)
+
+
 # ---- top-k uploads: csrc/sparse.hip topk_* kernels (client side, compress.py) / sparse_aggregate_kernel
 def FedSparse(global_state, updates, weights: Sequence[float], server_opt=None):
     """One round from top-k uploads (``compress.SparseDelta``): the PARAMETERS of the new global state are x + Σ_i (n_i/Σn)·sparse_i with
@@ -699,6 +755,7 @@ class Server(object):
         self.robust_agg = None                       # RobustAggregator of aggr_alg TrimmedMean / CoordMedian / Krum / MultiKrum (built in train())
         self.dp_mech = self.dp_accountant = None     # privacy.GaussianMechanism / RDPAccountant of dp_noise_multiplier > 0 (built in train())
         self.dp_epsilon = None                       # the (epsilon, dp_delta) guarantee after the rounds aggregated so far
+        self.secagg_rng = None                       # n -> n random bytes for the secure-aggregation secrets (None: os.urandom)
 
     def enable_local_verification(self, callback, candidates=None):
         """reference server.py:105-108: ``callback`` (``eval_local.CallBack_LocalVerifi``) is handed to the clients whose ``cid`` is a
@@ -803,6 +860,44 @@ class Server(object):
             if float(getattr(self.args, "clip_norm", 0.0) or 0.0) > 0:
                 raise ValueError("Server.train: topk_ratio=%r cannot be combined with clip_norm=%r: the clip needs per-client norms of the "
                                  "deltas, which are not provided" % (topk_ratio, self.args.clip_norm))
+        secagg_on = bool(getattr(self.args, "secure_aggregation", False))      # secure aggregation (a build extension): absent or False = off
+        if secagg_on:                                                        # the same: before anybody trains
+            from .secagg import MAX_PARTICIPANTS, check_frac_bits
+            K = len(self.current_client_list)
+            if aggr_alg in ROBUST_ALG_KINDS:
+                raise ValueError("Server.train: secure_aggregation cannot be combined with aggr_alg=%r: a robust rule needs whole client states, "
+                                 "which masked uploads hide" % (aggr_alg,))
+            if compress_bits:
+                raise ValueError("Server.train: secure_aggregation cannot be combined with compress_bits=%d: masking compressed uploads is not "
+                                 "provided" % (compress_bits,))
+            if topk_ratio:
+                raise ValueError("Server.train: secure_aggregation cannot be combined with topk_ratio=%r: masking sparse uploads is not provided"
+                                 % (topk_ratio,))
+            if dp_sigma:
+                raise ValueError("Server.train: secure_aggregation cannot be combined with dp_noise_multiplier=%r: distributed differential "
+                                 "privacy is not provided" % (dp_sigma,))
+            if float(getattr(self.args, "clip_norm", 0.0) or 0.0) > 0:
+                raise ValueError("Server.train: secure_aggregation cannot be combined with clip_norm=%r: the clip needs per-client norms of the "
+                                 "updates, which masked uploads hide by design" % (self.args.clip_norm,))
+            if getattr(self.args, "return_all", False):
+                raise ValueError("Server.train: secure_aggregation cannot be combined with return_all: the public class centres would travel "
+                                 "in the clear")
+            if not 2 <= K <= MAX_PARTICIPANTS:
+                raise ValueError("Server.train: secure_aggregation needs 2 to %d participants (got %d)" % (MAX_PARTICIPANTS, K))
+            secagg_frac_bits = check_frac_bits(getattr(self.args, "secagg_frac_bits", 24), "Server.train")
+            secagg_threshold = getattr(self.args, "secagg_threshold", None)
+            if secagg_threshold is None:
+                secagg_threshold = K // 2 + 1
+            if isinstance(secagg_threshold, bool) or not isinstance(secagg_threshold, (int, np.integer)) or not 2 <= secagg_threshold <= K:
+                raise ValueError("Server.train: secagg_threshold must be an integer in 2 ... %d, the number of participants (got %r)"
+                                 % (K, secagg_threshold))
+            secagg_drop = sorted(set(int(d) for d in (getattr(self.args, "secagg_drop", None) or ())))
+            if any(d not in self.current_client_list for d in secagg_drop):
+                raise ValueError("Server.train: secagg_drop=%r names clients that do not take part in this round (%s)"
+                                 % (secagg_drop, list(self.current_client_list)))
+            if K - len(secagg_drop) < secagg_threshold:
+                raise ValueError("Server.train: secagg_drop=%r leaves %d of %d uploads, fewer than secagg_threshold=%d: the round could not be "
+                                 "recovered" % (secagg_drop, K - len(secagg_drop), K, secagg_threshold))
         models, models_fc, losses_, data_sizes = [], [], [], []
         public = bool(getattr(self.args, "add_pretrained_data", False))
         return_all = bool(getattr(self.args, "return_all", False))
@@ -868,12 +963,23 @@ class Server(object):
                     t.join()
                 if errs:
                     raise errs[0]
-        if compress_bits or topk_ratio:
+        if compress_bits or topk_ratio or secagg_on:
             global_state = flat_state_dict(self.federated_model)              # what the round started from: the clients trained on copies
             feedback = bool(getattr(self.args, "error_feedback", True))
-        for i in order:
+        if secagg_on:                                                         # rounds 0 to 2 of the protocol: keys, shares, public weights
+            from .secagg import SecAggServer
+            sa_server = SecAggServer(order, secagg_threshold, self.global_round)
+            for i in order:
+                sa_server.register(i, self.clients[i].secagg_client(i, secagg_frac_bits, self.secagg_rng).begin_round(self.global_round))
+            for i in order:
+                sa_server.deliver_shares(i, self.clients[i].secagg.make_shares(order, secagg_threshold))
+            sizes_all = [self.clients[i].get_data_size() for i in order]
+            public_w = [sz / float(sum(sizes_all)) for sz in sizes_all]        # w_i = n_i / Σn: public, the factor each client encodes with
+        for pos, i in enumerate(order):
             losses_.append(self.clients[i].get_train_loss())
-            if compress_bits:                                                 # "client sends Q(x_i - x + e_i)" and keeps e_i
+            if secagg_on:                                                     # "client sends its masked fixed-point update"
+                models.append(self.clients[i].get_masked_update(global_state, public_w[pos], order, sa_server.public_keys, self.global_round))
+            elif compress_bits:                                                 # "client sends Q(x_i - x + e_i)" and keeps e_i
                 models.append(self.clients[i].get_compressed_update(global_state, compress_bits, feedback))
             elif topk_ratio:                                                  # "client sends the largest entries of x_i - x + e_i" and keeps the rest
                 models.append(self.clients[i].get_sparse_update(global_state, topk_ratio, feedback))
@@ -917,6 +1023,21 @@ class Server(object):
                 if nb > 0:
                     self.logger.warning('Client %s sent %d non-finite elements (NaN in the aggregate there)'
                                         % (getattr(self.clients[order[j]], "cid", order[j]), nb))
+        elif secagg_on:
+            keep = [pos for pos, i in enumerate(order) if i not in secagg_drop]      # (a dropped client's upload is discarded after masking)
+            from .secagg import survivor_rescale
+            streams = sa_server.recovery_streams([order[pos] for pos in keep])
+            aggr_state_dict = FedSecAgg(global_state, [models[pos] for pos in keep], [data_sizes[pos] for pos in keep], streams,
+                                        survivor_rescale(public_w, keep), self.server_opt if aggr_alg in AGGR_ALG_KINDS else None)
+            sent, dense = sum(u.nbytes for u in models), sum(u.dense_nbytes for u in models)
+            self.logger.info('Masked uploads (%d fraction bits, threshold %d): %d bytes from %d clients, %.4f of the %d bytes of fp32 states; '
+                             '%d dropped, %d recovery streams' % (secagg_frac_bits, secagg_threshold, sent, len(models), sent / dense, dense,
+                                                                 len(models) - len(keep), len(streams)))
+            bad = torch.stack([models[pos].code_counters for pos in keep]).cpu().tolist()      # one small copy: the round's one read of the counters
+            for pos, (nsat, nbad) in zip(keep, bad):
+                if nsat > 0 or nbad > 0:
+                    self.logger.warning('Client %s sent %d saturated and %d non-finite elements (clamped to the code range / sent as 0)'
+                                        % (getattr(self.clients[order[pos]], "cid", order[pos]), nsat, nbad))
         elif dp_sigma:
             aggr_state_dict = self._aggregate_dp(models, data_sizes, aggr_alg, dp_sigma, clip_norm, dp_delta)
         elif aggr_alg in ("FedAvg", "FedProx"):

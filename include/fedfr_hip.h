@@ -697,6 +697,49 @@ int fedfr_dp_multi(int kind, float* x_out, const float* x, const float* const* x
                    unsigned stream_id, unsigned long long offset, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * secure aggregation (Bonawitz et al., CCS 2017) — no reference counterpart.  A client uploads its update as fixed-point words under
+ * pairwise and self masks; the server adds the uploads and the recovery streams and learns only the sum.  The masks come from a stream
+ * cipher (a secure-aggregation mask must be indistinguishable from uniform without the key; Philox above is not a cipher).
+ * THE MASK STREAM.  The generator is the ChaCha20 block function of RFC 8439 section 2.3: 20 rounds, then the input state is added.
+ * State words 0-3 are the constants, 4-11 the key as 8 little-endian words, 12 the block counter, 13-15 three nonce words.  Element e of
+ * the stream (key, counter0, nonce[3]) is word e % 16 of block counter0 + e / 16.  The counter is ONE 32-bit word: an entry returns
+ * FEDFR_ERR_ARG for a call whose last block would pass 2^32 - 1.  A value depends on (key, nonce, counter0, e) only: not on the grid, on
+ * the number of streams of a launch, or on how passes are chained.
+ *   PROTOCOL NONCES (fedfr_amd/secagg.py).  nonce = (round low 32, round high 32, purpose), counter0 = 0; purpose 0 = pairwise mask,
+ *   1 = self mask.  fedfr_secagg_mask and fedfr_secagg_aggregate always start their streams at counter0 = 0.
+ *   ENCODING.  All arithmetic in Z / 2^32.  Client i with public weight w_i = n_i / sum n, c_i = fp32(fp32(w_i) 2^f) formed on the host
+ *   (f = frac_bits, 8 ... 30), and K participants, L = (2^31 - 1) / K (integer division):
+ *     d = x_i - x (one fp32 subtraction);  t = d c_i (one fp32 multiplication);  q = clamp(rint(t), -L, L) as int32, round half to even.
+ *   A t that is NaN or infinite encodes as 0 and counts in `nonfinite`; a q equal to +L or -L counts in `saturated`.  The sum of K codes
+ *   cannot leave the signed 32-bit range.
+ *   MASKED UPLOAD.  y_i[e] = q_i[e] + sum_s sign_s m_s[e] mod 2^32 over the client's streams s (sign +1 for the pair mask with a peer
+ *   j > i, -1 with a peer j < i, +1 for its own self mask).
+ *   AGGREGATE.  S = sum_i y_i + sum_r sign_r m_r mod 2^32 over the received uploads and the recovery streams r;
+ *     D = float(int32(S)) 2^-f rescale (one conversion, two fp32 multiplications);  out = x + D, or D when x is NULL.
+ *   rescale = fp32(1 / sum of the survivors' w_i), exactly 1.0f when nobody dropped (the product is then the identity).  Addition mod
+ *   2^32 is associative and commutative: S has ONE bit pattern whatever the order, the chaining or the grid.
+ * keys ([k][8] words), nonces ([k][3] words) and signs (k values, each +1 or -1) are HOST arrays; they travel as one kernel argument.
+ * tests/secagg_cases.py restates all of it in numpy, bit for bit.
+ * ------------------------------------------------------------------------------------------------ */
+/* dst[j] = word j of the stream (key[8], counter0, nonce[3]), j < n (key and nonce: HOST arrays).  dst 16-byte aligned; nothing is
+ * written behind n; n = 0 is a no-op.  FEDFR_ERR_ARG for a NULL pointer, a misaligned dst, or a counter overflow. */
+int fedfr_chacha20_fill(unsigned* dst, size_t n, const unsigned* key, unsigned counter0, const unsigned* nonce, void* stream);
+/* y = encode(xi - x) + the k streams (0 <= k <= 32), as above, with coef = c_i and limit = L >= 1.  counters: DEVICE int32[2]
+ * {saturated, nonfinite}, added to (atomically), may be NULL.  One pass: x and xi are read once (non-temporal), y is written once.
+ * y, x, xi 16-byte aligned and distinct; n = 0 is a no-op.  Bad arguments return FEDFR_ERR_ARG before anything is launched. */
+int fedfr_secagg_mask(unsigned* y, const float* x, const float* xi, float coef, int limit, const unsigned* keys, const unsigned* nonces,
+                      const int* signs, int k, size_t n, int* counters, void* stream);
+/* One pass of the aggregate over ku uploads (HOST array of 0 ... 8 device pointers) and k recovery streams (0 ... 32), ku + k > 0:
+ *   S = (first ? 0 : acc) + sum ys + sum_r sign_r m_r;   last ? out = (x ? x + D : D) : acc = S.
+ * More than 8 uploads or 32 streams: chain calls with first = 1 on the first and last = 1 on the final one, as fedfr_fedopt_multi (acc
+ * [n] words carries S; with one call first = last = 1 and acc may be NULL).  x is read on the last pass only; out may be x.  With
+ * <= 8 uploads and no dropout every upload word and x are read once and out is written once.  frac_bits 8 ... 30, rescale finite; all
+ * [n] buffers 16-byte aligned; n = 0 is a no-op.  Bad arguments return FEDFR_ERR_ARG before anything is launched. */
+int fedfr_secagg_aggregate(float* out, const float* x, unsigned* acc, const unsigned* const* ys, int ku, const unsigned* keys,
+                           const unsigned* nonces, const int* signs, int k, int frac_bits, float rescale, size_t n, int first, int last,
+                           void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * robust aggregation — no reference counterpart: every rule above is a weighted sum, so one client that returns a poisoned, diverged or NaN
  * state moves (or wipes out) the global model.  Coordinate-wise trimmed mean / median (Yin et al., 2018) and Krum / Multi-Krum (Blanchard
  * et al., 2017) over k <= 32 flat fp32 client states (HOST arrays of k device pointers, as fedfr_fedavg_multi), as streaming passes.
