@@ -1132,13 +1132,20 @@ class Client(object):
         return sa
 
     @_C.on_device(lambda self: self.device)
-    def get_masked_update(self, global_state, weight, participants, public_keys, round):
+    def get_masked_update(self, global_state, weight, participants, public_keys, round, dp=None):
         """The trained state as a masked upload against ``global_state`` (the state the round started from): ``secagg.MaskedUpdate``, the
         fixed-point update at the client's public weight ``weight`` = n_i / Σn under the pair masks with every other participant and the
-        client's self mask, from the secrets of ``secagg_client(...).begin_round(round)``.  One kernel pass."""
+        client's self mask, from the secrets of ``secagg_client(...).begin_round(round)``.  One kernel pass.  With ``dp`` (a
+        ``privacy.DistributedDiscreteGaussian``) the client first clips its own update and adds its own share of discrete Gaussian noise
+        (``SecAggClient.mask_dp``: the norm pass and one kernel pass); the mechanism's sensitivity is stated for ``weight`` = 1, and
+        anything else is refused."""
         sa = getattr(self, "secagg", None)
         if sa is None:
             raise RuntimeError("Client.get_masked_update: secagg_client(...).begin_round(round) first")
+        if dp is not None:
+            if float(weight) != 1.0:
+                raise ValueError("Client.get_masked_update: under distributed differential privacy every client encodes at weight 1 (got %r)" % (weight,))
+            return sa.mask_dp(global_state, self.backbone_state_dict, participants, public_keys, round, dp)
         return sa.mask(global_state, self.backbone_state_dict, weight, participants, public_keys, round)
 
     def get_global_fc(self):

@@ -14,6 +14,7 @@
 #include "sparse.h"
 #include "dp.h"
 #include "secagg.h"
+#include "ddp.h"
 
 static thread_local char g_err[512] = "";
 extern int g_tn_use_tr;
@@ -943,6 +944,17 @@ int fedfr_secagg_aggregate(float* out, const float* x, unsigned* acc, const unsi
                            const unsigned* nonces, const int* signs, int k, int frac_bits, float rescale, size_t n, int first, int last,
                            void* stream) {
   return secagg_aggregate(out, x, acc, ys, ku, keys, nonces, signs, k, frac_bits, rescale, n, first, last, ST(stream));
+}
+int fedfr_dgauss_fill(int* dst, size_t n, unsigned long long seed, unsigned long long round, unsigned stream_id, unsigned long long offset,
+                      double sigma, int* exhausted, void* stream) {
+  return ddp_dgauss_fill(dst, n, seed, round, stream_id, offset, sigma, exhausted, ST(stream));
+}
+int fedfr_secagg_mask_dp(unsigned* y, const float* x, const float* xi, const float* clip_coef, int frac_bits, int code_limit,
+                         unsigned long long noise_seed, unsigned long long noise_round, unsigned long long noise_offset, double sigma,
+                         const unsigned* keys, const unsigned* nonces, const int* signs, int k, size_t n, int* counters,
+                         unsigned long long* sqnorm, void* stream) {
+  return ddp_secagg_mask_dp(y, x, xi, clip_coef, frac_bits, code_limit, noise_seed, noise_round, noise_offset, sigma, keys, nonces, signs, k, n,
+                            counters, sqnorm, ST(stream));
 }
 int fedfr_robust_trimmed_mean(float* dst, const float* const* srcs, int k, int trim, size_t n, void* stream) {
   return robust_trimmed_mean(dst, srcs, k, trim, n, ST(stream));

@@ -8,6 +8,7 @@
 // word: the entries refuse a call whose last block would pass 2^32 - 1.  tests/secagg_cases.py restates the words bit for bit.
 #pragma once
 #include "common.h"
+#include "multi_state.h"
 
 constexpr int SECAGG_MAX_STREAMS = 32;      // streams per launch
 constexpr int SECAGG_MAX_UPLOADS = 8;       // uploads per aggregate pass
@@ -67,6 +68,71 @@ __device__ __forceinline__ void chacha_add_streams(unsigned (&acc)[16], const Ma
       for (int i = 0; i < 16; ++i) acc[i] -= w[i];
     }
   }
+}
+
+// ---- shared by the kernels of secagg.hip and ddp.hip: the exchange, the encoder and the host-side checks, written ONCE -----------------
+typedef unsigned uvec4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ uvec4 ld_once_u4(const unsigned* p, size_t i) { return __builtin_nontemporal_load(reinterpret_cast<const uvec4*>(p) + i); }
+
+constexpr int SECAGG_WPB = MULTI_STATE_BLOCK / 64;          // waves per workgroup
+constexpr int SECAGG_CHUNK = 64 * SECAGG_EPT;               // elements per wave and loop iteration: 64 blocks = 256 16-byte slots
+static_assert(MULTI_STATE_BLOCK % 64 == 0, "whole waves");
+
+// THE EXCHANGE.  The generator leaves lane L of a wave with the 16 words of block L: slots 4 L + j, j < 4, of the wave's chunk of 256
+// 16-byte slots, 64 B apart from lane to lane.  Memory wants lane L on slot 64 h + L, h < 4: one contiguous KiB per instruction.  The wave
+// passes its 4 KiB through LDS: block layout in, memory layout out.  Slot s lives at s ^ ((s >> 4) & 3): the block-layout writes of 8
+// neighbouring lanes then fall on 4 bank groups instead of 2, and every memory-layout ds_read_b128 lane group reads 16 distinct
+// slots of a 256-byte bank row.  One wave owns the buffer: no workgroup barrier, only the wave's own program order.
+__device__ __forceinline__ int xch_slot(int s) { return s ^ ((s >> 4) & 3); }
+__device__ __forceinline__ void block_to_memory_layout(uvec4* __restrict__ buf, unsigned (&m)[16], int lane) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) buf[xch_slot(4 * lane + j)] = uvec4{m[4 * j], m[4 * j + 1], m[4 * j + 2], m[4 * j + 3]};
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+  for (int h = 0; h < 4; ++h) {
+    const uvec4 v = buf[xch_slot(64 * h + lane)];
+    m[4 * h] = v.x; m[4 * h + 1] = v.y; m[4 * h + 2] = v.z; m[4 * h + 3] = v.w;
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // (the next iteration's writes stay behind these reads)
+  __builtin_amdgcn_wave_barrier();
+}
+
+// One element's code: d = xi - x, t = d coef, q = clamp(rint(t), -limit, limit); a t that is NaN or infinite gives 0.  rint(t) is an
+// integer-valued float: below 2^31 in magnitude it converts exactly, and beyond that it is past every limit.
+__device__ __forceinline__ unsigned secagg_encode(float xi, float x, float coef, int limit, int& saturated, int& nonfinite) {
+  const float t = __fmul_rn(__fsub_rn(xi, x), coef);
+  const bool finite = __builtin_fabsf(t) < __builtin_inff();
+  const float r = __builtin_rintf(t);      // round half to even
+  const float rc = __builtin_fminf(__builtin_fmaxf(finite ? r : 0.f, -0x1p31f), 0x1.fffffep30f);      // inside int32: the conversion is exact
+  int q = min(max((int)rc, -limit), limit);
+  q = r >= 0x1p31f ? limit : q;                                                                        // (inf and NaN: finite is false)
+  q = finite ? q : 0;
+  saturated += (finite && (q == limit || q == -limit)) ? 1 : 0;
+  nonfinite += finite ? 0 : 1;
+  return (unsigned)q;
+}
+
+// the one 32-bit block counter: the last block of n elements from counter0 on must not pass 2^32 - 1
+static inline int counter_fits(const char* who, size_t n, unsigned counter0) {
+  const unsigned long long last = (unsigned long long)counter0 + (unsigned long long)((n - 1) / SECAGG_EPT);
+  FEDFR_REQUIRE(last <= 0xFFFFFFFFull, "%s: the 32-bit block counter overflows (counter0=%u, n=%zu: last block %llu > 4294967295)", who, counter0, n,
+                last);
+  return FEDFR_OK;
+}
+// keys [k][8], nonces [k][3], signs [k] (HOST arrays) -> the kernel argument
+static inline int mask_streams_fill(MaskStreams& ms, const char* who, const unsigned* keys, const unsigned* nonces, const int* signs, int k) {
+  FEDFR_REQUIRE(k >= 0 && k <= SECAGG_MAX_STREAMS, "%s: 0 to %d streams per call (k=%d)", who, SECAGG_MAX_STREAMS, k);
+  FEDFR_REQUIRE(k == 0 || (keys && nonces && signs), "%s: null pointer (keys=%p nonces=%p signs=%p) with k=%d", who, (const void*)keys,
+                (const void*)nonces, (const void*)signs, k);
+  for (int s = 0; s < k; ++s) {
+    FEDFR_REQUIRE(signs[s] == 1 || signs[s] == -1, "%s: sign %d is %d, not +1 or -1", who, s, signs[s]);
+    for (int i = 0; i < 8; ++i) ms.key[s][i] = keys[8 * s + i];
+    for (int i = 0; i < 3; ++i) ms.nonce[s][i] = nonces[3 * s + i];
+    ms.sign[s] = signs[s];
+  }
+  return FEDFR_OK;
 }
 
 int secagg_chacha20_fill(unsigned* dst, size_t n, const unsigned* key, unsigned counter0, const unsigned* nonce, hipStream_t st);

@@ -62,6 +62,85 @@ class GaussianMechanism:
             self.stream_id = int(sd["stream_id"])
 
 
+class DistributedDiscreteGaussian:
+    """The arithmetic of the distributed discrete Gaussian mechanism (Kairouz, Liu, Steinke, "The Distributed Discrete Gaussian Mechanism
+    for Federated Learning with Secure Aggregation", ICML 2021) on the fixed-point words of secure aggregation: ``participants`` K clients
+    each clip their update to ``clip_norm`` C, encode it at ``frac_bits`` f, add integer Gaussian noise of
+        sigma_int = z C 2^f / sqrt(T)
+    (z = ``noise_multiplier``, T = ``threshold``: the fewest uploads a round can be recovered from, so the unmasked sum always carries at
+    least the noise z C 2^f whoever dropped) and mask the result (``secagg.SecAggClient.mask_dp``: fedfr_secagg_mask_dp).  In the integers:
+        delta_int  = C 2^f (1 + EPS_FP) + sqrt(n) / 2     the L2 sensitivity: the clipped, scaled update (EPS_FP bounds the fp32 rounding of the
+                                                          clip factor and of the product) plus the rounding to
+                                                          the nearest integer of ``n`` coordinates
+        code_limit = L(K) - 37 (floor(sigma_int) + 1)     the clamp of a code: |noise| <= 37 (floor(sigma_int) + 1) always, so code +
+                                                          noise stays inside L(K) = (2^31 - 1) // K and the sum of K of them inside int32
+        z_eff      = sqrt(T) sigma_int / delta_int        the noise multiplier the mechanism GUARANTEES (below z by the rounding term)
+        tau        = 10 sum_{k=1}^{T-1} exp(-2 pi^2 sigma_int^2 k / (k + 1))     how far a sum of T discrete Gaussians is from one (DDG, Theorem 1)
+    ``ValueError`` when sigma_int is outside the sampler's [16, 2^26], when code_limit < delta_int (a clipped update would be clamped), or
+    when tau n >= 1e-12 (at sigma_int >= 16 tau underflows to 0 in fp64); the message names the ``secagg_frac_bits`` that would work.  One
+    round is then (delta_int / (sqrt(T) sigma_int))^2 / 2-zCDP, which is RDP(alpha) = alpha / (2 z_eff^2): ``accountant()`` returns
+    ``RDPAccountant(1.0, z_eff)``.  Rounds are accounted at q = 1 whatever the sampling rate: valid and conservative (the amplification
+    bound of ``RDPAccountant`` is proven for the continuous Gaussian only)."""
+
+    EPS_FP = 2.0 ** -22
+    SIGMA_MIN, SIGMA_MAX = 16.0, 2.0 ** 26
+    TAIL = 37                                        # |noise| <= TAIL (floor(sigma_int) + 1): U1 >= 2^-53 and 53 ln 2 < 37
+
+    def __init__(self, noise_multiplier, clip_norm, frac_bits, participants, threshold, n):
+        from .secagg import MAX_PARTICIPANTS, check_frac_bits
+        who = "DistributedDiscreteGaussian"
+        self.noise_multiplier, self.clip_norm = float(noise_multiplier), float(clip_norm)
+        if not (self.noise_multiplier > 0.0 and math.isfinite(self.noise_multiplier)):
+            raise ValueError("%s: noise_multiplier must be finite and > 0 (got %r)" % (who, noise_multiplier))
+        if not (self.clip_norm > 0.0 and math.isfinite(self.clip_norm)):
+            raise ValueError("%s: clip_norm must be finite and > 0: without a clip there is no sensitivity bound (got %r)" % (who, clip_norm))
+        self.frac_bits = check_frac_bits(frac_bits, who)
+        for name, v, lo, hi in (("participants", participants, 2, MAX_PARTICIPANTS), ("threshold", threshold, 2, participants),
+                                ("n", n, 1, None)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo or (hi is not None and v > hi):
+                raise ValueError("%s: %s must be an integer in %d ... %s (got %r)" % (who, name, lo, "" if hi is None else hi, v))
+        self.participants, self.threshold, self.n = int(participants), int(threshold), int(n)
+        ok = [f for f in range(8, 31) if self._refusal(f) is None]
+        why = self._refusal(self.frac_bits)
+        if why is not None:
+            hint = ("secagg_frac_bits in %d ... %d would work" % (ok[0], ok[-1])) if ok else "no secagg_frac_bits in 8 ... 30 would work"
+            raise ValueError("%s: %s (noise_multiplier=%g, clip_norm=%g, secagg_frac_bits=%d, participants=%d, threshold=%d, n=%d): %s"
+                             % (who, why, self.noise_multiplier, self.clip_norm, self.frac_bits, self.participants, self.threshold, self.n, hint))
+        self.sigma_int, self.delta_int, self.code_limit, self.tau = self._numbers(self.frac_bits)
+        self.z_eff = math.sqrt(self.threshold) * self.sigma_int / self.delta_int
+
+    def _numbers(self, f):
+        from .secagg import code_limit
+        scale = self.clip_norm * 2.0 ** f
+        sigma = self.noise_multiplier * scale / math.sqrt(self.threshold)
+        delta = scale * (1.0 + self.EPS_FP) + math.sqrt(self.n) / 2.0
+        limit = code_limit(self.participants) - self.TAIL * (int(math.floor(min(sigma, 2.0 ** 40))) + 1)
+        tau = 10.0 * sum(math.exp(-2.0 * math.pi ** 2 * sigma * sigma * k / (k + 1.0)) for k in range(1, self.threshold))
+        return sigma, delta, limit, tau
+
+    def _refusal(self, f):
+        sigma, delta, limit, tau = self._numbers(f)
+        if not self.SIGMA_MIN <= sigma <= self.SIGMA_MAX:
+            return "sigma_int = %.6g is outside the sampler's range [16, 2^26]" % sigma
+        if limit < delta:
+            return "the code clamp L' = %d is below the sensitivity delta_int = %.6g: clipped updates would be clamped" % (limit, delta)
+        if tau * self.n >= 1e-12:
+            return "the sum of %d discrete Gaussians of sigma_int = %.6g is not close to one (tau n = %.3g >= 1e-12)" % (self.threshold, sigma, tau * self.n)
+        return None
+
+    def realised_multiplier(self, survivors: int) -> float:
+        """the multiplier of a round in which ``survivors`` >= threshold uploads arrived: sqrt(survivors / T) z_eff (not accounted: the
+        accountant keeps the guaranteed z_eff)"""
+        return math.sqrt(survivors / float(self.threshold)) * self.z_eff
+
+    def accountant(self) -> "RDPAccountant":
+        return RDPAccountant(1.0, self.z_eff)
+
+    def same_as(self, other) -> bool:
+        keys = ("noise_multiplier", "clip_norm", "frac_bits", "participants", "threshold", "n")
+        return isinstance(other, DistributedDiscreteGaussian) and all(getattr(self, k) == getattr(other, k) for k in keys)
+
+
 def _logsumexp(terms):
     mx = max(terms)
     return mx + math.log(sum(math.exp(t - mx) for t in terms))

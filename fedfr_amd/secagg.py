@@ -15,8 +15,12 @@ dropout recovery run end to end:
     semi-honest server must keep is enforced: it never reconstructs both the secret key and the self seed of the same client);
   * the integer arithmetic on Python numbers is not constant-time;
   * BN running statistics and ``num_batches_tracked`` travel in the clear, the stance ``compress.py`` and ``server.FedDP`` already take;
-  * the RCCL path (``server.fedavg_all_reduce``) is left alone, and combining with differential privacy (distributed DP), with
-    compression or with top-k uploads is not provided.
+  * the RCCL path (``server.fedavg_all_reduce``) is left alone, and combining with compression or with top-k uploads is not provided.
+
+DISTRIBUTED DIFFERENTIAL PRIVACY.  With a ``privacy.DistributedDiscreteGaussian`` every client clips its own update, adds its own share of
+integer Gaussian noise to the codes and masks the result (``SecAggClient.mask_dp``: fedfr_secagg_mask_dp, one pass); the sum the server
+unmasks then carries the noise of all surviving clients, and nobody ever holds an un-noised sum.  The sampler and its stream are stated in
+include/fedfr_hip.h, "THE DISCRETE NOISE STREAM"; what the guarantee covers: DESIGN.md section 3.27.
 """
 from __future__ import annotations
 
@@ -210,12 +214,14 @@ class MaskedUpdate:
     ``frac_bits``, the client's BN running statistics ``stats`` (fp32) and ``counters`` (int64) UNMASKED, and ``code_counters``: a DEVICE
     int32 pair {saturated, nonfinite} — elements whose code hit +-L, elements whose scaled value was NaN or infinite (sent as 0) — read
     back only when ``saturated_count()`` / ``nonfinite_count()`` are asked for.  ``table`` / ``layers`` describe the state the upload
-    belongs to (FlatStateDict)."""
+    belongs to (FlatStateDict).  An upload of ``SecAggClient.mask_dp`` carries a third counter, {..., exhausted} (elements whose noise
+    sampler ran out of attempts: an error), and ``sqnorm``: a DEVICE int64 holding the exact sum of its squared codes mod 2^64, taken
+    before the noise (``sqnorm_value()``), which the server holds against the mechanism's sensitivity."""
 
-    def __init__(self, y, n, frac_bits, stats, counters, code_counters, table=None, layers=None):
+    def __init__(self, y, n, frac_bits, stats, counters, code_counters, table=None, layers=None, sqnorm=None):
         self.y, self.n, self.frac_bits = y, int(n), int(frac_bits)
         self.stats, self.counters, self.code_counters = stats, counters, code_counters
-        self.table, self.layers = table, layers
+        self.table, self.layers, self.sqnorm = table, layers, sqnorm
 
     @property
     def nbytes(self) -> int:
@@ -234,6 +240,14 @@ class MaskedUpdate:
     def nonfinite_count(self) -> int:
         return int(self.code_counters[1].item())
 
+    def exhausted_count(self) -> int:
+        """the third counter of a ``mask_dp`` upload (0 for a plain one), read back"""
+        return int(self.code_counters[2].item()) if self.code_counters.numel() > 2 else 0
+
+    def sqnorm_value(self):
+        """the sum of the squared codes as a Python integer in [0, 2^64), read back; None for a plain upload"""
+        return None if self.sqnorm is None else int(self.sqnorm.item()) & ((1 << 64) - 1)
+
 
 class SecAggClient:
     """The protocol state of ONE client.  ``begin_round`` draws a fresh X25519 key pair and a 32-byte self seed b_i; ``make_shares`` hands
@@ -243,6 +257,8 @@ class SecAggClient:
         self.cid, self.frac_bits, self.rng = int(cid), check_frac_bits(frac_bits, "SecAggClient"), rng
         self.round = None
         self.secret_key = self.public_key = self.self_seed = None
+        self.noise_seed = None          # the 64-bit seed of the client's noise share of the round (mask_dp): drawn here, never sent
+        self._clipper = None            # mask_dp keeps the workspace of its norm pass here
 
     def begin_round(self, round: int) -> bytes:
         """fresh secrets for ``round``; returns the public key"""
@@ -297,6 +313,44 @@ class SecAggClient:
             _C.call("fedfr_secagg_mask", y.data_ptr(), x.data_ptr(), xi.data_ptr(), code_coef(weight, self.frac_bits), code_limit(K), keys, nonces,
                     signs, K, n, cc.data_ptr(), _C.stream())
         return MaskedUpdate(y, n, self.frac_bits, stats, counters, cc, client_state.table, client_state.layers)
+
+
+    def mask_dp(self, global_state, client_state, participants: Sequence[int], public_keys: Dict[int, bytes], round: int, mech) -> MaskedUpdate:
+        """``mask`` under distributed differential privacy (``mech``: a ``privacy.DistributedDiscreteGaussian`` of this round's K, T, n and
+        this client's ``frac_bits``), at weight 1: the norm pass (fedfr_fedopt_sqnorm, which leaves min(1, C / ||x_i - x||) ON THE DEVICE),
+        then ONE call of fedfr_secagg_mask_dp, which clips, encodes at the clamp ``mech.code_limit``, sums the squared codes, adds the
+        client's noise share of sigma_int and the masks.  No host synchronisation in between.  The 64-bit noise seed is drawn from
+        ``rng`` per call and stays here (``noise_seed``: the client knows its own share, nobody else does)."""
+        import torch
+        from . import _C
+        from .client import FlatStateDict
+        from .privacy import DistributedDiscreteGaussian
+        from .server import ServerOptimizer, _check_states
+        if not all(isinstance(s, FlatStateDict) and s.flat is not None for s in (global_state, client_state)):
+            raise RuntimeError("fedfr_amd.SecAggClient: the global and the client state must be FlatStateDicts (client.flat_state_dict)")
+        if not isinstance(mech, DistributedDiscreteGaussian):
+            raise RuntimeError("fedfr_amd.SecAggClient.mask_dp: mech must be a privacy.DistributedDiscreteGaussian (got %r)" % (type(mech).__name__,))
+        K = len(participants)
+        if not 2 <= K <= MAX_PARTICIPANTS or len(set(participants)) != K:
+            raise ValueError("SecAggClient.mask_dp: 2 to %d distinct participants (got %d: %s)" % (MAX_PARTICIPANTS, K, list(participants)))
+        x, (xi, stats, counters) = global_state.flat[0], client_state.flat
+        _check_states(x, [xi], "SecAggClient")
+        n, dev = x.numel(), x.device
+        if (mech.participants, mech.frac_bits, mech.n) != (K, self.frac_bits, n):
+            raise ValueError("SecAggClient.mask_dp: the mechanism is one of %d participants, %d fraction bits and %d parameters; this upload has %d, %d "
+                             "and %d" % (mech.participants, mech.frac_bits, mech.n, K, self.frac_bits, n))
+        keys, nonces, signs = stream_arrays(self.streams(participants, public_keys, round))
+        if self._clipper is None or self._clipper.clip_norm != mech.clip_norm:
+            self._clipper = ServerOptimizer("AVGM", clip_norm=mech.clip_norm)
+        self.noise_seed = int.from_bytes((self.rng or os.urandom)(8), "little")
+        y = torch.empty(n, dtype=torch.int32, device=dev)
+        cc = torch.zeros(3, dtype=torch.int32, device=dev)
+        sq = torch.zeros(1, dtype=torch.int64, device=dev)
+        if n:
+            coef = self._clipper.coefficients(x, [xi], [1.0])
+            _C.call("fedfr_secagg_mask_dp", y.data_ptr(), x.data_ptr(), xi.data_ptr(), coef.data_ptr(), self.frac_bits, mech.code_limit, self.noise_seed,
+                    int(round) & 0xFFFFFFFF, 0, mech.sigma_int, keys, nonces, signs, K, n, cc.data_ptr(), sq.data_ptr(), _C.stream())
+        return MaskedUpdate(y, n, self.frac_bits, stats, counters, cc, client_state.table, client_state.layers, sqnorm=sq)
 
 
 class SecAggServer:

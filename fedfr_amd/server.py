@@ -6,7 +6,9 @@ checkpoints (reference server.py:135-148).  Build extensions beyond the referenc
 robust rules (``FedRobust``: coordinate-wise trimmed mean / median, Krum / Multi-Krum) and compressed client uploads (``FedCompressed``:
 8 / 4-bit block-scaled deltas with error feedback; ``FedSparse``: top-k sparsified deltas with error feedback; see compress.py) and
 client-level differential privacy (``FedDP``: clipped updates and Gaussian noise drawn on the device; see privacy.py) and secure
-aggregation (``FedSecAgg``: pairwise-masked fixed-point uploads of which the server learns only the sum; see secagg.py)."""
+aggregation (``FedSecAgg``: pairwise-masked fixed-point uploads of which the server learns only the sum; see secagg.py), and the two
+together (``FedSecAggDP``: every client clips its own update and adds its share of discrete Gaussian noise before masking it; see
+privacy.DistributedDiscreteGaussian)."""
 from __future__ import annotations
 
 import copy
@@ -546,6 +548,60 @@ def FedSecAgg(global_state, uploads, weights: Sequence[float], recovery_streams,
     return FlatStateDict.from_flat((P, *stats), global_state.table, global_state.layers)
 
 
+# ---- distributed differential privacy: csrc/ddp.hip ddp_mask_kernel (client side, secagg.py) / secagg_aggregate_kernel
+def FedSecAggDP(global_state, uploads, recovery_streams, mech, server_opt=None):
+    """One round from the uploads of ``secagg.SecAggClient.mask_dp`` (clipped, noised, masked; all of ``mech``, a
+    ``privacy.DistributedDiscreteGaussian``): ``FedSecAgg``'s sum S through the same kernel (fedfr_secagg_aggregate, chained in the same
+    way), with every client at weight 1 and rescale = fp32(1 / number of uploads): the PARAMETERS are x + float(int32(S)) 2^-f rescale, the
+    MEAN of the clipped updates plus the noise of all uploads, or that mean as the pseudo-gradient of ``server_opt``.  (``FedSecAgg``
+    itself takes a rescale >= 1 only, the reciprocal of a sum of public weights.)  BN running statistics and ``num_batches_tracked``
+    arrive UNMASKED and are averaged uniformly, outside the mechanism.  At least ``mech.threshold`` uploads are required: with fewer the
+    sum carries less noise than the accountant is told."""
+    from .privacy import DistributedDiscreteGaussian
+    from .secagg import MaskedUpdate, stream_arrays
+    if not isinstance(global_state, FlatStateDict) or global_state.flat is None:
+        raise RuntimeError("fedfr_amd.FedSecAggDP: the global state must be a FlatStateDict (client.flat_state_dict)")
+    if not isinstance(mech, DistributedDiscreteGaussian):
+        raise RuntimeError("fedfr_amd.FedSecAggDP: mech must be a privacy.DistributedDiscreteGaussian")
+    if not uploads or not all(isinstance(u, MaskedUpdate) and u.sqnorm is not None for u in uploads):
+        raise RuntimeError("fedfr_amd.FedSecAggDP: the client uploads must be the MaskedUpdates of SecAggClient.mask_dp (Client.get_masked_update "
+                           "with dp=...)")
+    if not mech.threshold <= len(uploads) <= mech.participants:
+        raise ValueError("FedSecAggDP: %d uploads, the mechanism needs %d to %d (its threshold and its participants)"
+                         % (len(uploads), mech.threshold, mech.participants))
+    if isinstance(server_opt, RobustAggregator):
+        raise ValueError("FedSecAggDP: a robust rule (%s) needs whole client states, which masked uploads hide" % server_opt.kind)
+    if server_opt is not None and server_opt.clip_norm > 0:
+        raise ValueError("FedSecAggDP: the clients have clipped their own updates at %g; a server optimiser with clip_norm > 0 needs per-client "
+                         "norms, which masked uploads hide by design" % mech.clip_norm)
+    x = global_state.flat[0]
+    _check_states(x, [], "FedSecAggDP")
+    n, frac_bits = x.numel(), mech.frac_bits
+    for u in uploads:
+        if u.frac_bits != frac_bits or u.n != n or n != mech.n:
+            raise RuntimeError("fedfr_amd.FedSecAggDP: an upload of %d fraction bits and %d parameters under a mechanism of %d bits for %d parameters "
+                               "(the state has %d)" % (u.frac_bits, u.n, frac_bits, mech.n, n))
+        if u.y.dtype != torch.int32 or u.y.numel() != n or u.y.device != x.device or not u.y.is_contiguous():
+            raise RuntimeError("fedfr_amd.FedSecAggDP: y must be a contiguous int32 tensor of %d words on %s" % (n, x.device))
+    rescale = float(np.float32(1.0 / len(uploads)))
+    streams = list(recovery_streams)
+    passes = max((len(uploads) + 7) // 8, (len(streams) + 31) // 32)
+    acc = torch.empty(n, dtype=torch.int32, device=x.device) if passes > 1 else None
+    P = torch.empty_like(x)
+    for p in range(passes):
+        grp, sgrp = uploads[8 * p:8 * p + 8], streams[32 * p:32 * p + 32]
+        last = p == passes - 1
+        keys, nonces, signs = stream_arrays(sgrp)
+        if n:
+            _C.call("fedfr_secagg_aggregate", P.data_ptr(), x.data_ptr() if last and server_opt is None else None, _C.ptr(acc),
+                    _C.ptr_array([u.y for u in grp]), len(grp), keys, nonces, signs, len(sgrp), frac_bits, rescale, n, 1 if p == 0 else 0,
+                    1 if last else 0, _C.stream())
+    if server_opt is not None:
+        server_opt.apply_delta(P, x, P)
+    stats = _average_stats([_StatsOnly(u.stats, u.counters) for u in uploads], [1.0 / len(uploads)] * len(uploads))
+    return FlatStateDict.from_flat((P, *stats), global_state.table, global_state.layers)
+
+
 # ---- top-k uploads: csrc/sparse.hip topk_* kernels (client side, compress.py) / sparse_aggregate_kernel
 def FedSparse(global_state, updates, weights: Sequence[float], server_opt=None):
     """One round from top-k uploads (``compress.SparseDelta``): the PARAMETERS of the new global state are x + Σ_i (n_i/Σn)·sparse_i with
@@ -755,6 +811,7 @@ class Server(object):
         self.robust_agg = None                       # RobustAggregator of aggr_alg TrimmedMean / CoordMedian / Krum / MultiKrum (built in train())
         self.dp_mech = self.dp_accountant = None     # privacy.GaussianMechanism / RDPAccountant of dp_noise_multiplier > 0 (built in train())
         self.dp_epsilon = None                       # the (epsilon, dp_delta) guarantee after the rounds aggregated so far
+        self.dp_last_sqnorms = None                  # distributed_dp: the survivors' sums of squared codes of the last round (each <= delta_int^2)
         self.secagg_rng = None                       # n -> n random bytes for the secure-aggregation secrets (None: os.urandom)
 
     def enable_local_verification(self, callback, candidates=None):
@@ -803,6 +860,16 @@ class Server(object):
             raise ValueError("Server.train: unknown aggr_alg %r (FedAvg, FedProx, %s, %s)"
                              % (aggr_alg, ", ".join(AGGR_ALG_KINDS), ", ".join(sorted(ROBUST_ALG_KINDS))))
         dp_sigma = float(getattr(self.args, "dp_noise_multiplier", 0) or 0)      # client-level differential privacy (a build extension): absent or 0 = off
+        ddp_on = bool(getattr(self.args, "distributed_dp", False))           # the noise added by the CLIENTS under secure aggregation: absent or False = off
+        if ddp_on:
+            if not getattr(self.args, "secure_aggregation", False):
+                raise ValueError("Server.train: distributed_dp needs secure_aggregation: the clients' noise shares protect only a sum that "
+                                 "nobody sees in parts")
+            if not dp_sigma:
+                raise ValueError("Server.train: distributed_dp needs dp_noise_multiplier > 0 (got %r)" % (getattr(self.args, "dp_noise_multiplier", 0),))
+            if not bool(getattr(self.args, "dp_uniform_weights", True)):
+                raise ValueError("Server.train: distributed_dp needs dp_uniform_weights on: every client encodes at weight 1, the weight the "
+                                 "sensitivity bound is stated for")
         if dp_sigma:                                                         # what cannot be served: before anybody trains
             clip_norm = float(getattr(self.args, "clip_norm", 0.0) or 0.0)
             if not (dp_sigma > 0 and np.isfinite(dp_sigma)):
@@ -822,7 +889,7 @@ class Server(object):
             if getattr(self.args, "return_all", False):
                 raise ValueError("Server.train: dp_noise_multiplier=%r cannot be combined with return_all: the averaged public class centres "
                                  "would be released un-noised" % (dp_sigma,))
-            if self.dp_accountant is not None and self.dp_accountant.sigma != dp_sigma:
+            if not ddp_on and self.dp_accountant is not None and self.dp_accountant.sigma != dp_sigma:
                 raise ValueError("Server.train: dp_noise_multiplier=%r after rounds accounted at %r: the accountant composes rounds of one noise "
                                  "multiplier (set server.dp_accountant yourself to continue)" % (dp_sigma, self.dp_accountant.sigma))
             dp_delta = float(getattr(self.args, "dp_delta", 1e-5))
@@ -873,10 +940,10 @@ class Server(object):
             if topk_ratio:
                 raise ValueError("Server.train: secure_aggregation cannot be combined with topk_ratio=%r: masking sparse uploads is not provided"
                                  % (topk_ratio,))
-            if dp_sigma:
+            if dp_sigma and not ddp_on:
                 raise ValueError("Server.train: secure_aggregation cannot be combined with dp_noise_multiplier=%r: distributed differential "
                                  "privacy is not provided" % (dp_sigma,))
-            if float(getattr(self.args, "clip_norm", 0.0) or 0.0) > 0:
+            if float(getattr(self.args, "clip_norm", 0.0) or 0.0) > 0 and not ddp_on:
                 raise ValueError("Server.train: secure_aggregation cannot be combined with clip_norm=%r: the clip needs per-client norms of the "
                                  "updates, which masked uploads hide by design" % (self.args.clip_norm,))
             if getattr(self.args, "return_all", False):
@@ -898,6 +965,14 @@ class Server(object):
             if K - len(secagg_drop) < secagg_threshold:
                 raise ValueError("Server.train: secagg_drop=%r leaves %d of %d uploads, fewer than secagg_threshold=%d: the round could not be "
                                  "recovered" % (secagg_drop, K - len(secagg_drop), K, secagg_threshold))
+            if ddp_on:                                                       # the mechanism's arithmetic, and what it refuses: also before anybody trains
+                from .privacy import DistributedDiscreteGaussian
+                ddp_mech = DistributedDiscreteGaussian(dp_sigma, clip_norm, secagg_frac_bits, K, int(secagg_threshold),
+                                                       int(self.federated_model.flat_state()[0].numel()))
+                if self.dp_accountant is not None and (self.dp_accountant.q, self.dp_accountant.sigma) != (1.0, ddp_mech.z_eff):
+                    raise ValueError("Server.train: distributed_dp at an effective noise multiplier of %r after rounds accounted at %r (q = %g): "
+                                     "the accountant composes rounds of one mechanism (set server.dp_accountant yourself to continue)"
+                                     % (ddp_mech.z_eff, self.dp_accountant.sigma, self.dp_accountant.q))
         models, models_fc, losses_, data_sizes = [], [], [], []
         public = bool(getattr(self.args, "add_pretrained_data", False))
         return_all = bool(getattr(self.args, "return_all", False))
@@ -975,10 +1050,13 @@ class Server(object):
                 sa_server.deliver_shares(i, self.clients[i].secagg.make_shares(order, secagg_threshold))
             sizes_all = [self.clients[i].get_data_size() for i in order]
             public_w = [sz / float(sum(sizes_all)) for sz in sizes_all]        # w_i = n_i / Σn: public, the factor each client encodes with
+            if ddp_on:
+                public_w = [1.0] * len(order)                                 # distributed DP: every client at weight 1, the mean is taken by the rescale
         for pos, i in enumerate(order):
             losses_.append(self.clients[i].get_train_loss())
             if secagg_on:                                                     # "client sends its masked fixed-point update"
-                models.append(self.clients[i].get_masked_update(global_state, public_w[pos], order, sa_server.public_keys, self.global_round))
+                models.append(self.clients[i].get_masked_update(global_state, public_w[pos], order, sa_server.public_keys, self.global_round,
+                                                                **({"dp": ddp_mech} if ddp_on else {})))
             elif compress_bits:                                                 # "client sends Q(x_i - x + e_i)" and keeps e_i
                 models.append(self.clients[i].get_compressed_update(global_state, compress_bits, feedback))
             elif topk_ratio:                                                  # "client sends the largest entries of x_i - x + e_i" and keeps the rest
@@ -1002,7 +1080,7 @@ class Server(object):
             a = self.args
             self.server_opt = ServerOptimizer(aggr_alg, lr=getattr(a, "server_lr", 1.0), beta1=getattr(a, "server_momentum", 0.9),
                                               beta2=getattr(a, "server_beta2", 0.99), tau=getattr(a, "server_tau", 1e-3),
-                                              clip_norm=getattr(a, "clip_norm", 0.0))
+                                              clip_norm=0.0 if ddp_on else getattr(a, "clip_norm", 0.0))      # (distributed DP: the clients clip)
         if compress_bits:
             aggr_state_dict = FedCompressed(global_state, models, data_sizes, self.server_opt if aggr_alg in AGGR_ALG_KINDS else None)
             sent, dense = sum(u.nbytes for u in models), sum(u.dense_nbytes for u in models)
@@ -1027,17 +1105,23 @@ class Server(object):
             keep = [pos for pos, i in enumerate(order) if i not in secagg_drop]      # (a dropped client's upload is discarded after masking)
             from .secagg import survivor_rescale
             streams = sa_server.recovery_streams([order[pos] for pos in keep])
-            aggr_state_dict = FedSecAgg(global_state, [models[pos] for pos in keep], [data_sizes[pos] for pos in keep], streams,
-                                        survivor_rescale(public_w, keep), self.server_opt if aggr_alg in AGGR_ALG_KINDS else None)
+            if ddp_on:
+                aggr_state_dict = FedSecAggDP(global_state, [models[pos] for pos in keep], streams, ddp_mech,
+                                              self.server_opt if aggr_alg in AGGR_ALG_KINDS else None)
+            else:
+                aggr_state_dict = FedSecAgg(global_state, [models[pos] for pos in keep], [data_sizes[pos] for pos in keep], streams,
+                                            survivor_rescale(public_w, keep), self.server_opt if aggr_alg in AGGR_ALG_KINDS else None)
             sent, dense = sum(u.nbytes for u in models), sum(u.dense_nbytes for u in models)
             self.logger.info('Masked uploads (%d fraction bits, threshold %d): %d bytes from %d clients, %.4f of the %d bytes of fp32 states; '
                              '%d dropped, %d recovery streams' % (secagg_frac_bits, secagg_threshold, sent, len(models), sent / dense, dense,
                                                                  len(models) - len(keep), len(streams)))
             bad = torch.stack([models[pos].code_counters for pos in keep]).cpu().tolist()      # one small copy: the round's one read of the counters
-            for pos, (nsat, nbad) in zip(keep, bad):
+            for pos, (nsat, nbad, *_) in zip(keep, bad):
                 if nsat > 0 or nbad > 0:
                     self.logger.warning('Client %s sent %d saturated and %d non-finite elements (clamped to the code range / sent as 0)'
                                         % (getattr(self.clients[order[pos]], "cid", order[pos]), nsat, nbad))
+            if ddp_on:
+                self._account_distributed_dp(ddp_mech, [order[pos] for pos in keep], [row[2] for row in bad], [models[pos] for pos in keep], dp_delta)
         elif dp_sigma:
             aggr_state_dict = self._aggregate_dp(models, data_sizes, aggr_alg, dp_sigma, clip_norm, dp_delta)
         elif aggr_alg in ("FedAvg", "FedProx"):
@@ -1056,6 +1140,32 @@ class Server(object):
         self.federated_model.load_state_dict(aggr_state_dict)
         # the round / epoch counters belong to the driver, as in the reference (train.py:87-88): call step_round() after train()
         return self.avg_loss
+
+    def _account_distributed_dp(self, mech, survivors, exhausted, uploads, delta):
+        """what ``distributed_dp`` checks and accounts after the round's aggregation (the counters have been read): a sampler that ran out
+        of attempts and an upload beyond the sensitivity bound are errors (the round's result is not installed); then the accountant's
+        step at q = 1 and the guaranteed noise multiplier, and ``self.dp_epsilon``"""
+        for cid, nex in zip(survivors, exhausted):
+            if nex > 0:
+                raise RuntimeError("Server.train: the noise sampler of client %s ran out of attempts on %d elements (they carry no noise): the "
+                                   "round is void" % (getattr(self.clients[cid], "cid", cid), nex))
+        sq = [int(v) & ((1 << 64) - 1) for v in torch.cat([u.sqnorm for u in uploads]).cpu().tolist()]
+        bound = mech.delta_int * mech.delta_int
+        for cid, v in zip(survivors, sq):
+            if v > bound:
+                raise RuntimeError("Server.train: the codes of client %s have squared norm %d, beyond the sensitivity bound delta_int^2 = %.6g of "
+                                   "the mechanism: the round is void" % (getattr(self.clients[cid], "cid", cid), v, bound))
+        self.dp_last_sqnorms = sq
+        acc = self.dp_accountant
+        if acc is None:
+            acc = self.dp_accountant = mech.accountant()
+        acc.step()
+        self.dp_epsilon = acc.epsilon(delta)
+        self.logger.info('Distributed differential privacy: (epsilon, delta) = (%.4f, %g) after %d rounds; guaranteed noise multiplier z_eff = %.6g '
+                         '(asked %g; sigma_int %.6g per client, delta_int %.6g, threshold %d), realised %.6g with %d uploads; accounted at q = 1 '
+                         'whatever the sampling rate (the amplification bound is proven for the continuous Gaussian only)'
+                         % (self.dp_epsilon, delta, acc.steps, mech.z_eff, mech.noise_multiplier, mech.sigma_int, mech.delta_int, mech.threshold,
+                            mech.realised_multiplier(len(survivors)), len(survivors)))
 
     def _aggregate_dp(self, models, data_sizes, aggr_alg, sigma, clip_norm, delta):
         """the round's aggregation under ``dp_noise_multiplier`` > 0: ``FedDP`` with the server's mechanism (one per server: it holds the

@@ -740,6 +740,44 @@ int fedfr_secagg_aggregate(float* out, const float* x, unsigned* acc, const unsi
                            void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * distributed differential privacy under secure aggregation (the distributed discrete Gaussian of Kairouz, Liu, Steinke, ICML 2021) — no
+ * reference counterpart.  Every client clips its own update, encodes it as above, adds its own share of INTEGER Gaussian noise and masks
+ * the result; the sum the server unmasks carries the noise of all surviving clients.
+ * THE DISCRETE NOISE STREAM.  The target is N_Z(0, sigma^2), P(y) ~ exp(-y^2 / (2 sigma^2)) on the integers, 16 <= sigma <= 2^26 (fp64),
+ * by the rejection scheme of Canonne, Kamath, Steinke (NeurIPS 2020): a discrete Laplace proposal of scale t = floor(sigma) + 1, thinned.
+ * Attempt a = 0 ... 63 of element e = offset + j of the logical stream (seed, round, stream_id) takes the four words (w0, w1, w2, w3) of the
+ * Philox4x32-10 block of THE NOISE STREAM with
+ *   key = (seed low 32 bits, seed high 32 bits),   counter = (blk low 32, blk high 32, round low 32, stream_id),   blk = e * 64 + a (64 bits)
+ * so a value depends on (seed, round, stream_id, e) only: not on the grid, on the lane, or on how many attempts a neighbour needed.
+ * offset + n must not pass 2^58.  One attempt, in fp64, every operation rounded once, with s2 = sigma sigma, s2t = s2 / t,
+ * c = -1 / (2 s2) formed on the host:
+ *   U1 = double((w0 2^21 + (w1 >> 11)) + 1) 2^-53 in (0, 1],  U2 = double(w2 2^21 + (w3 >> 11)) 2^-53 in [0, 1)   (both exact),  B = w1 & 1
+ *   G = floor(-t log(U1));   rejected if B == 1 and G == 0;   Y = B ? -G : G                          (|Y| <= 37 t)
+ *   d = G - s2t;   p = exp((d d) c);   accepted iff U2 < p
+ * The first accepted attempt is the value.  After 64 rejections (about 1e-40 per element) the value is 0 and the element is counted as
+ * exhausted: a caller must treat a non-zero count as an error.  log and exp are the device library's; tests/ddp_cases.py restates the rest
+ * operation by operation.
+ *   THE CLIENTS' NOISE SHARES use stream_id 0x44444750 ("DDGP"; fedfr_secagg_mask_dp), beside stream_id 0 of the central mechanism's
+ *   THE NOISE STREAM; the seed is the client's own secret of the round.
+ * ------------------------------------------------------------------------------------------------ */
+/* dst[j] = the value of element offset + j, j < n, as int32 (mod 2^32).  exhausted: DEVICE int32, added to.  dst 16-byte aligned; nothing
+ * is written behind n; n = 0 is a no-op.  FEDFR_ERR_ARG for a NULL pointer, misalignment, sigma outside [16, 2^26] or offset + n > 2^58. */
+int fedfr_dgauss_fill(int* dst, size_t n, unsigned long long seed, unsigned long long round, unsigned stream_id,
+                      unsigned long long offset, double sigma, int* exhausted, void* stream);
+/* fedfr_secagg_mask with the client's clip and noise share, one pass (x and xi read once, y written once):
+ *   coef = clip_coef[0] 2^f (exact);   q = the ENCODING above of (xi - x) with this coef and limit = code_limit;
+ *   y = q + noise(noise_offset + e) + sum_s sign_s m_s mod 2^32,   noise from the stream (noise_seed, noise_round, 0x44444750) at sigma.
+ * clip_coef: DEVICE float, min(1, C / ||xi - x||) as fedfr_fedopt_sqnorm (k = 1, w = 1) leaves it: no host synchronisation between the
+ * two passes.  sqnorm: DEVICE uint64, receives (is added) the exact sum of q^2 mod 2^64, taken BEFORE the noise: one reduction per
+ * workgroup and one 64-bit atomic add (integer addition: one result whatever the order).  counters: DEVICE int32[3] {saturated,
+ * nonfinite, exhausted}, added to.  counters and sqnorm may be NULL.  FEDFR_ERR_ARG before anything is launched for what fedfr_secagg_mask
+ * refuses, frac_bits outside 8 ... 30, code_limit < 1, sigma outside [16, 2^26] or noise_offset + n > 2^58. */
+int fedfr_secagg_mask_dp(unsigned* y, const float* x, const float* xi, const float* clip_coef, int frac_bits, int code_limit,
+                         unsigned long long noise_seed, unsigned long long noise_round, unsigned long long noise_offset, double sigma,
+                         const unsigned* keys, const unsigned* nonces, const int* signs, int k, size_t n, int* counters,
+                         unsigned long long* sqnorm, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * robust aggregation — no reference counterpart: every rule above is a weighted sum, so one client that returns a poisoned, diverged or NaN
  * state moves (or wipes out) the global model.  Coordinate-wise trimmed mean / median (Yin et al., 2018) and Krum / Multi-Krum (Blanchard
  * et al., 2017) over k <= 32 flat fp32 client states (HOST arrays of k device pointers, as fedfr_fedavg_multi), as streaming passes.
