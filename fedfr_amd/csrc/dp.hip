@@ -2,9 +2,9 @@
 // Gaussian mechanism's noise fused into the server optimisers' streaming pass.  The clip is fedopt_sqnorm's (optim.hip); here:
 //   philox_fill_kernel     the raw words of the noise stream (dp.h), the part a host restatement reproduces bit for bit
 //   gaussian_fill_kernel   dst (+)= std z
-//   dp_multi_kernel<K, KIND>   fedopt_multi_kernel (optim.hip) with Delta += noise_std z before the step of the LAST pass, and with the
-//                          kind FEDOPT_PLAIN (x' = x + Delta, no moments).  The step is fedopt_one (fedopt_step.h), the noise dp_gauss4
-//                          (dp.h): one definition each, so this kernel, fedopt_multi and gaussian_fill round alike.
+//   dp_multi_kernel<K, KIND>   the shell of fedopt_pass (fedopt_step.h) WITH noise: Delta += noise_std z before the step of the LAST pass, and
+//                          the kind FEDOPT_PLAIN (x' = x + Delta, no moments).  optim.hip's fedopt_multi_kernel is the shell without noise;
+//                          the noise is dp_gauss4 (dp.h), so this kernel and gaussian_fill round alike.
 // All on the skeleton of multi_state.h: one thread per float4 = one Philox block, grid-stride, then the n % 4 tail, whose elements are the
 // leading lanes of the block behind the last whole one.
 #include "dp.h"
@@ -61,109 +61,35 @@ int dp_gaussian_fill(float* dst, size_t n, unsigned long long seed, unsigned lon
   return FEDFR_OK;
 }
 
-template <int KIND>
-__device__ __forceinline__ void dp_step(float d, float x, float& m, float& v, float& xo, const FedoptHyper& h) {
-  if constexpr (KIND == FEDOPT_PLAIN) xo = __fadd_rn(x, d);
-  else fedopt_one<KIND>(d, x, m, v, xo, h);
-}
-
-// fedopt_multi_kernel's loops and flags (first / last / scratch: see there).  noisy = last pass with noise_std > 0: wave-uniform, so a pass
-// without noise pays one branch; 0 * z is never added.
+// the pass with noise: fedopt_pass (fedopt_step.h; first / last / scratch, the aliasing rules and the wave-uniform noise test: see there)
 template <int K, int KIND>
 __global__ __launch_bounds__(MULTI_STATE_BLOCK) void dp_multi_kernel(float* xo, const float* x, StatePtrs<8> p, const float* __restrict__ coef, float* __restrict__ m,
                                                                      float* __restrict__ v, float* scratch, size_t n, int first, int last, FedoptHyper h,
                                                                      float noise_std, DpStream rs) {
-  constexpr bool HAS_M = KIND != FEDOPT_PLAIN, HAS_V = HAS_M && KIND != FEDOPT_AVGM;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  const size_t n4 = n / 4;
-  const bool noisy = last && noise_std > 0.f;
-  float c[K];
-#pragma unroll
-  for (int k = 0; k < K; ++k) c[k] = coef[k];
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    fvec<4> s[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) s[k] = ld_once<4>(p.src[k], i);
-    const float4 xv = reinterpret_cast<const float4*>(x)[i];
-    float4 d = first ? make_float4(0.f, 0.f, 0.f, 0.f) : reinterpret_cast<const float4*>(scratch)[i];
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      d.x = __fadd_rn(d.x, __fmul_rn(c[k], __fsub_rn(s[k].x, xv.x)));
-      d.y = __fadd_rn(d.y, __fmul_rn(c[k], __fsub_rn(s[k].y, xv.y)));
-      d.z = __fadd_rn(d.z, __fmul_rn(c[k], __fsub_rn(s[k].z, xv.z)));
-      d.w = __fadd_rn(d.w, __fmul_rn(c[k], __fsub_rn(s[k].w, xv.w)));
-    }
-    if (!last) {
-      reinterpret_cast<float4*>(scratch)[i] = d;
-      continue;
-    }
-    if (noisy) {
-      const float4 z = dp_gauss4(rs, i);
-      d.x = __fadd_rn(d.x, __fmul_rn(noise_std, z.x));
-      d.y = __fadd_rn(d.y, __fmul_rn(noise_std, z.y));
-      d.z = __fadd_rn(d.z, __fmul_rn(noise_std, z.z));
-      d.w = __fadd_rn(d.w, __fmul_rn(noise_std, z.w));
-    }
-    float4 mv = HAS_M ? reinterpret_cast<const float4*>(m)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 vv = HAS_V ? reinterpret_cast<const float4*>(v)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 o;
-    dp_step<KIND>(d.x, xv.x, mv.x, vv.x, o.x, h);
-    dp_step<KIND>(d.y, xv.y, mv.y, vv.y, o.y, h);
-    dp_step<KIND>(d.z, xv.z, mv.z, vv.z, o.z, h);
-    dp_step<KIND>(d.w, xv.w, mv.w, vv.w, o.w, h);
-    if (HAS_M) reinterpret_cast<float4*>(m)[i] = mv;
-    if (HAS_V) reinterpret_cast<float4*>(v)[i] = vv;
-    reinterpret_cast<float4*>(xo)[i] = o;
-  }
-  for (size_t i = n4 * 4 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const float xv = x[i];
-    float d = first ? 0.f : scratch[i];
-#pragma unroll
-    for (int k = 0; k < K; ++k) d = __fadd_rn(d, __fmul_rn(c[k], __fsub_rn(p.src[k][i], xv)));
-    if (!last) {
-      scratch[i] = d;
-      continue;
-    }
-    if (noisy) d = __fadd_rn(d, __fmul_rn(noise_std, lane_of(dp_gauss4(rs, n4), (int)(i & 3))));
-    float mv = HAS_M ? m[i] : 0.f, vv = HAS_V ? v[i] : 0.f, o;
-    dp_step<KIND>(d, xv, mv, vv, o, h);
-    if (HAS_M) m[i] = mv;
-    if (HAS_V) v[i] = vv;
-    xo[i] = o;
-  }
+  fedopt_pass<K, KIND, true>(xo, x, p, coef, m, v, scratch, n, first, last, h, noise_std, rs, (size_t)blockIdx.x * blockDim.x + threadIdx.x,
+                             (size_t)gridDim.x * blockDim.x);
 }
 
-// The checks of optim_fedopt_multi, and: noise_std finite and >= 0, offset % 4 == 0.  A chain's passes must all be given the chain's
-// (noise_std, seed, round, stream_id, offset): only the last one draws, but the entry point keeps no state to hold the others to it.
-// noise_std == 0 with one of fedopt_multi's four kinds IS fedopt_multi: routed there, so the bits are its own.
+// The checks of optim_fedopt_multi (fedopt_pass_args, with FEDOPT_PLAIN admitted), and: noise_std finite and >= 0, offset % 4 == 0.  A chain's
+// passes must all be given the chain's (noise_std, seed, round, stream_id, offset): only the last one draws, but the entry point keeps no
+// state to hold the others to it.  noise_std == 0 with one of fedopt_multi's four kinds IS fedopt_multi: routed there, so the bits are its own.
 int dp_multi(int kind, float* x_out, const float* x, const float* const* xs, const float* coef, int k, size_t n, float* m, float* v,
              float* scratch, int first, int last, float lr, float beta1, float one_minus_beta1, float beta2, float one_minus_beta2, float tau,
              float noise_std, unsigned long long seed, unsigned long long round, unsigned stream_id, unsigned long long offset, hipStream_t st) {
-  FEDFR_REQUIRE(kind >= FEDOPT_AVGM && kind <= FEDOPT_PLAIN, "dp_multi: unknown optimiser kind %d", kind);
+  FEDFR_REQUIRE(kind >= FEDOPT_AVGM && kind <= FEDOPT_PLAIN, "dp_multi: unknown optimiser kind %d", kind);      // (under this name, before the routing)
   FEDFR_REQUIRE(std::isfinite(noise_std) && noise_std >= 0.f, "dp_multi: noise_std must be finite and >= 0 (got %g)", (double)noise_std);
   FEDFR_REQUIRE(offset % 4 == 0, "dp_multi: offset %llu is not a multiple of 4", offset);
   if (noise_std == 0.f && kind != FEDOPT_PLAIN) {
     return optim_fedopt_multi(kind, x_out, x, xs, coef, k, n, m, v, scratch, first, last, lr, beta1, one_minus_beta1, beta2, one_minus_beta2, tau, st);
   }
-  FEDFR_REQUIRE(x && xs && coef && n > 0 && k >= 1 && k <= 8, "dp_multi: bad args (k=%d)", k);
-  first = first ? 1 : 0;
-  last = last ? 1 : 0;
-  const bool has_m = kind != FEDOPT_PLAIN, has_v = has_m && kind != FEDOPT_AVGM;
-  FEDFR_REQUIRE((first && last) || scratch, "dp_multi: a chained pass (first=%d last=%d) needs the scratch buffer", first, last);
-  FEDFR_REQUIRE(!last || (x_out && (!has_m || m) && (!has_v || v)), "dp_multi: the last pass needs x_out%s%s", has_m ? ", m" : "", has_v ? " and v" : "");
-  StatePtrs<8> p{};
-  uintptr_t al = (uintptr_t)x | (uintptr_t)x_out | (uintptr_t)scratch;      // (null: no bits)
-  if (has_m) al |= (uintptr_t)m;
-  if (has_v) al |= (uintptr_t)v;
-  FEDFR_TRY(state_ptrs_fill(p, xs, k, "dp_multi", "client state", al));
-  FEDFR_REQUIRE((al & 15) == 0, "dp_multi: buffers must be 16-byte aligned");
-  FEDFR_REQUIRE(((uintptr_t)coef & 3) == 0, "dp_multi: coef must be 4-byte aligned");
-  const FedoptHyper h{lr, beta1, one_minus_beta1, beta2, one_minus_beta2, tau};
+  FedoptPassArgs a;
+  FEDFR_TRY(fedopt_pass_args("dp_multi", FEDOPT_PLAIN, a, kind, x_out, x, xs, coef, k, n, m, v, scratch, first, last, lr, beta1, one_minus_beta1, beta2,
+                             one_minus_beta2, tau));
   const DpStream rs = dp_stream(seed, round, stream_id, offset);
   dispatch_int<FEDOPT_AVGM, FEDOPT_PLAIN>(kind, [&](auto kindc) {
     dispatch_int<1, 8>(k, [&](auto kc) {
-      hipLaunchKernelGGL((dp_multi_kernel<decltype(kc)::value, decltype(kindc)::value>), dim3(multi_state_grid(n)), dim3(MULTI_STATE_BLOCK), 0, st, x_out, x, p,
-                         coef, m, v, scratch, n, first, last, h, noise_std, rs);
+      hipLaunchKernelGGL((dp_multi_kernel<decltype(kc)::value, decltype(kindc)::value>), dim3(multi_state_grid(n)), dim3(MULTI_STATE_BLOCK), 0, st, x_out, x, a.p,
+                         coef, m, v, scratch, n, a.first, a.last, a.h, noise_std, rs);
     });
   });
   FEDFR_LAUNCH_CHECK("dp_multi");

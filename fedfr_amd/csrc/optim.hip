@@ -197,12 +197,13 @@ int optim_fedavg_i64(float* acc, const long long* src, float w, int n, int accum
 //                                 partial per client and block, added in ascending block order by fedopt_sqnorm_final_kernel, which also forms
 //                                 coef_i = w_i min(1, clip / sqrt(sq_i)) on the device: no host synchronisation between the two passes)
 //   fedopt_multi_kernel<K, KIND>  Delta = sum_i coef_i (x_i - x) (ascending i: subtract, multiply, add = three roundings per client), then the
-//                                 moment and parameter update of KIND.  Every fp32 operation is an explicit single-rounding intrinsic (the build
-//                                 contracts a*b+c otherwise), so tests/fedopt_cases.py restates the kernel operation by operation.
+//                                 moment and parameter update of KIND: the shell of fedopt_pass (fedopt_step.h) without noise; dp.hip's
+//                                 dp_multi_kernel is the shell with it.  Every fp32 operation is an explicit single-rounding intrinsic (the build
+//                                 contracts a*b+c otherwise), so tests/fedopt_cases.py restates the pass operation by operation.
 // The square root is __builtin_sqrtf, not __fsqrt_rn: this toolchain's __fsqrt_rn is the bare v_sqrt_f32 (1 ulp), while hipcc's default
 // (-fhip-fp32-correctly-rounded-divide-sqrt) expands __builtin_sqrtf and the division behind __fdiv_rn to correctly rounded sequences.
 // ---------------------------------------------------------------------------------------------------------
-// (the kinds, FedoptHyper and the per-element step fedopt_one: fedopt_step.h, shared with dp.hip)
+// (the kinds, FedoptHyper, the per-element step, the pass body and the host's argument check: fedopt_step.h, shared with dp.hip)
 
 template <int K>
 __global__ __launch_bounds__(MULTI_STATE_BLOCK) void fedopt_sqnorm_kernel(const float* __restrict__ x, StatePtrs<8> p, size_t n, double* __restrict__ part) {
@@ -275,82 +276,24 @@ int optim_fedopt_sqnorm(const float* x, const float* const* xs, const float* ws,
   return FEDFR_OK;
 }
 
-// first: Delta starts at 0 (else at scratch); last: the update is applied (else Delta goes to scratch and m, v, x are untouched).  xo may be x;
-// scratch may be a client state on a non-last pass and xo on the last one (every thread reads index i of each before it writes index i).
-// Two explicit loops, not for_each_vec_then_tail: through the callable 23 of the 32 instantiations need 4-11 more VGPRs.
+// the pass without noise: fedopt_pass (fedopt_step.h; first / last / scratch and the aliasing rules: see there)
 template <int K, int KIND>
 __global__ __launch_bounds__(MULTI_STATE_BLOCK) void fedopt_multi_kernel(float* xo, const float* x, StatePtrs<8> p, const float* __restrict__ coef, float* __restrict__ m,
                                                            float* __restrict__ v, float* scratch, size_t n, int first, int last,
                                                            FedoptHyper h) {
-  constexpr bool HAS_V = KIND != FEDOPT_AVGM;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  const size_t n4 = n / 4;
-  float c[K];
-#pragma unroll
-  for (int k = 0; k < K; ++k) c[k] = coef[k];
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    fvec<4> s[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) s[k] = ld_once<4>(p.src[k], i);
-    const float4 xv = reinterpret_cast<const float4*>(x)[i];
-    float4 d = first ? make_float4(0.f, 0.f, 0.f, 0.f) : reinterpret_cast<const float4*>(scratch)[i];
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      d.x = __fadd_rn(d.x, __fmul_rn(c[k], __fsub_rn(s[k].x, xv.x)));
-      d.y = __fadd_rn(d.y, __fmul_rn(c[k], __fsub_rn(s[k].y, xv.y)));
-      d.z = __fadd_rn(d.z, __fmul_rn(c[k], __fsub_rn(s[k].z, xv.z)));
-      d.w = __fadd_rn(d.w, __fmul_rn(c[k], __fsub_rn(s[k].w, xv.w)));
-    }
-    if (!last) {
-      reinterpret_cast<float4*>(scratch)[i] = d;
-      continue;
-    }
-    float4 mv = reinterpret_cast<const float4*>(m)[i];
-    float4 vv = HAS_V ? reinterpret_cast<const float4*>(v)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 o;
-    fedopt_one<KIND>(d.x, xv.x, mv.x, vv.x, o.x, h);
-    fedopt_one<KIND>(d.y, xv.y, mv.y, vv.y, o.y, h);
-    fedopt_one<KIND>(d.z, xv.z, mv.z, vv.z, o.z, h);
-    fedopt_one<KIND>(d.w, xv.w, mv.w, vv.w, o.w, h);
-    reinterpret_cast<float4*>(m)[i] = mv;
-    if (HAS_V) reinterpret_cast<float4*>(v)[i] = vv;
-    reinterpret_cast<float4*>(xo)[i] = o;
-  }
-  for (size_t i = n4 * 4 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const float xv = x[i];
-    float d = first ? 0.f : scratch[i];
-#pragma unroll
-    for (int k = 0; k < K; ++k) d = __fadd_rn(d, __fmul_rn(c[k], __fsub_rn(p.src[k][i], xv)));
-    if (!last) {
-      scratch[i] = d;
-      continue;
-    }
-    float mv = m[i], vv = HAS_V ? v[i] : 0.f, o;
-    fedopt_one<KIND>(d, xv, mv, vv, o, h);
-    m[i] = mv;
-    if (HAS_V) v[i] = vv;
-    xo[i] = o;
-  }
+  fedopt_pass<K, KIND, false>(xo, x, p, coef, m, v, scratch, n, first, last, h, 0.f, DpStream{}, (size_t)blockIdx.x * blockDim.x + threadIdx.x,
+                              (size_t)gridDim.x * blockDim.x);
 }
 int optim_fedopt_multi(int kind, float* x_out, const float* x, const float* const* xs, const float* coef, int k, size_t n, float* m, float* v,
                        float* scratch, int first, int last, float lr, float beta1, float one_minus_beta1, float beta2, float one_minus_beta2,
                        float tau, hipStream_t st) {
-  FEDFR_REQUIRE(kind >= FEDOPT_AVGM && kind <= FEDOPT_YOGI, "fedopt_multi: unknown optimiser kind %d", kind);
-  FEDFR_REQUIRE(x && xs && coef && n > 0 && k >= 1 && k <= 8, "fedopt_multi: bad args (k=%d)", k);
-  first = first ? 1 : 0;
-  last = last ? 1 : 0;
-  FEDFR_REQUIRE((first && last) || scratch, "fedopt_multi: a chained pass (first=%d last=%d) needs the scratch buffer", first, last);
-  FEDFR_REQUIRE(!last || (x_out && m && (kind == FEDOPT_AVGM || v)), "fedopt_multi: the last pass needs x_out, m%s", kind == FEDOPT_AVGM ? "" : " and v");
-  StatePtrs<8> p{};
-  uintptr_t al = (uintptr_t)x | (uintptr_t)x_out | (uintptr_t)m | (uintptr_t)v | (uintptr_t)scratch;      // (null: no bits)
-  FEDFR_TRY(state_ptrs_fill(p, xs, k, "fedopt_multi", "client state", al));
-  FEDFR_REQUIRE((al & 15) == 0, "fedopt_multi: buffers must be 16-byte aligned");
-  FEDFR_REQUIRE(((uintptr_t)coef & 3) == 0, "fedopt_multi: coef must be 4-byte aligned");
-  const FedoptHyper h{lr, beta1, one_minus_beta1, beta2, one_minus_beta2, tau};
+  FedoptPassArgs a;
+  FEDFR_TRY(fedopt_pass_args("fedopt_multi", FEDOPT_YOGI, a, kind, x_out, x, xs, coef, k, n, m, v, scratch, first, last, lr, beta1, one_minus_beta1, beta2,
+                             one_minus_beta2, tau));
   dispatch_int<FEDOPT_AVGM, FEDOPT_YOGI>(kind, [&](auto kindc) {
     dispatch_int<1, 8>(k, [&](auto kc) {
-      hipLaunchKernelGGL((fedopt_multi_kernel<decltype(kc)::value, decltype(kindc)::value>), dim3(multi_state_grid(n)), dim3(MULTI_STATE_BLOCK), 0, st, x_out, x, p,
-                         coef, m, v, scratch, n, first, last, h);
+      hipLaunchKernelGGL((fedopt_multi_kernel<decltype(kc)::value, decltype(kindc)::value>), dim3(multi_state_grid(n)), dim3(MULTI_STATE_BLOCK), 0, st, x_out, x, a.p,
+                         coef, m, v, scratch, n, a.first, a.last, a.h);
     });
   });
   FEDFR_LAUNCH_CHECK("fedopt_multi");

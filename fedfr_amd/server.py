@@ -2,13 +2,13 @@
 averaging of client models, as HIP kernels over flat buffers (single process) or one RCCL all-reduce over
 xGMI when every client is its own rank (one client = one MI355X); the spread-out step on the clients' class centres
 (reference server.py:48-63, :340-371) on one fused HIP kernel; and the round's 1:1 verification of the global model with its
-checkpoints (reference server.py:135-148).  Build extensions beyond the reference's FedAvg: the server optimisers (``FedOpt``), the
-robust rules (``FedRobust``: coordinate-wise trimmed mean / median, Krum / Multi-Krum) and compressed client uploads (``FedCompressed``:
-8 / 4-bit block-scaled deltas with error feedback; ``FedSparse``: top-k sparsified deltas with error feedback; see compress.py) and
-client-level differential privacy (``FedDP``: clipped updates and Gaussian noise drawn on the device; see privacy.py) and secure
-aggregation (``FedSecAgg``: pairwise-masked fixed-point uploads of which the server learns only the sum; see secagg.py), and the two
-together (``FedSecAggDP``: every client clips its own update and adds its share of discrete Gaussian noise before masking it; see
-privacy.DistributedDiscreteGaussian)."""
+checkpoints (reference server.py:135-148).  Build extensions beyond the reference's FedAvg, one module-level round function each: the
+server optimisers (``FedOpt``), the robust rules (``FedRobust``), client-level differential privacy (``FedDP``; privacy.py), and the
+rounds from UPLOADS instead of states: 8 / 4-bit and top-k deltas with error feedback (``FedCompressed``, ``FedSparse``; compress.py),
+pairwise-masked fixed-point updates (``FedSecAgg``; secagg.py) and those with the clients' own clip and discrete Gaussian noise
+(``FedSecAggDP``).  What these share exists once: the chained delta step (``ServerOptimizer._chain``), the head, the tail and the masked
+sum of a round from uploads (``_upload_round_head``, ``_upload_round_tail``, ``_masked_sum``).  ``Server.train`` runs a round in four
+stages: settings and refusals, local training, the uploads, the aggregation."""
 from __future__ import annotations
 
 import copy
@@ -16,6 +16,7 @@ import ctypes
 import logging
 import random
 from collections import OrderedDict
+from types import SimpleNamespace
 from typing import List, Sequence
 
 import numpy as np
@@ -55,11 +56,21 @@ class _Workspace:
         return self.buf.data_ptr(), self.buf.numel() * 8
 
 
+def _normalised(weights: Sequence[float]) -> List[float]:
+    """w_i / Σw: the reference's ``weights[i] / sum(weights)`` (server.py:27)"""
+    tot = sum(weights)
+    return [w / tot for w in weights]
+
+
+def _f32_vector(ws: Sequence[float]):
+    """``ws`` rounded to fp32, as the ctypes array a kernel entry point takes its ≤ 8 weights in"""
+    return (_C.f32 * len(ws))(*[float(np.float32(w)) for w in ws])
+
+
 def _multi(dst: torch.Tensor, srcs: Sequence[torch.Tensor], ws: Sequence[float], accumulate: bool):
     """dst (+)= Σ_i ws[i]·srcs[i] over ≤ 8 same-shape contiguous fp32 tensors in one kernel (csrc/optim.hip: fedavg_multi_kernel)."""
     _check_states(dst, srcs, "FedPavg")
-    wv = (_C.f32 * len(srcs))(*[float(np.float32(w)) for w in ws])
-    _C.call("fedfr_fedavg_multi", dst.data_ptr(), _C.ptr_array(srcs), wv, len(srcs), dst.numel(), 1 if accumulate else 0, _C.stream())
+    _C.call("fedfr_fedavg_multi", dst.data_ptr(), _C.ptr_array(srcs), _f32_vector(ws), len(srcs), dst.numel(), 1 if accumulate else 0, _C.stream())
 
 
 def _client_weights(what: str, models: List[dict], weights: Sequence[float], also=()) -> List[float]:
@@ -70,8 +81,7 @@ def _client_weights(what: str, models: List[dict], weights: Sequence[float], als
                            % (what, "global and the " if also else ""))
     if len(weights) != len(models):
         raise RuntimeError("fedfr_amd.%s: %d weights for %d client states" % (what, len(weights), len(models)))
-    tot = sum(weights)
-    return [w / tot for w in weights]
+    return _normalised(weights)
 
 
 def _average_stats(models: List[dict], ws: Sequence[float], stats_rule=None):
@@ -109,8 +119,7 @@ def FedPavg(models: List[dict], weights: Sequence[float]):
         for c0 in range(0, len(models), 8):
             _multi(P, [m.flat[0] for m in models[c0:c0 + 8]], ws[c0:c0 + 8], c0 > 0)
         return FlatStateDict.from_flat((P, *_average_stats(models, ws)), models[0].table, models[0].layers)
-    tot = sum(weights)
-    ws = [w / tot for w in weights]
+    ws = _normalised(weights)
     aggr = OrderedDict()
     for name in models[0]:
         t0 = models[0][name]
@@ -132,6 +141,7 @@ def FedPavg(models: List[dict], weights: Sequence[float]):
 
 # ---- server optimisers (Reddi et al., "Adaptive Federated Optimization"): csrc/optim.hip fedopt_sqnorm_kernel / fedopt_multi_kernel
 FEDOPT_KINDS = {"AVGM": 0, "ADAGRAD": 1, "ADAM": 2, "YOGI": 3}
+FEDOPT_PLAIN = 4                       # x' = x + Δ, no moments (DP-FedAvg proper): fedfr_dp_multi only
 AGGR_ALG_KINDS = {"FedAvgM": "AVGM", "FedAdagrad": "ADAGRAD", "FedAdam": "ADAM", "FedYogi": "YOGI"}
 
 
@@ -195,8 +205,7 @@ class ServerOptimizer:
         wsp = self._ws.ensure(int(_C.lib().fedfr_fedopt_sqnorm_workspace_bytes(min(8, len(xs)), n)), dev)
         for c0 in range(0, len(xs), 8):
             grp = xs[c0:c0 + 8]
-            wv = (_C.f32 * len(grp))(*[float(np.float32(w)) for w in ws[c0:c0 + 8]])
-            _C.call("fedfr_fedopt_sqnorm", x.data_ptr(), _C.ptr_array(grp), wv, len(grp), n, float(np.float32(self.clip_norm)),
+            _C.call("fedfr_fedopt_sqnorm", x.data_ptr(), _C.ptr_array(grp), _f32_vector(ws[c0:c0 + 8]), len(grp), n, float(np.float32(self.clip_norm)),
                     sq.data_ptr() + 8 * c0, coef.data_ptr() + 4 * c0, *wsp, _C.stream())
         self.last_update_sqnorm, self.last_coef = sq, coef
         return coef
@@ -207,17 +216,25 @@ class ServerOptimizer:
         _check_states(x, list(xs) + [x_out], "ServerOptimizer")
         if coef.numel() != len(xs) or coef.dtype != f32 or coef.device != x.device or not coef.is_contiguous():
             raise RuntimeError("fedfr_amd.ServerOptimizer: coef must be a contiguous fp32 device tensor with one entry per client state")
-        self._ensure(x)
+        self._chain(x_out, x, xs, coef)
+
+    def _chain(self, x_out, x, xs, coef, noise=None, plain=False):
+        """THE chained delta step: ≤ 8 client states per pass, ascending; the last pass applies the step.  Through fedfr_fedopt_multi, or
+        with ``noise`` = (noise_std, seed, round, stream_id, offset), given to every pass, through fedfr_dp_multi, whose last pass adds
+        noise_std·z to Δ.  ``plain`` (with ``noise`` only): the kind FEDOPT_PLAIN, x_out = x + Δ, no moments, no round counted."""
+        if not plain:
+            self._ensure(x)
         n = x.numel()
+        entry, noise = ("fedfr_fedopt_multi", ()) if noise is None else ("fedfr_dp_multi", tuple(noise))
         if len(xs) > 8 and (self._scratch is None or self._scratch.numel() != n or self._scratch.device != x.device):
-            self._scratch = torch.empty(n, dtype=f32, device=x.device)
+            self._scratch = torch.empty(n, dtype=f32, device=x.device)      # the Δ buffer a chain runs through: kept between rounds
         for c0 in range(0, len(xs), 8):
             grp = xs[c0:c0 + 8]
-            _C.call("fedfr_fedopt_multi", FEDOPT_KINDS[self.kind], x_out.data_ptr(), x.data_ptr(), _C.ptr_array(grp), coef.data_ptr() + 4 * c0, len(grp), n,
-                    self.m.data_ptr(), self.v.data_ptr() if self.adaptive else None,
-                    self._scratch.data_ptr() if len(xs) > 8 else None, 1 if c0 == 0 else 0, 1 if c0 + 8 >= len(xs) else 0, *self.hyper(),
-                    _C.stream())
-        self.rounds += 1
+            _C.call(entry, FEDOPT_PLAIN if plain else FEDOPT_KINDS[self.kind], x_out.data_ptr(), x.data_ptr(), _C.ptr_array(grp), coef.data_ptr() + 4 * c0,
+                    len(grp), n, None if plain else self.m.data_ptr(), self.v.data_ptr() if self.adaptive and not plain else None,
+                    self._scratch.data_ptr() if len(xs) > 8 else None, 1 if c0 == 0 else 0, 1 if c0 + 8 >= len(xs) else 0, *self.hyper(), *noise, _C.stream())
+        if not plain:
+            self.rounds += 1
 
     def _pass(self, x_out, x, xi, coef, scratch, first, last):
         _C.call("fedfr_fedopt_multi", FEDOPT_KINDS[self.kind], _C.ptr(x_out), x.data_ptr(), _C.ptr_array([xi]), coef.data_ptr(), 1, x.numel(),
@@ -273,9 +290,6 @@ def FedOpt(global_state, models: List[dict], weights: Sequence[float], opt: Serv
 
 
 # ---- client-level differential privacy: csrc/dp.hip dp_multi_kernel (the clip: fedopt_sqnorm_kernel; mechanism and accounting: privacy.py)
-FEDOPT_PLAIN = 4
-
-
 def FedDP(global_state, models: List[dict], weights: Sequence[float], mech, opt: ServerOptimizer = None):
     """One DP-FedAvg round: the PARAMETERS of the new global state are x + step(Σ_i c_i (x_i - x) + noise_std z) with x = ``global_state``'s
     parameters, c_i = w_i min(1, clip_norm / ||x_i - x||) (``ServerOptimizer.coefficients``, as ``FedOpt``), w_i = ``weights[i]`` / Σ weights,
@@ -296,23 +310,9 @@ def FedDP(global_state, models: List[dict], weights: Sequence[float], mech, opt:
         if clipper is None or clipper.clip_norm != mech.clip_norm:
             clipper = mech._clipper = ServerOptimizer("AVGM", clip_norm=mech.clip_norm)
     coef = clipper.coefficients(x, xs, ws)
-    n = x.numel()
     P = torch.empty_like(x)
-    if opt is not None:
-        opt._ensure(x)
-    if len(xs) > 8 and (clipper._scratch is None or clipper._scratch.numel() != n or clipper._scratch.device != x.device):
-        clipper._scratch = torch.empty(n, dtype=f32, device=x.device)
-    kind = FEDOPT_PLAIN if opt is None else FEDOPT_KINDS[opt.kind]
-    hyper = clipper.hyper()
     std = mech.noise_std([float(np.float32(w)) for w in ws])
-    for c0 in range(0, len(xs), 8):
-        grp = xs[c0:c0 + 8]
-        _C.call("fedfr_dp_multi", kind, P.data_ptr(), x.data_ptr(), _C.ptr_array(grp), coef.data_ptr() + 4 * c0, len(grp), n,
-                None if opt is None else opt.m.data_ptr(), opt.v.data_ptr() if opt is not None and opt.adaptive else None,
-                clipper._scratch.data_ptr() if len(xs) > 8 else None, 1 if c0 == 0 else 0, 1 if c0 + 8 >= len(xs) else 0, *hyper,
-                std, mech.seed, mech.round, mech.stream_id, 0, _C.stream())
-    if opt is not None:
-        opt.rounds += 1
+    clipper._chain(P, x, xs, coef, noise=(std, mech.seed, mech.round, mech.stream_id, 0), plain=opt is None)
     mech.advance()
     return FlatStateDict.from_flat((P, *_average_stats(models, ws)), models[0].table, models[0].layers)
 
@@ -445,6 +445,36 @@ class _StatsOnly:
         self.flat = (None, stats, counters)
 
 
+def _upload_round_head(what, global_state, uploads, is_upload, noun, expected, weights, server_opt, robust_why, clip_refusal):
+    """What every round from uploads refuses, in this order: a global state that is no FlatStateDict with its flat buffers; uploads that
+    are empty or not all ``is_upload`` (``noun``: "updates" / "uploads", ``expected``: what they must be); another number of ``weights``
+    (None: the round takes none); a robust rule (``robust_why``); a server optimiser that clips (``clip_refusal``: the sentence that says
+    why not); global parameters off the GPU.  Returns those parameters and the weights, normalised (``weights`` None: uniform)."""
+    if not isinstance(global_state, FlatStateDict) or global_state.flat is None:
+        raise RuntimeError("fedfr_amd.%s: the global state must be a FlatStateDict (client.flat_state_dict)" % what)
+    if not uploads or not all(is_upload(u) for u in uploads):
+        raise RuntimeError("fedfr_amd.%s: the client %s must be %s" % (what, noun, expected))
+    if weights is not None and len(weights) != len(uploads):
+        raise RuntimeError("fedfr_amd.%s: %d weights for %d client %s" % (what, len(weights), len(uploads), noun))
+    if isinstance(server_opt, RobustAggregator):
+        raise ValueError("%s: a robust rule (%s) needs whole client states, %s" % (what, server_opt.kind, robust_why))
+    if server_opt is not None and server_opt.clip_norm > 0:
+        raise ValueError("%s: %s" % (what, clip_refusal))
+    x = global_state.flat[0]
+    _check_states(x, [], what)
+    return x, _normalised(weights if weights is not None else [1.0] * len(uploads))
+
+
+def _upload_round_tail(global_state, P: torch.Tensor, x: torch.Tensor, uploads, ws: Sequence[float], server_opt):
+    """The new global state of a round from uploads: ``P`` holds x + the aggregate, or with ``server_opt`` the aggregate alone, which then
+    is the pseudo-gradient Δ of ``server_opt.apply_delta`` (in place); the BN running statistics and counters the uploads carry in the clear
+    are averaged with ``ws`` exactly as ``FedPavg`` averages them."""
+    if server_opt is not None:
+        server_opt.apply_delta(P, x, P)
+    stats = _average_stats([_StatsOnly(u.stats, u.counters) for u in uploads], ws)
+    return FlatStateDict.from_flat((P, *stats), global_state.table, global_state.layers)
+
+
 def FedCompressed(global_state, updates, weights: Sequence[float], server_opt=None):
     """One round from compressed uploads (``compress.CompressedDelta``, all of one width): the PARAMETERS of the new global state are
     x + Σ_i (n_i/Σn)·dq_i with x = ``global_state``'s parameters and dq_i the dequantised upload of client i (fedfr_delta_aggregate: ≤ 8
@@ -455,21 +485,10 @@ def FedCompressed(global_state, updates, weights: Sequence[float], server_opt=No
     exactly as ``FedPavg`` averages them.  A block a client sent as non-finite is NaN in the result, as it would be with fp32 uploads.
     Only a GPU ``FlatStateDict`` is accepted as ``global_state``."""
     from .compress import CompressedDelta
-    if not isinstance(global_state, FlatStateDict) or global_state.flat is None:
-        raise RuntimeError("fedfr_amd.FedCompressed: the global state must be a FlatStateDict (client.flat_state_dict)")
-    if not updates or not all(isinstance(u, CompressedDelta) for u in updates):
-        raise RuntimeError("fedfr_amd.FedCompressed: the client updates must be CompressedDeltas (Client.get_compressed_update)")
-    if len(weights) != len(updates):
-        raise RuntimeError("fedfr_amd.FedCompressed: %d weights for %d client updates" % (len(weights), len(updates)))
-    if isinstance(server_opt, RobustAggregator):
-        raise ValueError("FedCompressed: a robust rule (%s) needs whole client states, not compressed uploads" % server_opt.kind)
-    if server_opt is not None and server_opt.clip_norm > 0:
-        raise ValueError("FedCompressed: clip_norm > 0 needs per-client norms of the dequantised deltas, which compressed uploads do not "
-                         "provide; use FedOpt on uncompressed states")
-    tot = sum(weights)
-    ws = [w / tot for w in weights]
-    x = global_state.flat[0]
-    _check_states(x, [], "FedCompressed")
+    x, ws = _upload_round_head("FedCompressed", global_state, updates, lambda u: isinstance(u, CompressedDelta), "updates",
+                               "CompressedDeltas (Client.get_compressed_update)", weights, server_opt, "not compressed uploads",
+                               "clip_norm > 0 needs per-client norms of the dequantised deltas, which compressed uploads do not provide; use "
+                               "FedOpt on uncompressed states")
     n, bits = x.numel(), updates[0].bits
     lib = _C.lib()
     for u in updates:
@@ -483,17 +502,40 @@ def FedCompressed(global_state, updates, weights: Sequence[float], server_opt=No
     for c0 in range(0, len(updates), 8):
         grp = updates[c0:c0 + 8]
         last = c0 + 8 >= len(updates)
-        wv = (_C.f32 * len(grp))(*[float(np.float32(w)) for w in ws[c0:c0 + 8]])
         if n:
             _C.call("fedfr_delta_aggregate", P.data_ptr(), x.data_ptr() if last and server_opt is None else None, _C.ptr_array([u.codes for u in grp]),
-                    _C.ptr_array([u.scales for u in grp]), wv, len(grp), bits, n, 1 if c0 > 0 else 0, _C.stream())
-    if server_opt is not None:
-        server_opt.apply_delta(P, x, P)
-    stats = _average_stats([_StatsOnly(u.stats, u.counters) for u in updates], ws)
-    return FlatStateDict.from_flat((P, *stats), global_state.table, global_state.layers)
+                    _C.ptr_array([u.scales for u in grp]), _f32_vector(ws[c0:c0 + 8]), len(grp), bits, n, 1 if c0 > 0 else 0, _C.stream())
+    return _upload_round_tail(global_state, P, x, updates, ws, server_opt)
 
 
 # ---- secure aggregation: csrc/secagg.hip secagg_mask_kernel (client side, secagg.py) / secagg_aggregate_kernel
+def _masked_sum(what, x: torch.Tensor, uploads, recovery_streams, frac_bits: int, rescale: float, add_x: bool, mismatch: str) -> torch.Tensor:
+    """(``add_x``: x +) float(int32(S)) 2^-``frac_bits`` ``rescale`` as a new tensor, S = Σ_i y_i + Σ_r sign_r m_r mod 2^32 over the masked
+    ``uploads`` and the ``recovery_streams`` (fedfr_secagg_aggregate: ≤ 8 uploads and ≤ 32 streams per pass; more chain passes through an
+    integer buffer, and the last pass alone scales and adds x).  RuntimeError for an upload of other fraction bits or parameter count
+    (``mismatch``: the sentence, the upload's two numbers left open) or whose ``y`` is not n contiguous int32 words on x's device."""
+    from .secagg import stream_arrays
+    n = x.numel()
+    for u in uploads:
+        if u.frac_bits != frac_bits or u.n != n:
+            raise RuntimeError("fedfr_amd.%s: %s" % (what, mismatch % (u.frac_bits, u.n)))
+        if u.y.dtype != torch.int32 or u.y.numel() != n or u.y.device != x.device or not u.y.is_contiguous():
+            raise RuntimeError("fedfr_amd.%s: y must be a contiguous int32 tensor of %d words on %s" % (what, n, x.device))
+    streams = list(recovery_streams)
+    passes = max((len(uploads) + 7) // 8, (len(streams) + 31) // 32)
+    acc = torch.empty(n, dtype=torch.int32, device=x.device) if passes > 1 else None
+    P = torch.empty_like(x)
+    for p in range(passes):
+        grp, sgrp = uploads[8 * p:8 * p + 8], streams[32 * p:32 * p + 32]
+        last = p == passes - 1
+        keys, nonces, signs = stream_arrays(sgrp)
+        if n:
+            _C.call("fedfr_secagg_aggregate", P.data_ptr(), x.data_ptr() if last and add_x else None, _C.ptr(acc),
+                    _C.ptr_array([u.y for u in grp]), len(grp), keys, nonces, signs, len(sgrp), frac_bits, rescale, n, 1 if p == 0 else 0,
+                    1 if last else 0, _C.stream())
+    return P
+
+
 def FedSecAgg(global_state, uploads, weights: Sequence[float], recovery_streams, rescale: float = 1.0, server_opt=None):
     """One round from masked uploads (``secagg.MaskedUpdate``, all of one ``frac_bits``): the PARAMETERS of the new global state are
     x + float(int32(S)) 2^-f rescale with x = ``global_state``'s parameters and S = Σ_i y_i + Σ_r sign_r m_r mod 2^32 over the uploads
@@ -505,47 +547,17 @@ def FedSecAgg(global_state, uploads, weights: Sequence[float], recovery_streams,
     raises ``ValueError`` (the clip needs per-client norms, which masked uploads hide by design).  BN running statistics and
     ``num_batches_tracked`` arrive UNMASKED and are averaged over the uploads with ``weights`` exactly as ``FedPavg`` averages them.  Only a
     GPU ``FlatStateDict`` is accepted as ``global_state``."""
-    from .secagg import MaskedUpdate, stream_arrays
-    if not isinstance(global_state, FlatStateDict) or global_state.flat is None:
-        raise RuntimeError("fedfr_amd.FedSecAgg: the global state must be a FlatStateDict (client.flat_state_dict)")
-    if not uploads or not all(isinstance(u, MaskedUpdate) for u in uploads):
-        raise RuntimeError("fedfr_amd.FedSecAgg: the client uploads must be MaskedUpdates (Client.get_masked_update)")
-    if len(weights) != len(uploads):
-        raise RuntimeError("fedfr_amd.FedSecAgg: %d weights for %d client uploads" % (len(weights), len(uploads)))
-    if isinstance(server_opt, RobustAggregator):
-        raise ValueError("FedSecAgg: a robust rule (%s) needs whole client states, which masked uploads hide" % server_opt.kind)
-    if server_opt is not None and server_opt.clip_norm > 0:
-        raise ValueError("FedSecAgg: clip_norm > 0 needs per-client norms of the updates, which masked uploads hide by design")
+    from .secagg import MaskedUpdate
     rescale = float(np.float32(rescale))
     if not (np.isfinite(rescale) and rescale >= 1.0):
         raise ValueError("FedSecAgg: rescale is fp32(1 / sum of the survivors' weights), a finite number >= 1 (got %r)" % (rescale,))
-    tot = sum(weights)
-    ws = [w / tot for w in weights]
-    x = global_state.flat[0]
-    _check_states(x, [], "FedSecAgg")
-    n, frac_bits = x.numel(), uploads[0].frac_bits
-    for u in uploads:
-        if u.frac_bits != frac_bits or u.n != n:
-            raise RuntimeError("fedfr_amd.FedSecAgg: an upload of %d fraction bits and %d parameters among uploads of %d bits for %d parameters"
-                               % (u.frac_bits, u.n, frac_bits, n))
-        if u.y.dtype != torch.int32 or u.y.numel() != n or u.y.device != x.device or not u.y.is_contiguous():
-            raise RuntimeError("fedfr_amd.FedSecAgg: y must be a contiguous int32 tensor of %d words on %s" % (n, x.device))
-    streams = list(recovery_streams)
-    passes = max((len(uploads) + 7) // 8, (len(streams) + 31) // 32)
-    acc = torch.empty(n, dtype=torch.int32, device=x.device) if passes > 1 else None
-    P = torch.empty_like(x)
-    for p in range(passes):
-        grp, sgrp = uploads[8 * p:8 * p + 8], streams[32 * p:32 * p + 32]
-        last = p == passes - 1
-        keys, nonces, signs = stream_arrays(sgrp)
-        if n:
-            _C.call("fedfr_secagg_aggregate", P.data_ptr(), x.data_ptr() if last and server_opt is None else None, _C.ptr(acc),
-                    _C.ptr_array([u.y for u in grp]), len(grp), keys, nonces, signs, len(sgrp), frac_bits, rescale, n, 1 if p == 0 else 0,
-                    1 if last else 0, _C.stream())
-    if server_opt is not None:
-        server_opt.apply_delta(P, x, P)
-    stats = _average_stats([_StatsOnly(u.stats, u.counters) for u in uploads], ws)
-    return FlatStateDict.from_flat((P, *stats), global_state.table, global_state.layers)
+    x, ws = _upload_round_head("FedSecAgg", global_state, uploads, lambda u: isinstance(u, MaskedUpdate), "uploads",
+                               "MaskedUpdates (Client.get_masked_update)", weights, server_opt, "which masked uploads hide",
+                               "clip_norm > 0 needs per-client norms of the updates, which masked uploads hide by design")
+    frac_bits = uploads[0].frac_bits
+    P = _masked_sum("FedSecAgg", x, uploads, recovery_streams, frac_bits, rescale, server_opt is None,
+                    "an upload of %%d fraction bits and %%d parameters among uploads of %d bits for %d parameters" % (frac_bits, x.numel()))
+    return _upload_round_tail(global_state, P, x, uploads, ws, server_opt)
 
 
 # ---- distributed differential privacy: csrc/ddp.hip ddp_mask_kernel (client side, secagg.py) / secagg_aggregate_kernel
@@ -558,48 +570,23 @@ def FedSecAggDP(global_state, uploads, recovery_streams, mech, server_opt=None):
     arrive UNMASKED and are averaged uniformly, outside the mechanism.  At least ``mech.threshold`` uploads are required: with fewer the
     sum carries less noise than the accountant is told."""
     from .privacy import DistributedDiscreteGaussian
-    from .secagg import MaskedUpdate, stream_arrays
-    if not isinstance(global_state, FlatStateDict) or global_state.flat is None:
-        raise RuntimeError("fedfr_amd.FedSecAggDP: the global state must be a FlatStateDict (client.flat_state_dict)")
+    from .secagg import MaskedUpdate
+    # the mechanism's own checks come first: what follows them reads the mechanism
     if not isinstance(mech, DistributedDiscreteGaussian):
         raise RuntimeError("fedfr_amd.FedSecAggDP: mech must be a privacy.DistributedDiscreteGaussian")
-    if not uploads or not all(isinstance(u, MaskedUpdate) and u.sqnorm is not None for u in uploads):
-        raise RuntimeError("fedfr_amd.FedSecAggDP: the client uploads must be the MaskedUpdates of SecAggClient.mask_dp (Client.get_masked_update "
-                           "with dp=...)")
-    if not mech.threshold <= len(uploads) <= mech.participants:
+    if uploads and not mech.threshold <= len(uploads) <= mech.participants:
         raise ValueError("FedSecAggDP: %d uploads, the mechanism needs %d to %d (its threshold and its participants)"
                          % (len(uploads), mech.threshold, mech.participants))
-    if isinstance(server_opt, RobustAggregator):
-        raise ValueError("FedSecAggDP: a robust rule (%s) needs whole client states, which masked uploads hide" % server_opt.kind)
-    if server_opt is not None and server_opt.clip_norm > 0:
-        raise ValueError("FedSecAggDP: the clients have clipped their own updates at %g; a server optimiser with clip_norm > 0 needs per-client "
-                         "norms, which masked uploads hide by design" % mech.clip_norm)
-    x = global_state.flat[0]
-    _check_states(x, [], "FedSecAggDP")
-    n, frac_bits = x.numel(), mech.frac_bits
-    for u in uploads:
-        if u.frac_bits != frac_bits or u.n != n or n != mech.n:
-            raise RuntimeError("fedfr_amd.FedSecAggDP: an upload of %d fraction bits and %d parameters under a mechanism of %d bits for %d parameters "
-                               "(the state has %d)" % (u.frac_bits, u.n, frac_bits, mech.n, n))
-        if u.y.dtype != torch.int32 or u.y.numel() != n or u.y.device != x.device or not u.y.is_contiguous():
-            raise RuntimeError("fedfr_amd.FedSecAggDP: y must be a contiguous int32 tensor of %d words on %s" % (n, x.device))
-    rescale = float(np.float32(1.0 / len(uploads)))
-    streams = list(recovery_streams)
-    passes = max((len(uploads) + 7) // 8, (len(streams) + 31) // 32)
-    acc = torch.empty(n, dtype=torch.int32, device=x.device) if passes > 1 else None
-    P = torch.empty_like(x)
-    for p in range(passes):
-        grp, sgrp = uploads[8 * p:8 * p + 8], streams[32 * p:32 * p + 32]
-        last = p == passes - 1
-        keys, nonces, signs = stream_arrays(sgrp)
-        if n:
-            _C.call("fedfr_secagg_aggregate", P.data_ptr(), x.data_ptr() if last and server_opt is None else None, _C.ptr(acc),
-                    _C.ptr_array([u.y for u in grp]), len(grp), keys, nonces, signs, len(sgrp), frac_bits, rescale, n, 1 if p == 0 else 0,
-                    1 if last else 0, _C.stream())
-    if server_opt is not None:
-        server_opt.apply_delta(P, x, P)
-    stats = _average_stats([_StatsOnly(u.stats, u.counters) for u in uploads], [1.0 / len(uploads)] * len(uploads))
-    return FlatStateDict.from_flat((P, *stats), global_state.table, global_state.layers)
+    x, ws = _upload_round_head("FedSecAggDP", global_state, uploads, lambda u: isinstance(u, MaskedUpdate) and u.sqnorm is not None, "uploads",
+                               "the MaskedUpdates of SecAggClient.mask_dp (Client.get_masked_update with dp=...)", None, server_opt,
+                               "which masked uploads hide", "the clients have clipped their own updates at %g; a server optimiser with clip_norm > 0 "
+                               "needs per-client norms, which masked uploads hide by design" % mech.clip_norm)
+    mismatch = "an upload of %%d fraction bits and %%d parameters under a mechanism of %d bits for %d parameters (the state has %d)" \
+        % (mech.frac_bits, mech.n, x.numel())
+    if x.numel() != mech.n:
+        raise RuntimeError("fedfr_amd.FedSecAggDP: %s" % (mismatch % (uploads[0].frac_bits, uploads[0].n)))
+    P = _masked_sum("FedSecAggDP", x, uploads, recovery_streams, mech.frac_bits, float(np.float32(1.0 / len(uploads))), server_opt is None, mismatch)
+    return _upload_round_tail(global_state, P, x, uploads, ws, server_opt)
 
 
 # ---- top-k uploads: csrc/sparse.hip topk_* kernels (client side, compress.py) / sparse_aggregate_kernel
@@ -614,21 +601,10 @@ def FedSparse(global_state, updates, weights: Sequence[float], server_opt=None):
     ``num_batches_tracked`` arrive uncompressed and are averaged exactly as ``FedPavg`` averages them.  An element a client sent as
     non-finite is NaN in the result, as it would be with fp32 uploads.  Only a GPU ``FlatStateDict`` is accepted as ``global_state``."""
     from .compress import SparseDelta
-    if not isinstance(global_state, FlatStateDict) or global_state.flat is None:
-        raise RuntimeError("fedfr_amd.FedSparse: the global state must be a FlatStateDict (client.flat_state_dict)")
-    if not updates or not all(isinstance(u, SparseDelta) for u in updates):
-        raise RuntimeError("fedfr_amd.FedSparse: the client updates must be SparseDeltas (Client.get_sparse_update)")
-    if len(weights) != len(updates):
-        raise RuntimeError("fedfr_amd.FedSparse: %d weights for %d client updates" % (len(weights), len(updates)))
-    if isinstance(server_opt, RobustAggregator):
-        raise ValueError("FedSparse: a robust rule (%s) needs whole client states, not top-k uploads" % server_opt.kind)
-    if server_opt is not None and server_opt.clip_norm > 0:
-        raise ValueError("FedSparse: clip_norm > 0 needs per-client norms of the deltas, which top-k uploads do not provide; use FedOpt on "
-                         "uncompressed states")
-    tot = sum(weights)
-    ws = [w / tot for w in weights]
-    x = global_state.flat[0]
-    _check_states(x, [], "FedSparse")
+    x, ws = _upload_round_head("FedSparse", global_state, updates, lambda u: isinstance(u, SparseDelta), "updates",
+                               "SparseDeltas (Client.get_sparse_update)", weights, server_opt, "not top-k uploads",
+                               "clip_norm > 0 needs per-client norms of the deltas, which top-k uploads do not provide; use FedOpt on uncompressed "
+                               "states")
     n = x.numel()
     for u in updates:
         if u.n != n:
@@ -643,21 +619,16 @@ def FedSparse(global_state, updates, weights: Sequence[float], server_opt=None):
     for c0 in range(0, len(updates), 8):
         grp = updates[c0:c0 + 8]
         last = c0 + 8 >= len(updates)
-        wv = (_C.f32 * len(grp))(*[float(np.float32(w)) for w in ws[c0:c0 + 8]])
         keeps = (ctypes.c_size_t * len(grp))(*[u.keep for u in grp])
         if n:
             _C.call("fedfr_sparse_aggregate", P.data_ptr(), x.data_ptr() if last and server_opt is None else None, _C.ptr_array([u.idx for u in grp]),
-                    _C.ptr_array([u.val for u in grp]), keeps, wv, len(grp), n, 1 if c0 > 0 else 0, _C.stream())
-    if server_opt is not None:
-        server_opt.apply_delta(P, x, P)
-    stats = _average_stats([_StatsOnly(u.stats, u.counters) for u in updates], ws)
-    return FlatStateDict.from_flat((P, *stats), global_state.table, global_state.layers)
+                    _C.ptr_array([u.val for u in grp]), keeps, _f32_vector(ws[c0:c0 + 8]), len(grp), n, 1 if c0 > 0 else 0, _C.stream())
+    return _upload_round_tail(global_state, P, x, updates, ws, server_opt)
 
 
 def FedAvg_on_FC(pretrain_fc, models, weights, p):
     """reference server.py:36-46."""
-    tot = sum(weights)
-    ws = [w / tot for w in weights]
+    ws = _normalised(weights)
     m0 = models[0].contiguous()
     if not m0.is_cuda:
         raise RuntimeError("fedfr_amd.FedAvg_on_FC: tensors must be on the GPU")
@@ -854,64 +825,87 @@ class Server(object):
 
     @_C.on_device(lambda self: self.device)
     def train(self):
-        from .config import config as cfg
-        aggr_alg = getattr(self.args, "aggr_alg", "FedAvg")
+        """One round (reference server.py:265-338) in four stages: the settings and everything they refuse, local training, the clients'
+        uploads, the aggregation; then the new global state is installed.  Returns the clients' mean training loss."""
+        s = self._round_settings()
+        order = self._train_clients(s)
+        up = self._collect_uploads(s, order)
+        if s.return_all:                                                                         # server.py:316-327
+            # Reference quirk kept (SURVEY App. D): the averaged public centres are assigned to `self.pretrain_fc` — a misspelling of
+            # `self.pretrained_fc` (server.py:325 vs :121-124, :295) — so the clients of the NEXT round still receive the initial
+            # centres.  `args.feedback_public_fc = True` (a build extension, off by default) feeds the average back.
+            self.pretrain_fc = FedAvg_on_FC(self.pretrained_fc, up.models_fc, up.data_sizes, p=1.0)
+            if getattr(self.args, "feedback_public_fc", False):
+                self.pretrained_fc = self.pretrain_fc
+        self.federated_model.load_state_dict(self._aggregate(s, order, up))
+        # the round / epoch counters belong to the driver, as in the reference (train.py:87-88): call step_round() after train()
+        return self.avg_loss
+
+    def _round_settings(self):
+        """Stage 1: ``self.args`` read once, and every combination of settings that cannot be served refused, BEFORE a round of client
+        training is spent on it (no client is touched here).  Builds ``self.robust_agg`` and the distributed-DP mechanism; returns the
+        resolved values as one record (what is off is 0 / False / None)."""
+        a = self.args
+        aggr_alg = getattr(a, "aggr_alg", "FedAvg")
+        dp_sigma = float(getattr(a, "dp_noise_multiplier", 0) or 0)          # client-level differential privacy (a build extension): absent or 0 = off
+        clip_norm = float(getattr(a, "clip_norm", 0.0) or 0.0)
+        ddp_on = bool(getattr(a, "distributed_dp", False))                   # the noise added by the CLIENTS under secure aggregation: absent or False = off
+        compress_bits = getattr(a, "compress_bits", 0) or 0                  # compressed uploads (a build extension): absent or 0 = off
+        topk_ratio = getattr(a, "topk_ratio", 0) or 0                        # top-k uploads (a build extension): absent or 0 = off
+        secagg_on = bool(getattr(a, "secure_aggregation", False))            # secure aggregation (a build extension): absent or False = off
+        return_all = bool(getattr(a, "return_all", False))
+        dp_delta = ddp_mech = secagg_frac_bits = secagg_threshold = None     # (resolved below where their feature is on)
+        secagg_drop = []
         if aggr_alg not in ("FedAvg", "FedProx") and aggr_alg not in AGGR_ALG_KINDS and aggr_alg not in ROBUST_ALG_KINDS:      # before a round of client training is spent on it
             raise ValueError("Server.train: unknown aggr_alg %r (FedAvg, FedProx, %s, %s)"
                              % (aggr_alg, ", ".join(AGGR_ALG_KINDS), ", ".join(sorted(ROBUST_ALG_KINDS))))
-        dp_sigma = float(getattr(self.args, "dp_noise_multiplier", 0) or 0)      # client-level differential privacy (a build extension): absent or 0 = off
-        ddp_on = bool(getattr(self.args, "distributed_dp", False))           # the noise added by the CLIENTS under secure aggregation: absent or False = off
         if ddp_on:
-            if not getattr(self.args, "secure_aggregation", False):
+            if not secagg_on:
                 raise ValueError("Server.train: distributed_dp needs secure_aggregation: the clients' noise shares protect only a sum that "
                                  "nobody sees in parts")
             if not dp_sigma:
-                raise ValueError("Server.train: distributed_dp needs dp_noise_multiplier > 0 (got %r)" % (getattr(self.args, "dp_noise_multiplier", 0),))
-            if not bool(getattr(self.args, "dp_uniform_weights", True)):
+                raise ValueError("Server.train: distributed_dp needs dp_noise_multiplier > 0 (got %r)" % (getattr(a, "dp_noise_multiplier", 0),))
+            if not bool(getattr(a, "dp_uniform_weights", True)):
                 raise ValueError("Server.train: distributed_dp needs dp_uniform_weights on: every client encodes at weight 1, the weight the "
                                  "sensitivity bound is stated for")
         if dp_sigma:                                                         # what cannot be served: before anybody trains
-            clip_norm = float(getattr(self.args, "clip_norm", 0.0) or 0.0)
             if not (dp_sigma > 0 and np.isfinite(dp_sigma)):
-                raise ValueError("Server.train: dp_noise_multiplier must be a finite number >= 0 (got %r)" % (self.args.dp_noise_multiplier,))
+                raise ValueError("Server.train: dp_noise_multiplier must be a finite number >= 0 (got %r)" % (a.dp_noise_multiplier,))
             if not clip_norm > 0:
                 raise ValueError("Server.train: dp_noise_multiplier=%r needs clip_norm > 0: the clip is the sensitivity bound of the mechanism"
                                  % (dp_sigma,))
             if aggr_alg in ROBUST_ALG_KINDS:
                 raise ValueError("Server.train: dp_noise_multiplier=%r cannot be combined with aggr_alg=%r: a robust rule provides no per-client "
                                  "norms to clip" % (dp_sigma, aggr_alg))
-            if getattr(self.args, "compress_bits", 0):
+            if compress_bits:
                 raise ValueError("Server.train: dp_noise_multiplier=%r cannot be combined with compress_bits=%d: the clip needs per-client norms "
-                                 "of the dequantised deltas, which are not provided" % (dp_sigma, self.args.compress_bits))
-            if getattr(self.args, "topk_ratio", 0):
+                                 "of the dequantised deltas, which are not provided" % (dp_sigma, compress_bits))
+            if topk_ratio:
                 raise ValueError("Server.train: dp_noise_multiplier=%r cannot be combined with topk_ratio=%r: the clip needs per-client norms of "
-                                 "the deltas, which are not provided" % (dp_sigma, self.args.topk_ratio))
-            if getattr(self.args, "return_all", False):
+                                 "the deltas, which are not provided" % (dp_sigma, topk_ratio))
+            if return_all:
                 raise ValueError("Server.train: dp_noise_multiplier=%r cannot be combined with return_all: the averaged public class centres "
                                  "would be released un-noised" % (dp_sigma,))
             if not ddp_on and self.dp_accountant is not None and self.dp_accountant.sigma != dp_sigma:
                 raise ValueError("Server.train: dp_noise_multiplier=%r after rounds accounted at %r: the accountant composes rounds of one noise "
                                  "multiplier (set server.dp_accountant yourself to continue)" % (dp_sigma, self.dp_accountant.sigma))
-            dp_delta = float(getattr(self.args, "dp_delta", 1e-5))
+            dp_delta = float(getattr(a, "dp_delta", 1e-5))
             if not 0.0 < dp_delta < 1.0:
                 raise ValueError("Server.train: dp_delta must be in (0, 1) (got %r)" % (dp_delta,))
         if aggr_alg in ROBUST_ALG_KINDS:                   # a client count the rule cannot serve: also before anybody trains
             if getattr(self, "robust_agg", None) is None or self.robust_agg.kind != aggr_alg:      # one aggregator per server (it keeps the distance workspace)
-                a = self.args
                 self.robust_agg = RobustAggregator(aggr_alg, trim_ratio=getattr(a, "trim_ratio", 0.1), num_byzantine=getattr(a, "num_byzantine", 1),
                                                    multi_m=getattr(a, "multi_krum_m", None))
             self.robust_agg.validate(len(self.current_client_list))
-        compress_bits = getattr(self.args, "compress_bits", 0) or 0          # compressed uploads (a build extension): absent or 0 = off
         if compress_bits:                                                    # what cannot be served: also before anybody trains
             from .compress import check_bits
             check_bits(compress_bits, "Server.train")
             if aggr_alg in ROBUST_ALG_KINDS:
                 raise ValueError("Server.train: compress_bits=%d cannot be combined with aggr_alg=%r: a robust rule needs whole client states"
                                  % (compress_bits, aggr_alg))
-            if float(getattr(self.args, "clip_norm", 0.0) or 0.0) > 0:
+            if clip_norm > 0:
                 raise ValueError("Server.train: compress_bits=%d cannot be combined with clip_norm=%r: the clip needs per-client norms of the "
-                                 "dequantised deltas, which are not provided" % (compress_bits, self.args.clip_norm))
-        topk_ratio = getattr(self.args, "topk_ratio", 0) or 0                # top-k uploads (a build extension): absent or 0 = off
+                                 "dequantised deltas, which are not provided" % (compress_bits, a.clip_norm))
         if topk_ratio:                                                       # the same: before anybody trains
             from .compress import keep_count
             try:
@@ -924,10 +918,9 @@ class Server(object):
             if aggr_alg in ROBUST_ALG_KINDS:
                 raise ValueError("Server.train: topk_ratio=%r cannot be combined with aggr_alg=%r: a robust rule needs whole client states"
                                  % (topk_ratio, aggr_alg))
-            if float(getattr(self.args, "clip_norm", 0.0) or 0.0) > 0:
+            if clip_norm > 0:
                 raise ValueError("Server.train: topk_ratio=%r cannot be combined with clip_norm=%r: the clip needs per-client norms of the "
-                                 "deltas, which are not provided" % (topk_ratio, self.args.clip_norm))
-        secagg_on = bool(getattr(self.args, "secure_aggregation", False))      # secure aggregation (a build extension): absent or False = off
+                                 "deltas, which are not provided" % (topk_ratio, a.clip_norm))
         if secagg_on:                                                        # the same: before anybody trains
             from .secagg import MAX_PARTICIPANTS, check_frac_bits
             K = len(self.current_client_list)
@@ -943,22 +936,22 @@ class Server(object):
             if dp_sigma and not ddp_on:
                 raise ValueError("Server.train: secure_aggregation cannot be combined with dp_noise_multiplier=%r: distributed differential "
                                  "privacy is not provided" % (dp_sigma,))
-            if float(getattr(self.args, "clip_norm", 0.0) or 0.0) > 0 and not ddp_on:
+            if clip_norm > 0 and not ddp_on:
                 raise ValueError("Server.train: secure_aggregation cannot be combined with clip_norm=%r: the clip needs per-client norms of the "
-                                 "updates, which masked uploads hide by design" % (self.args.clip_norm,))
-            if getattr(self.args, "return_all", False):
+                                 "updates, which masked uploads hide by design" % (a.clip_norm,))
+            if return_all:
                 raise ValueError("Server.train: secure_aggregation cannot be combined with return_all: the public class centres would travel "
                                  "in the clear")
             if not 2 <= K <= MAX_PARTICIPANTS:
                 raise ValueError("Server.train: secure_aggregation needs 2 to %d participants (got %d)" % (MAX_PARTICIPANTS, K))
-            secagg_frac_bits = check_frac_bits(getattr(self.args, "secagg_frac_bits", 24), "Server.train")
-            secagg_threshold = getattr(self.args, "secagg_threshold", None)
+            secagg_frac_bits = check_frac_bits(getattr(a, "secagg_frac_bits", 24), "Server.train")
+            secagg_threshold = getattr(a, "secagg_threshold", None)
             if secagg_threshold is None:
                 secagg_threshold = K // 2 + 1
             if isinstance(secagg_threshold, bool) or not isinstance(secagg_threshold, (int, np.integer)) or not 2 <= secagg_threshold <= K:
                 raise ValueError("Server.train: secagg_threshold must be an integer in 2 ... %d, the number of participants (got %r)"
                                  % (K, secagg_threshold))
-            secagg_drop = sorted(set(int(d) for d in (getattr(self.args, "secagg_drop", None) or ())))
+            secagg_drop = sorted(set(int(d) for d in (getattr(a, "secagg_drop", None) or ())))
             if any(d not in self.current_client_list for d in secagg_drop):
                 raise ValueError("Server.train: secagg_drop=%r names clients that do not take part in this round (%s)"
                                  % (secagg_drop, list(self.current_client_list)))
@@ -973,16 +966,23 @@ class Server(object):
                     raise ValueError("Server.train: distributed_dp at an effective noise multiplier of %r after rounds accounted at %r (q = %g): "
                                      "the accountant composes rounds of one mechanism (set server.dp_accountant yourself to continue)"
                                      % (ddp_mech.z_eff, self.dp_accountant.sigma, self.dp_accountant.q))
-        models, models_fc, losses_, data_sizes = [], [], [], []
-        public = bool(getattr(self.args, "add_pretrained_data", False))
-        return_all = bool(getattr(self.args, "return_all", False))
-        mine = public and bool(getattr(self.args, "choose_hard_negative", True)) and self.public_test_loader is not None \
+        return SimpleNamespace(aggr_alg=aggr_alg, dp_sigma=dp_sigma, clip_norm=clip_norm, dp_delta=dp_delta, ddp_on=ddp_on, ddp_mech=ddp_mech,
+                               compress_bits=compress_bits, topk_ratio=topk_ratio, feedback=bool(getattr(a, "error_feedback", True)),
+                               secagg_on=secagg_on, secagg_frac_bits=secagg_frac_bits, secagg_threshold=secagg_threshold, secagg_drop=secagg_drop,
+                               public=bool(getattr(a, "add_pretrained_data", False)), return_all=return_all)
+
+    def _train_clients(self, s) -> List[int]:
+        """Stage 2: every client of ``current_client_list`` receives the global model and trains, one after another or
+        ``args.parallel_clients`` at a time; returns the clients in the order they are aggregated in."""
+        from .config import config as cfg
+        mine = s.public and bool(getattr(self.args, "choose_hard_negative", True)) and self.public_test_loader is not None \
             and self.pretrained_label is not None
         if mine:                                                                                 # server.py:272-275
             self.pretrained_feats = self.Generate_pretrain_feats()
         if getattr(self.args, "adaptive_local_epoch", False) and self.global_round != 0:        # server.py:277-280
             self.local_epoch = max(4, self.local_epoch - 2)
             cfg.train_decay = max(1, int(3 / 4 * self.local_epoch))
+
         def run_client(i, slot=0):
             c = self.clients[i]
             c.slot = slot
@@ -991,7 +991,7 @@ class Server(object):
             veri = {}                                                           # server.py:291-298: candidates train with the local test
             if self.callback_local_veri is not None and c.cid in self.local_candidates:
                 veri = {"callback_verification": self.callback_local_veri}
-            if public:
+            if s.public:
                 if self.pretrained_fc is None:
                     raise RuntimeError("Server.train: add_pretrained_data needs server.pretrained_fc ([n_public, 512] class centres)")
                 c.train_with_public_data(self.global_epoch, public_train_loader=self.public_train_loader,
@@ -1038,96 +1038,97 @@ class Server(object):
                     t.join()
                 if errs:
                     raise errs[0]
-        if compress_bits or topk_ratio or secagg_on:
-            global_state = flat_state_dict(self.federated_model)              # what the round started from: the clients trained on copies
-            feedback = bool(getattr(self.args, "error_feedback", True))
-        if secagg_on:                                                         # rounds 0 to 2 of the protocol: keys, shares, public weights
+        return order
+
+    def _collect_uploads(self, s, order):
+        """Stage 3: what every client of ``order`` sends: its state, or its compressed / top-k / masked update against ``global_state``
+        (after the key and share rounds of secure aggregation), its data size and, under ``return_all``, the public class centres.  Sets
+        ``self.avg_loss``.  Returns one record; ``global_state``, ``sa_server`` and ``public_w`` are None where the round has no use for them."""
+        up = SimpleNamespace(models=[], models_fc=[], data_sizes=[], global_state=None, sa_server=None, public_w=None)
+        losses_ = []
+        if s.compress_bits or s.topk_ratio or s.secagg_on:
+            up.global_state = flat_state_dict(self.federated_model)           # what the round started from: the clients trained on copies
+        if s.secagg_on:                                                       # rounds 0 to 2 of the protocol: keys, shares, public weights
             from .secagg import SecAggServer
-            sa_server = SecAggServer(order, secagg_threshold, self.global_round)
+            up.sa_server = SecAggServer(order, s.secagg_threshold, self.global_round)
             for i in order:
-                sa_server.register(i, self.clients[i].secagg_client(i, secagg_frac_bits, self.secagg_rng).begin_round(self.global_round))
+                up.sa_server.register(i, self.clients[i].secagg_client(i, s.secagg_frac_bits, self.secagg_rng).begin_round(self.global_round))
             for i in order:
-                sa_server.deliver_shares(i, self.clients[i].secagg.make_shares(order, secagg_threshold))
-            sizes_all = [self.clients[i].get_data_size() for i in order]
-            public_w = [sz / float(sum(sizes_all)) for sz in sizes_all]        # w_i = n_i / Σn: public, the factor each client encodes with
-            if ddp_on:
-                public_w = [1.0] * len(order)                                 # distributed DP: every client at weight 1, the mean is taken by the rescale
+                up.sa_server.deliver_shares(i, self.clients[i].secagg.make_shares(order, s.secagg_threshold))
+            up.public_w = _normalised([self.clients[i].get_data_size() for i in order])      # w_i = n_i / Σn: public, the factor each client encodes with
+            if s.ddp_on:
+                up.public_w = [1.0] * len(order)                              # distributed DP: every client at weight 1, the mean is taken by the rescale
         for pos, i in enumerate(order):
             losses_.append(self.clients[i].get_train_loss())
-            if secagg_on:                                                     # "client sends its masked fixed-point update"
-                models.append(self.clients[i].get_masked_update(global_state, public_w[pos], order, sa_server.public_keys, self.global_round,
-                                                                **({"dp": ddp_mech} if ddp_on else {})))
-            elif compress_bits:                                                 # "client sends Q(x_i - x + e_i)" and keeps e_i
-                models.append(self.clients[i].get_compressed_update(global_state, compress_bits, feedback))
-            elif topk_ratio:                                                  # "client sends the largest entries of x_i - x + e_i" and keeps the rest
-                models.append(self.clients[i].get_sparse_update(global_state, topk_ratio, feedback))
+            if s.secagg_on:                                                   # "client sends its masked fixed-point update"
+                up.models.append(self.clients[i].get_masked_update(up.global_state, up.public_w[pos], order, up.sa_server.public_keys, self.global_round,
+                                                                   **({"dp": s.ddp_mech} if s.ddp_on else {})))
+            elif s.compress_bits:                                             # "client sends Q(x_i - x + e_i)" and keeps e_i
+                up.models.append(self.clients[i].get_compressed_update(up.global_state, s.compress_bits, s.feedback))
+            elif s.topk_ratio:                                                # "client sends the largest entries of x_i - x + e_i" and keeps the rest
+                up.models.append(self.clients[i].get_sparse_update(up.global_state, s.topk_ratio, s.feedback))
             else:
-                models.append(self.clients[i].get_model())
-            if return_all:
-                models_fc.append(self.clients[i].get_global_fc().to(self.device))
+                up.models.append(self.clients[i].get_model())
+            if s.return_all:
+                up.models_fc.append(self.clients[i].get_global_fc().to(self.device))
                 self.clients[i].fc_module.remove_pretrain()
-            data_sizes.append(self.clients[i].get_data_size())
+            up.data_sizes.append(self.clients[i].get_data_size())
         self.avg_loss = sum(losses_) / len(losses_)
-        if return_all:                                                                           # server.py:316-327
-            # Reference quirk kept: the averaged public centres are assigned to `self.pretrain_fc` — a misspelling of
-            # `self.pretrained_fc` (server.py:325 vs :121-124, :295) — so the clients of the NEXT round still receive the initial
-            # centres.  `args.feedback_public_fc = True` (a build extension, off by default) feeds the average back.
-            self.pretrain_fc = FedAvg_on_FC(self.pretrained_fc, models_fc, data_sizes, p=1.0)
-            if getattr(self.args, "feedback_public_fc", False):
-                self.pretrained_fc = self.pretrain_fc
-        if aggr_alg in AGGR_ALG_KINDS and getattr(self, "server_opt", None) is None:
+        return up
+
+    def _report_uploads(self, label, uploads, tail, senders, counters, warning):
+        """The log lines of a round from uploads: "``label``: N bytes from K clients, ... of the D bytes of fp32 states``tail``" over all
+        ``uploads``; then ``counters`` (one small device tensor per aggregated upload, of the clients ``senders``) in ONE copy, the round's one
+        read of them, and ``warning`` % (client, the counters it names) where one of those is not 0.  Returns the counters as lists."""
+        sent, dense = sum(u.nbytes for u in uploads), sum(u.dense_nbytes for u in uploads)
+        self.logger.info('%s: %d bytes from %d clients, %.4f of the %d bytes of fp32 states%s' % (label, sent, len(uploads), sent / dense, dense, tail))
+        rows = torch.stack([c.reshape(-1) for c in counters]).cpu().tolist()
+        shown = warning.count('%d')
+        for i, row in zip(senders, rows):
+            if any(v > 0 for v in row[:shown]):
+                self.logger.warning(warning % (getattr(self.clients[i], "cid", i), *row[:shown]))
+        return rows
+
+    def _aggregate(self, s, order, up):
+        """Stage 4: the round's new global state from what ``_collect_uploads`` gathered, by the path the settings select; logs what the
+        uploads cost and carried, and accounts the privacy spent."""
+        if s.aggr_alg in AGGR_ALG_KINDS and getattr(self, "server_opt", None) is None:
             # server optimiser (a build extension: the reference's flag runs FedAvg only): one optimiser per server, moments kept across rounds
             a = self.args
-            self.server_opt = ServerOptimizer(aggr_alg, lr=getattr(a, "server_lr", 1.0), beta1=getattr(a, "server_momentum", 0.9),
+            self.server_opt = ServerOptimizer(s.aggr_alg, lr=getattr(a, "server_lr", 1.0), beta1=getattr(a, "server_momentum", 0.9),
                                               beta2=getattr(a, "server_beta2", 0.99), tau=getattr(a, "server_tau", 1e-3),
-                                              clip_norm=0.0 if ddp_on else getattr(a, "clip_norm", 0.0))      # (distributed DP: the clients clip)
-        if compress_bits:
-            aggr_state_dict = FedCompressed(global_state, models, data_sizes, self.server_opt if aggr_alg in AGGR_ALG_KINDS else None)
-            sent, dense = sum(u.nbytes for u in models), sum(u.dense_nbytes for u in models)
-            self.logger.info('Compressed uploads (%d bits%s): %d bytes from %d clients, %.4f of the %d bytes of fp32 states'
-                             % (compress_bits, ", error feedback" if feedback else "", sent, len(models), sent / dense, dense))
-            bad = torch.cat([u.nonfinite_blocks for u in models]).cpu().tolist()      # one small copy: the round's one read of the counters
-            for j, nb in enumerate(bad):
-                if nb > 0:
-                    self.logger.warning('Client %s sent %d non-finite blocks (NaN in the aggregate there)'
-                                        % (getattr(self.clients[order[j]], "cid", order[j]), nb))
-        elif topk_ratio:
-            aggr_state_dict = FedSparse(global_state, models, data_sizes, self.server_opt if aggr_alg in AGGR_ALG_KINDS else None)
-            sent, dense = sum(u.nbytes for u in models), sum(u.dense_nbytes for u in models)
-            self.logger.info('Top-k uploads (ratio %g%s): %d bytes from %d clients, %.4f of the %d bytes of fp32 states'
-                             % (topk_ratio, ", error feedback" if feedback else "", sent, len(models), sent / dense, dense))
-            bad = torch.cat([u.nonfinite for u in models]).cpu().tolist()     # one small copy: the round's one read of the counters
-            for j, nb in enumerate(bad):
-                if nb > 0:
-                    self.logger.warning('Client %s sent %d non-finite elements (NaN in the aggregate there)'
-                                        % (getattr(self.clients[order[j]], "cid", order[j]), nb))
-        elif secagg_on:
-            keep = [pos for pos, i in enumerate(order) if i not in secagg_drop]      # (a dropped client's upload is discarded after masking)
+                                              clip_norm=0.0 if s.ddp_on else getattr(a, "clip_norm", 0.0))      # (distributed DP: the clients clip)
+        opt = self.server_opt if s.aggr_alg in AGGR_ALG_KINDS else None
+        models, data_sizes, aggr_alg = up.models, up.data_sizes, s.aggr_alg
+        if s.compress_bits:
+            aggr_state_dict = FedCompressed(up.global_state, models, data_sizes, opt)
+            self._report_uploads('Compressed uploads (%d bits%s)' % (s.compress_bits, ", error feedback" if s.feedback else ""), models, '', order,
+                                 [u.nonfinite_blocks for u in models], 'Client %s sent %d non-finite blocks (NaN in the aggregate there)')
+        elif s.topk_ratio:
+            aggr_state_dict = FedSparse(up.global_state, models, data_sizes, opt)
+            self._report_uploads('Top-k uploads (ratio %g%s)' % (s.topk_ratio, ", error feedback" if s.feedback else ""), models, '', order,
+                                 [u.nonfinite for u in models], 'Client %s sent %d non-finite elements (NaN in the aggregate there)')
+        elif s.secagg_on:
             from .secagg import survivor_rescale
-            streams = sa_server.recovery_streams([order[pos] for pos in keep])
-            if ddp_on:
-                aggr_state_dict = FedSecAggDP(global_state, [models[pos] for pos in keep], streams, ddp_mech,
-                                              self.server_opt if aggr_alg in AGGR_ALG_KINDS else None)
+            keep = [pos for pos, i in enumerate(order) if i not in s.secagg_drop]      # (a dropped client's upload is discarded after masking)
+            survivors, kept = [order[pos] for pos in keep], [models[pos] for pos in keep]
+            streams = up.sa_server.recovery_streams(survivors)
+            if s.ddp_on:
+                aggr_state_dict = FedSecAggDP(up.global_state, kept, streams, s.ddp_mech, opt)
             else:
-                aggr_state_dict = FedSecAgg(global_state, [models[pos] for pos in keep], [data_sizes[pos] for pos in keep], streams,
-                                            survivor_rescale(public_w, keep), self.server_opt if aggr_alg in AGGR_ALG_KINDS else None)
-            sent, dense = sum(u.nbytes for u in models), sum(u.dense_nbytes for u in models)
-            self.logger.info('Masked uploads (%d fraction bits, threshold %d): %d bytes from %d clients, %.4f of the %d bytes of fp32 states; '
-                             '%d dropped, %d recovery streams' % (secagg_frac_bits, secagg_threshold, sent, len(models), sent / dense, dense,
-                                                                 len(models) - len(keep), len(streams)))
-            bad = torch.stack([models[pos].code_counters for pos in keep]).cpu().tolist()      # one small copy: the round's one read of the counters
-            for pos, (nsat, nbad, *_) in zip(keep, bad):
-                if nsat > 0 or nbad > 0:
-                    self.logger.warning('Client %s sent %d saturated and %d non-finite elements (clamped to the code range / sent as 0)'
-                                        % (getattr(self.clients[order[pos]], "cid", order[pos]), nsat, nbad))
-            if ddp_on:
-                self._account_distributed_dp(ddp_mech, [order[pos] for pos in keep], [row[2] for row in bad], [models[pos] for pos in keep], dp_delta)
-        elif dp_sigma:
-            aggr_state_dict = self._aggregate_dp(models, data_sizes, aggr_alg, dp_sigma, clip_norm, dp_delta)
+                aggr_state_dict = FedSecAgg(up.global_state, kept, [data_sizes[pos] for pos in keep], streams, survivor_rescale(up.public_w, keep), opt)
+            bad = self._report_uploads('Masked uploads (%d fraction bits, threshold %d)' % (s.secagg_frac_bits, s.secagg_threshold), models,
+                                       '; %d dropped, %d recovery streams' % (len(models) - len(keep), len(streams)), survivors,
+                                       [u.code_counters for u in kept],
+                                       'Client %s sent %d saturated and %d non-finite elements (clamped to the code range / sent as 0)')
+            if s.ddp_on:
+                self._account_distributed_dp(s.ddp_mech, survivors, [row[2] for row in bad], kept, s.dp_delta)
+        elif s.dp_sigma:
+            aggr_state_dict = self._aggregate_dp(models, data_sizes, aggr_alg, s.dp_sigma, s.clip_norm, s.dp_delta)
         elif aggr_alg in ("FedAvg", "FedProx"):
             aggr_state_dict = FedPavg(models, data_sizes)
         elif aggr_alg in AGGR_ALG_KINDS:
-            aggr_state_dict = FedOpt(flat_state_dict(self.federated_model), models, data_sizes, self.server_opt)
+            aggr_state_dict = FedOpt(flat_state_dict(self.federated_model), models, data_sizes, opt)
         else:
             # ROBUST_ALG_KINDS (nothing else passed the check above).  Robust aggregation (a build extension): trimmed mean / median per
             # coordinate, or Krum's selection (one host synchronisation)
@@ -1137,9 +1138,7 @@ class Server(object):
                 cid = [getattr(self.clients[i], "cid", i) for i in order]
                 self.logger.info('%s kept clients %s, rejected clients %s' % (aggr_alg, [cid[j] for j in sorted(kept)],
                                                                                [cid[j] for j in range(len(order)) if j not in kept]))
-        self.federated_model.load_state_dict(aggr_state_dict)
-        # the round / epoch counters belong to the driver, as in the reference (train.py:87-88): call step_round() after train()
-        return self.avg_loss
+        return aggr_state_dict
 
     def _account_distributed_dp(self, mech, survivors, exhausted, uploads, delta):
         """what ``distributed_dp`` checks and accounts after the round's aggregation (the counters have been read): a sampler that ran out

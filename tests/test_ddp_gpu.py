@@ -148,7 +148,8 @@ def test_secagg_mask_dp_without_counters_and_with_another_noise_seed(n=4100):
 
 
 # ---- the protocol on FlatStateDicts --------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("K, dropped, opt", [(4, (), None), (4, (2,), None), (11, (), None), (11, (0, 4, 9, 10), "ADAM")])
+@pytest.mark.parametrize("K, dropped, opt", [(4, (), None), (4, (2,), None), (11, (), None), (11, (0, 4, 9, 10), "ADAM"),
+                                            (11, (0, 4, 9, 10), None)])      # (the last row: a last pass of recovery streams only adds x)
 def test_protocol_reproduces_the_restatement_and_the_masks_leave_no_trace(K, dropped, opt):
     """SecAggClient.mask_dp -> SecAggServer.recovery_streams -> FedSecAggDP on the flat world of test_secagg_gpu.py: every upload is the
     restatement's words; the aggregate is x + float(sum of codes + sum of noise) 2^-f fp32(1 / survivors) bit for bit (past 8 uploads and

@@ -307,11 +307,13 @@ def _flat_world(K, n=4100 + 3, nb=40, nc=5):
     return glob, models, sizes
 
 
-@pytest.mark.parametrize("K, dropped, opt", [(3, (), None), (3, (1,), None), (11, (), None), (11, (0, 4, 9, 10), "ADAM"), (3, (), "AVGM")])
+@pytest.mark.parametrize("K, dropped, opt", [(3, (), None), (3, (1,), None), (11, (), None), (11, (0, 4, 9, 10), "ADAM"), (3, (), "AVGM"),
+                                            (11, (0, 4, 9, 10), None)])      # (appended last: the earlier rows keep their ids)
 def test_fedsecagg_reproduces_the_restatement(K, dropped, opt):
     """SecAggClient.mask -> SecAggServer.recovery_streams -> FedSecAgg on FlatStateDicts: the parameters are the restatement's bits (the
     plain codes summed: the masks cancel), also past 8 uploads and 32 recovery streams (chained passes) and through a server optimiser;
-    statistics and counters are FedPavg's over the survivors"""
+    statistics and counters are FedPavg's over the survivors.  11 clients of whom 4 drop leave 7 uploads and more than 32 recovery streams:
+    the LAST pass then carries streams only, and without an optimiser it is that pass that adds x"""
     glob, models, sizes = _flat_world(K)
     x, n = N(glob.flat[0]), glob.flat[0].numel()
     rnd, t = 9, K // 2 + 1
