@@ -404,8 +404,7 @@ int fedfr_conv2d_fwd_moments(const uint16_t* x, const uint16_t* w, uint16_t* y, 
   FEDFR_REQUIRE(x && w && y && other && partials && rows, "conv2d_fwd_moments: null argument");
   GemmNT p = conv_fwd_problem(batch, hin, cin, cout, 3, 1);
   p.A = BF(x); p.B = BF(w); p.Cb = BFM(y);
-  p.bx = BF(other); p.bmean = partials; p.brstd = partials;   // (any readable fp32 array of >= cout elements: read, never used in this mode)
-  p.bpart = partials; p.bmom = 1;
+  conv_set_moments(p, BF(other), partials);
   *rows = gemm_nt_plan(p, 1).part_rows;
   return gemm_nt_launch(p, 1, ST(stream));
 }
@@ -440,11 +439,11 @@ int fedfr_conv2d_dgrad_bnbwd(const uint16_t* dy, const uint16_t* wd, uint16_t* d
   FEDFR_REQUIRE(dy && wd && dx && bn_x && mean && rstd && partials && fused_rows && ksize == 3, "conv2d_dgrad_bnbwd: bad args");
   GemmNT p = conv_dgrad_problem(batch, hin, cin, cout, 3, stride);
   p.A = BF(dy); p.B = BF(wd); p.Cb = BFM(dx);
-  p.bx = BF(bn_x); p.bmean = mean; p.brstd = rstd; p.bgamma = gamma; p.bbeta = beta; p.balpha = alpha; p.bpart = partials;
+  conv_set_bnbwd(p, BF(bn_x), mean, rstd, gamma, beta, alpha, partials);
   *fused_rows = gemm_nt_plan(p, 1).part_rows;
   return gemm_nt_launch(p, 1, ST(stream));
 }
-// the eval-mode output epilogue of the LDS-DMA conv kernels, one launch (the GemmNT of net.hip: conv_fwd_ep)
+// the eval-mode output epilogue of the LDS-DMA conv kernels, one launch
 int fedfr_conv2d_fwd_epilogue(const uint16_t* x, const uint16_t* w, uint16_t* y, const float* scale, const float* shift, const float* alpha,
                               const uint16_t* add, uint16_t* y2, const float* scale2, const float* shift2, int batch, int hin, int cin,
                               int cout, void* stream) {
@@ -452,24 +451,21 @@ int fedfr_conv2d_fwd_epilogue(const uint16_t* x, const uint16_t* w, uint16_t* y,
   FEDFR_REQUIRE(x && w && y && scale && shift && (!y2 || (scale2 && shift2)), "conv2d_fwd_epilogue: null argument");
   GemmNT p = conv_fwd_problem(batch, hin, cin, cout, 3, 1);
   p.A = BF(x); p.B = BF(w); p.Cb = BFM(y);
-  p.esc = scale; p.esh = shift; p.ealpha = alpha; p.eadd = BF(add);
-  if (y2) { p.Cb2 = BFM(y2); p.esc2 = scale2; p.esh2 = shift2; }
+  conv_set_out_epilogue(p, scale, shift, alpha, BF(add), BFM(y2), scale2, shift2);
   if (!gemm_nt_plan(p, 1).out_epilogue) {
     fedfr_set_error("conv2d_fwd_epilogue: no kernel with the output epilogue serves batch=%d hin=%d cin=%d cout=%d", batch, hin, cin, cout);
     return FEDFR_ERR_UNSUPPORTED;
   }
   return gemm_nt_launch(p, 1, ST(stream));
 }
-// the PReLU-apply dgrad (GemmNT::bmom == 2), one launch (the GemmNT of net_sph.inc: dgrad_prelu)
+// the PReLU-apply dgrad (GemmNT::bmom == 2), one launch
 int fedfr_conv2d_dgrad_papply(const uint16_t* dy, const uint16_t* wd, uint16_t* dz, int batch, int hin, int cin, int cout, const uint16_t* act_x,
                               const float* bias, const float* alpha, float* partials, int* rows, void* stream) {
   FEDFR_TRY(conv_args_ok(batch, hin, cin, cout, 3, 1));
   FEDFR_REQUIRE(dy && wd && dz && act_x && alpha && partials && rows, "conv2d_dgrad_papply: null argument");
   GemmNT p = conv_dgrad_problem(batch, hin, cin, cout, 3, 1);
   p.A = BF(dy); p.B = BF(wd); p.Cb = BFM(dz);
-  p.bx = BF(act_x); p.bbeta = bias; p.balpha = alpha;
-  p.bmean = alpha; p.brstd = alpha;                     // (read, never used in this mode)
-  p.bpart = partials; p.bmom = 2;
+  conv_set_papply(p, BF(act_x), bias, alpha, partials);
   *rows = gemm_nt_plan(p, 1).part_rows;
   if (*rows == 0) {
     fedfr_set_error("conv2d_dgrad_papply: no kernel with the PReLU-apply epilogue serves batch=%d hin=%d cin=%d cout=%d", batch, hin, cin, cout);
@@ -489,8 +485,10 @@ int fedfr_conv2d_plan(int batch, int hin, int cin, int cout, int ksize, int stri
   static bf16_t h16s[1];
   p.A = p.B = p.Cb = h16s;
   if (want & 1) p.stats = f32s;
-  if (want & (2 | 4 | 8)) { p.bx = h16s; p.bmean = p.brstd = p.balpha = p.bpart = f32s; p.bmom = (want & 4) ? 1 : (want & 8) ? 2 : 0; }
-  if (want & 16) p.esc = p.esh = f32s;
+  if (want & 2) conv_set_bnbwd(p, h16s, f32s, f32s, nullptr, nullptr, f32s, f32s);
+  if (want & 4) conv_set_moments(p, h16s, f32s);
+  if (want & 8) conv_set_papply(p, h16s, nullptr, f32s, f32s);
+  if (want & 16) conv_set_out_epilogue(p, f32s, f32s, nullptr, nullptr, nullptr, nullptr, nullptr);
   const NtPlan pl = gemm_nt_plan(p, 1);
   *profile_slot = pl.profile_slot; *stat_rows = pl.stat_rows; *stat_rows_live = pl.stat_rows_live; *part_rows = pl.part_rows; *out_epilogue = pl.out_epilogue;
   return FEDFR_OK;
@@ -643,12 +641,9 @@ int fedfr_bn_bwd(const uint16_t* dy, const uint16_t* x, const float* mean, const
   BnBwd p{};
   p.dy = BF(dy); p.x = BF(x); p.mean = mean; p.rstd = rstd; p.gamma = gamma; p.beta = beta; p.alpha = alpha; p.M = M; p.C = C;
   p.partials = partials; p.coef = coef; p.add = BF(add); p.add_up = BF(add_up); p.H = H; p.W = H; p.dx = BFM(dx);
-  FEDFR_TRY(ew_bn_bwd_reduce(p, ST(stream)));
-  FEDFR_TRY(ew_bn_bwd_finalize(partials, ew_bn_bwd_grid(M, C), C, (double)M, gamma, mean, rstd, dgamma, dbeta, dalpha, coef, ST(stream)));
-  return ew_bn_bwd_apply(p, ST(stream));
+  return ew_bn_bwd_rowslab(p, 0, (double)M, dgamma, dbeta, dalpha, false, ST(stream));
 }
 int fedfr_bn_bwd_apply_rows(int M, int C) { return ew_bn_bwd_apply_grid(M, C); }
-// the row-slab branch of net.hip's bn_bwd, argument for argument
 int fedfr_bn_bwd_rowslab(const uint16_t* dy, const uint16_t* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
                          const float* alpha, const float* sc, const float* sh, int M, int C, double count, float* partials, int rows_in,
                          int coef_only, float* coef, float* dgamma, float* dbeta, float* dalpha, const uint16_t* add,
@@ -660,11 +655,7 @@ int fedfr_bn_bwd_rowslab(const uint16_t* dy, const uint16_t* x, const float* mea
   p.nx = BF(nx); p.nmean = nmean; p.nrstd = nrstd; p.npart = npart; p.nsc = nsc; p.nsh = nsh; p.nalpha = nalpha;
   p.dy = BF(dy); p.x = BF(x); p.mean = mean; p.rstd = rstd; p.gamma = gamma; p.beta = beta; p.alpha = alpha; p.sc = sc; p.sh = sh;
   p.M = M; p.C = C; p.partials = partials; p.coef = coef; p.add = BF(add); p.add_up = BF(add_up); p.H = H; p.W = H; p.dx = BFM(dx);
-  if (rows_in <= 0) FEDFR_TRY(ew_bn_bwd_reduce(p, ST(stream)));      // else: the producing pass already wrote the partials
-  FEDFR_TRY(ew_bn_bwd_finalize(partials, rows_in > 0 ? rows_in : ew_bn_bwd_grid(M, C), C, count, gamma, mean, rstd, dgamma, dbeta, dalpha, coef,
-                               ST(stream)));
-  if (coef_only) return FEDFR_OK;
-  return ew_bn_bwd_apply(p, ST(stream));
+  return ew_bn_bwd_rowslab(p, rows_in, count, dgamma, dbeta, dalpha, coef_only != 0, ST(stream));
 }
 
 int fedfr_bn_sliced_rows(int M, int C, int backward) { return ew_bn_sliced_rows(M, C, backward != 0); }
@@ -688,11 +679,9 @@ int fedfr_bn_bwd_sliced(const uint16_t* dy, const uint16_t* x, const float* mean
   BnBwdS p{};
   p.dy = BF(dy); p.x = BF(x); p.mean = mean; p.rstd = rstd; p.gamma = gamma; p.alpha = alpha; p.sc = sc; p.sh = sh; p.M = M; p.C = C;
   p.count = (double)M; p.partials = partials;
-  if (rows_in <= 0) FEDFR_TRY(ew_bn_bwd_reduce_sliced(p, ST(stream)));
-  p.part_in = partials; p.P = rows_in > 0 ? rows_in : ew_bn_sliced_rows(M, C, true);
   p.dgamma = dgamma; p.dbeta = dbeta; p.dalpha = dalpha; p.add = BF(add); p.dx = BFM(dx);
   p.nx = BF(nx); p.nmean = nmean; p.nrstd = nrstd; p.npart = npart;
-  return ew_bn_bwd_apply_sliced(p, ST(stream));
+  return ew_bn_bwd_sliced(p, rows_in, ST(stream));
 }
 
 // ---- head ------------------------------------------------------------------------------------------------------
@@ -838,7 +827,7 @@ int fedfr_bias_prelu_bwd(const uint16_t* dy, const uint16_t* x, const float* bia
                          float* coef, float* dbias, float* dalpha, const uint16_t* add, uint16_t* dx, void* stream) {
   return ew_bias_prelu_bwd(BF(dy), BF(x), bias, alpha, M, C, partials, coef, dbias, dalpha, BF(add), BFM(dx), ST(stream));
 }
-// the passes of the sphnet plan (net_sph.inc) and the eval-mode coefficient launch (net.hip), argument for argument: plumbing only
+// the launchers the sphnet plan (net_sph.inc) calls for its passes and the eval-mode coefficient launch (net.hip): plumbing only
 int fedfr_prelu_bwd_rows(int M, int C) { return ew_prelu_bwd_rows(M, C); }
 int fedfr_prelu_bwd_pass(const uint16_t* dy, const uint16_t* add, const uint16_t* x, const float* bias, const float* alpha, int M, int C,
                          uint16_t* gsum, uint16_t* dz, float* rows, void* stream) {

@@ -588,6 +588,13 @@ int ew_bn_bwd_apply(const BnBwd& p, hipStream_t st) {
   return FEDFR_OK;
 }
 
+int ew_bn_bwd_rowslab(const BnBwd& p, int rows_in, double count, float* dgamma, float* dbeta, float* dalpha, bool coef_only, hipStream_t st) {
+  if (rows_in <= 0) FEDFR_TRY(ew_bn_bwd_reduce(p, st));      // else: the producing pass already wrote the partials
+  FEDFR_TRY(ew_bn_bwd_finalize(p.partials, rows_in > 0 ? rows_in : ew_bn_bwd_grid(p.M, p.C), p.C, count, p.gamma, p.mean, p.rstd, dgamma, dbeta,
+                               dalpha, const_cast<float*>(p.coef), st));      // (coef: const to the apply kernel that reads it, written here)
+  return coef_only ? FEDFR_OK : ew_bn_bwd_apply(p, st);
+}
+
 // =====================================================================================================
 // bias + PReLU backward without normalisation (sphnet: conv(+bias) -> PReLU, reference backbones/sphnet.py:4-13, :53-60):
 // z = x + bias, dz = dy * (z > 0 ? 1 : alpha), dbias = sum dz, dalpha = sum dy * z [z <= 0], dx = dz (+ add).

@@ -646,3 +646,9 @@ int ew_bn_bwd_apply_sliced(BnBwdS p, hipStream_t st) {
   FEDFR_LAUNCH_CHECK("bn_bwd_apply_sliced");
   return FEDFR_OK;
 }
+
+int ew_bn_bwd_sliced(BnBwdS p, int rows_in, hipStream_t st) {
+  if (rows_in <= 0) FEDFR_TRY(ew_bn_bwd_reduce_sliced(p, st));      // else: the producing pass already wrote the rows
+  p.part_in = p.partials; p.P = rows_in > 0 ? rows_in : ew_bn_sliced_rows(p.M, p.C, true);
+  return ew_bn_bwd_apply_sliced(p, st);
+}

@@ -53,6 +53,9 @@ int ew_bn_bwd_reduce(const BnBwd& p, hipStream_t st);
 int ew_bn_bwd_finalize(const float* partials, int P, int C, double count, const float* gamma, const float* mean, const float* rstd,
                        float* dgamma, float* dbeta, float* dalpha, float* coef, hipStream_t st);
 int ew_bn_bwd_apply(const BnBwd& p, hipStream_t st);
+// The row-slab backward as the launches it is, for the plan (net.hip: bn_bwd) and the C ABI alike.  The rows live at p.partials: rows_in > 0 of them are
+// there already, else the reduce pass writes ew_bn_bwd_grid of them; finalize (-> parameter gradients, null = skipped, and p.coef); apply unless coef_only
+int ew_bn_bwd_rowslab(const BnBwd& p, int rows_in, double count, float* dgamma, float* dbeta, float* dalpha, bool coef_only, hipStream_t st);
 
 // ---- channel-sliced BatchNorm passes that reduce their partial rows themselves: no finalize launch (bn_sliced.hip) -------------
 // partial rows everywhere: [row][statistic][C] fp32, the layout the kernels above and the conv epilogues write
@@ -103,6 +106,8 @@ bool ew_bn_sliced_ok(int M, int C, int P_in, bool backward);
 int ew_bn_apply_sliced(BnApplyS p, hipStream_t st);
 int ew_bn_bwd_reduce_sliced(BnBwdS p, hipStream_t st);
 int ew_bn_bwd_apply_sliced(BnBwdS p, hipStream_t st);
+// ... and the sliced backward (plan and C ABI alike): rows at p.partials as above (else ew_bn_sliced_rows(M, C, true) of them); the apply pass reduces them itself (part_in / P set here)
+int ew_bn_bwd_sliced(BnBwdS p, int rows_in, hipStream_t st);
 
 // ---- BatchNorm1d on fp32 [B][C] (the `features` layer) ------------------------------------------------
 int ew_bn1d_fwd(const float* x, float* y, int B, int C, const float* gamma, const float* beta,

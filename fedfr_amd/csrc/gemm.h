@@ -34,7 +34,7 @@ struct GemmNT {
   float* bpart;
   // bmom != 0 (forward launches, round 3): the same epilogue leaves RAW moments of the output y against a same-shape tensor bx instead —
   // rows [3][N] of (sum y, sum y * bx, sum y * y) — from which the pass that follows derives the statistics of y AND of
-  // bn(y) + bx (the next block's bn1) without a pass over that sum (net.hip, conv2 of a residual block).  bmean / brstd: any readable [N].
+  // bn(y) + bx (the next block's bn1) without a pass over that sum (net.hip, conv2 of a residual block).  bmean / brstd: any readable [N] (conv_set_bmom).
   int bmom;               // 2 (dgrad launches, sphnet): a bare PReLU(+bias) precedes the conv — the OUTPUT becomes dz = dy * prelu'(bx + bias) (bias in
                           // bbeta or null, slopes in balpha), rows [3][N] = (sum dz, sum dy z over z <= 0, same): the PReLU's backward pass disappears
   // stride-2 dgrad by output-parity class (gemm.hip: nt_parity_problem): this launch computes the output pixels (2 h2 + par_h, 2 w2 + par_w)
@@ -116,6 +116,29 @@ inline GemmNT conv_dgrad_problem(int batch, int hin, int cin, int cout, int ksiz
     p.stride = 1; p.pad = 1; p.up = stride;
   }
   return p;
+}
+// The epilogues of a conv problem, attached from raw pointers: the plan (net.hip, net_sph.inc) and the fedfr_conv2d_* entries (api.hip) both
+// come through here.  BatchNorm-backward reduction on a dgrad's output (GemmNT::bx ...): rows [3][N] into `part`
+inline void conv_set_bnbwd(GemmNT& p, const bf16_t* bn_x, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                           const float* alpha, float* part) {
+  p.bx = bn_x; p.bmean = mean; p.brstd = rstd; p.bgamma = gamma; p.bbeta = beta; p.balpha = alpha; p.bpart = part;
+}
+// bmom modes: the kernels read bmean / brstd and never use them, so any readable [N] serves — the slopes where the mode has them, else the
+// rows the launch itself writes (at least [3][N])
+inline void conv_set_bmom(GemmNT& p, int bmom, const bf16_t* bx, float* part) {
+  p.bx = bx; p.bpart = part; p.bmom = bmom;
+  p.bmean = p.brstd = p.balpha ? p.balpha : part;
+}
+inline void conv_set_moments(GemmNT& p, const bf16_t* other, float* part) { conv_set_bmom(p, 1, other, part); }      // raw moments against same-shape `other`
+// PReLU-apply dgrad (bmom = 2): the output becomes dz of the PReLU(+bias) unit whose conv output is act_x
+inline void conv_set_papply(GemmNT& p, const bf16_t* act_x, const float* bias, const float* alpha, float* part) {
+  p.bbeta = bias; p.balpha = alpha; conv_set_bmom(p, 2, act_x, part);
+}
+// eval-mode output epilogue: y = prelu?(acc * scale + shift) (+ add); y2 (optional) = y * scale2 + shift2
+inline void conv_set_out_epilogue(GemmNT& p, const float* scale, const float* shift, const float* alpha, const bf16_t* add, bf16_t* y2,
+                                  const float* scale2, const float* shift2) {
+  p.esc = scale; p.esh = shift; p.ealpha = alpha; p.eadd = add;
+  if (y2) { p.Cb2 = y2; p.esc2 = scale2; p.esh2 = shift2; }
 }
 extern int g_tn_use_tr;
 inline GemmTN conv_wgrad_problem(int batch, int hin, int cin, int cout, int ksize, int stride) {

@@ -256,10 +256,14 @@ struct Ctx {
   bf16_t* t(int i) const { return reinterpret_cast<bf16_t*>(ws + n->ws_t[i]); }
   // tensors read by the weight-gradient GEMMs (dc2 = slot 0, dc1 = slot 1, dd = slot 2), double buffered per block parity
   bf16_t* tw(int slot, int par) const { return reinterpret_cast<bf16_t*>(ws + (par ? n->ws_t2[(par - 1) * 3 + slot] : n->ws_t[slot * 2])); }
-  float* save(const BnD& b, int which) const { return actf + b.save_off + (long long)which * b.C; }   // 0 scale 1 shift 2 mean 3 rstd
-  const float* gamma(const BnD& b) const { return params + b.g_off; }
-  const float* beta(const BnD& b) const { return params + b.b_off; }
 };
+// a BatchNorm's parameters, running statistics (forward passes only: a backward Ctx has no buffers) and the four rows it saves
+struct BnPtrs { const float *gamma, *beta; float *rm, *rv, *scale, *shift, *mean, *rstd; };
+static BnPtrs bn_ptrs(const Ctx& c, const BnD& b) {
+  float* s = c.actf + b.save_off;
+  return {c.params + b.g_off, c.params + b.b_off, c.bufs ? c.bufs + b.rm_off : nullptr, c.bufs ? c.bufs + b.rv_off : nullptr,
+          s, s + b.C, s + 2 * (long long)b.C, s + 3 * (long long)b.C};
+}
 
 static GemmNT fwd_problem(const Ctx& c, const ConvD& cv, const bf16_t* in, bf16_t* out) {
   GemmNT p = conv_fwd_problem(c.n->B, cv.Hin, cv.Cin, cv.Cout, cv.R, cv.stride);
@@ -279,12 +283,12 @@ int g_eval_fuse = 1;   // option "eval_fuse"
 static GemmNT conv_fwd_ep(const Ctx& c, const ConvD& cv, const bf16_t* in, bf16_t* out, const BnD& bn, const float* alpha, const bf16_t* add,
                              bf16_t* out2, const BnD* bn2) {
   GemmNT p = fwd_problem(c, cv, in, out);
-  p.esc = c.save(bn, 0); p.esh = c.save(bn, 1); p.ealpha = alpha; p.eadd = add;
-  if (out2) { p.Cb2 = out2; p.esc2 = c.save(*bn2, 0); p.esh2 = c.save(*bn2, 1); }
+  const BnPtrs b = bn_ptrs(c, bn), b2 = out2 ? bn_ptrs(c, *bn2) : BnPtrs{};
+  conv_set_out_epilogue(p, b.scale, b.shift, alpha, add, out2, b2.scale, b2.shift);
   return p;
 }
-static bool conv_epilogue_ok(const Ctx& c, const ConvD& cv, const BnD& bn) {      // (the plan reads which pointers are set, never through them)
-  return g_eval_fuse && gemm_nt_plan(conv_fwd_ep(c, cv, c.actb, c.actb, bn, nullptr, nullptr, nullptr, nullptr), 1).out_epilogue;
+static bool conv_epilogue_ok(const Ctx& c, const ConvD& cv, const BnD& bn, bool fuse) {      // (the plan reads which pointers are set, never through them)
+  return fuse && gemm_nt_plan(conv_fwd_ep(c, cv, c.actb, c.actb, bn, nullptr, nullptr, nullptr, nullptr), 1).out_epilogue;
 }
 int g_fwd_xmom = 1;       // option "fwd_xmom": bn3 + identity + the next block's bn1 as one pass from conv2's raw moments (14x14 / 28x28 blocks)
 int g_fuse_bnbwd28 = 1;   // option "fuse_bnbwd28": ... and in the two-tiles 28x28 dgrad (with fuse_bnbwd != 0)
@@ -308,7 +312,8 @@ static int conv_dgrad(const Ctx& c, const ConvD& cv, const bf16_t* dy, bf16_t* d
   p.A = dy; p.B = c.shadow + cv.wd_off; p.Cb = dx;
   if (bn && fused_rows && g_fuse_bnbwd) {
     GemmNT f = p;
-    f.bx = bn_x; f.bmean = c.save(*bn, 2); f.brstd = c.save(*bn, 3); f.bgamma = c.gamma(*bn); f.bbeta = c.beta(*bn); f.balpha = alpha; f.bpart = c.part();
+    const BnPtrs b = bn_ptrs(c, *bn);
+    conv_set_bnbwd(f, bn_x, b.mean, b.rstd, b.gamma, b.beta, alpha, c.part());
     const NtPlan pl = gemm_nt_plan(f, 1);
     // option value 2: only the kernels that leave one partial row per workgroup, few enough for the channel-sliced apply pass to reduce itself —
     // 14x14 (one per image), the persistent 64 -> 64 kernel (conv_c64p.hip), the two-tiles 28x28 kernel (256 at B = 128) where that pass takes them
@@ -389,11 +394,10 @@ static int conv_wgrad2(const Ctx& c, const ConvD& cva, const bf16_t* ina, const 
   FEDFR_TRY(conv_wgrad(c, cva, ina, dya, st));
   return conv_wgrad(c, cvb, inb, dyb, st);
 }
-struct Rows { const float* ptr; int P; };     // where a BatchNorm's partial statistics rows are
+struct Rows { float* ptr; int P; };     // where a BatchNorm's partial statistics rows are
 static int bn_coeffs(const Ctx& c, const BnD& b, Rows r, double count, bool training) {
-  if (training)
-    return ew_bn_finalize(r.ptr, r.P, b.C, count, c.gamma(b), c.beta(b), c.bufs + b.rm_off, c.bufs + b.rv_off, kBnMomentum,
-                          kBnEps, c.save(b, 0), c.save(b, 1), c.save(b, 2), c.save(b, 3), c.ftmp(), c.st);
+  const BnPtrs q = bn_ptrs(c, b);
+  if (training) return ew_bn_finalize(r.ptr, r.P, b.C, count, q.gamma, q.beta, q.rm, q.rv, kBnMomentum, kBnEps, q.scale, q.shift, q.mean, q.rstd, c.ftmp(), c.st);
   return FEDFR_OK;      // eval mode: every BatchNorm's (scale, shift) was computed up front by eval_coeffs_all (one launch)
 }
 // eval-mode coefficients of all 2-D BatchNorms of the network in one launch (they depend on parameters and running statistics only;
@@ -424,8 +428,9 @@ static int eval_coeffs_all(const Ctx& c) {
 static int apply(const Ctx& c, const bf16_t* x1, const BnD& b1, const float* alpha, const bf16_t* x2, const BnD* b2, bf16_t* y,
                  int M, bool stats, int nchw_hw = 0) {
   BnApply a{};
-  a.x1 = x1; a.sc1 = c.save(b1, 0); a.sh1 = c.save(b1, 1); a.alpha = alpha;
-  a.x2 = x2; a.sc2 = b2 ? c.save(*b2, 0) : nullptr; a.sh2 = b2 ? c.save(*b2, 1) : nullptr;
+  const BnPtrs q1 = bn_ptrs(c, b1), q2 = b2 ? bn_ptrs(c, *b2) : BnPtrs{};
+  a.x1 = x1; a.sc1 = q1.scale; a.sh1 = q1.shift; a.alpha = alpha;
+  a.x2 = x2; a.sc2 = q2.scale; a.sh2 = q2.shift;
   a.y = y; a.M = M; a.C = b1.C; a.nchw_hw = nchw_hw; a.stats = stats ? c.part() : nullptr;
   return ew_bn_apply(a, c.st);
 }
@@ -436,9 +441,9 @@ static int bn_apply_train(const Ctx& c, const BnD& b, Rows r, const bf16_t* x1, 
                           Rows* out) {
   if (ew_bn_sliced_ok(M, b.C, r.P, false)) {
     BnApplyS a{};
-    a.part = r.ptr; a.P = r.P; a.count = (double)M; a.gamma = c.gamma(b); a.beta = c.beta(b);
-    a.rm = c.bufs + b.rm_off; a.rv = c.bufs + b.rv_off; a.momentum = kBnMomentum; a.eps = kBnEps;
-    a.scale = c.save(b, 0); a.shift = c.save(b, 1); a.mean = c.save(b, 2); a.rstd = c.save(b, 3);
+    const BnPtrs q = bn_ptrs(c, b);
+    a.part = r.ptr; a.P = r.P; a.count = (double)M; a.gamma = q.gamma; a.beta = q.beta; a.rm = q.rm; a.rv = q.rv; a.momentum = kBnMomentum; a.eps = kBnEps;
+    a.scale = q.scale; a.shift = q.shift; a.mean = q.mean; a.rstd = q.rstd;
     a.x1 = x1; a.alpha = alpha; a.x2 = x2; a.y = y; a.M = M; a.C = b.C;
     a.stats = out ? c.part_other(r.ptr) : nullptr;
     if (out) *out = Rows{a.stats, ew_bn_sliced_rows(M, b.C)};
@@ -450,6 +455,27 @@ static int bn_apply_train(const Ctx& c, const BnD& b, Rows r, const bf16_t* x1, 
   return FEDFR_OK;
 }
 
+// the fc layer of either backbone.  Forward: out [B][F] = in [B][fc_in] W^T + bias, split-K slabs summed by ew_reduce_slabs
+static int fc_forward(const Ctx& c, const bf16_t* in, float* out) {
+  const FedfrNet* n = c.n;
+  GemmNT p{};
+  p.A = in; p.B = c.shadow + n->fc_w_off; p.M = n->B; p.N = n->F; p.K = n->fc_in; p.mode = 0; p.lda = n->fc_in; p.Cf = c.slab();
+  const int splits = gemm_nt_pick_splits(n->B, n->F, n->fc_in);
+  FEDFR_REQUIRE((size_t)splits * n->B * n->F <= n->slab_floats, "fc_forward: split-K slabs exceed the plan's slab workspace");
+  FEDFR_TRY(gemm_nt_launch(p, splits, c.st));
+  return ew_reduce_slabs(out, c.slab(), splits, (size_t)n->B * n->F, c.params + n->fc_b_off, n->F, c.st);
+}
+// Backward: the weight gradient [F][fc_in] = dY^T X (both operands batch-major -> TN kernel) on stream `wst`, and dX [Bp][fc_in] = dY W
+// (reduction over F: P = dY^T [F][Bp], Q = W [F][fc_in]) on the main stream.  dy: bf16 [B][F]; dyt: its transpose [F][Bp], columns >= B zero
+static int fc_backward(const Ctx& c, const bf16_t* dy, const bf16_t* dyt, const bf16_t* in, float* dx, hipStream_t wst) {
+  const FedfrNet* n = c.n;
+  GemmTN w{};
+  w.P = dy; w.Q = in; w.Kp = n->B; w.NI = n->F; w.NJ = n->fc_in; w.ldp = n->F; w.ldq = n->fc_in; w.out = c.grads + n->fc_w_off; w.use_tr = g_tn_use_tr;
+  FEDFR_TRY(gemm_tn_launch(w, 1, wst));
+  GemmTN d{};
+  d.P = dyt; d.Q = c.shadow + n->fc_w_off; d.Kp = n->F; d.NI = n->Bp; d.NJ = n->fc_in; d.ldp = n->Bp; d.ldq = n->fc_in; d.out = dx; d.use_tr = g_tn_use_tr;
+  return gemm_tn_launch(d, 1, c.st);
+}
 static int sph_prepare_weights(const FedfrNet* n, const float* params, bf16_t* shadow, int fwd_shadow_too, hipStream_t st);
 static int sph_forward(const FedfrNet* n, const float* x, const float* params, const bf16_t* shadow, unsigned char* act, unsigned char* ws,
                        float* feats, hipStream_t st);
@@ -490,8 +516,9 @@ int net_forward(const FedfrNet* n, const float* x, const float* params, float* b
   Ctx c{n, params, bufs, shadow, reinterpret_cast<bf16_t*>(act), reinterpret_cast<float*>(act + n->act_float_off_bytes), ws, nullptr, st};
   FEDFR_REQUIRE(training >= 0 && training <= 2, "net_forward: training must be 0 (eval), 1 (train) or 2 (train, BatchNorms frozen in eval mode)");
   // training = 2: every BatchNorm normalises with its running statistics and updates nothing (freeze_BN(test_mode=True)) while the net
-  // trains — dropout stays on and every activation the backward pass reads is kept: the per-layer eval path, not the fused epilogues
+  // trains — dropout stays on and every activation the backward pass reads is kept: the eval body with every fused epilogue refused
   const bool tr = training == 1, frozen = training == 2;
+  const bool fuse = g_eval_fuse && !frozen;
   n->bn_frozen = frozen;
   const int B = n->B, HW = n->HW;
   const int M0 = B * HW * HW;
@@ -518,18 +545,18 @@ int net_forward(const FedfrNet* n, const float* x, const float* params, float* b
   for (size_t bi = 0; bi < n->blocks.size(); ++bi) {
     const BlockD& k = n->blocks[bi];
     const int Mi = B * k.Hin * k.Hin, Mo = B * k.Hout * k.Hout;
-    if (!tr && !frozen && g_eval_fuse) {
-      // ---- eval mode: BatchNorms are known affines -> they ride in the conv epilogues where the kernel has one
+    if (!tr) {
+      // ---- eval mode: BatchNorms are known affines -> they ride in the conv epilogues where the kernel has one and `fuse` allows it
       if (!a1_ready) FEDFR_TRY(apply(c, A + k.x_off, k.bn1, nullptr, nullptr, nullptr, A + k.a1_off, Mi, false));
       a1_ready = false;
-      if (conv_epilogue_ok(c, k.conv1, k.bn2)) {
+      if (conv_epilogue_ok(c, k.conv1, k.bn2, fuse)) {
         FEDFR_TRY(gemm_nt_launch(conv_fwd_ep(c, k.conv1, A + k.a1_off, A + k.a2_off, k.bn2, params + k.alpha_off, nullptr, nullptr, nullptr), 1, st));
       } else {
         FEDFR_TRY(conv_fwd(c, k.conv1, A + k.a1_off, A + k.c1_off, false));
         FEDFR_TRY(apply(c, A + k.c1_off, k.bn2, params + k.alpha_off, nullptr, nullptr, A + k.a2_off, Mi, false));
       }
       if (k.has_ds) FEDFR_TRY(conv_fwd(c, k.ds, A + k.x_off, A + k.d_off, false));
-      if (conv_epilogue_ok(c, k.conv2, k.bn3)) {
+      if (conv_epilogue_ok(c, k.conv2, k.bn3, fuse)) {
         const bf16_t* idn = A + k.x_off;
         if (k.has_ds) {                                                 // identity = bnds(ds(x)), materialised in the (unused) c2 slot
           FEDFR_TRY(apply(c, A + k.d_off, k.bnds, nullptr, nullptr, nullptr, A + k.c2_off, Mo, false));
@@ -545,19 +572,6 @@ int net_forward(const FedfrNet* n, const float* x, const float* params, float* b
       }
       continue;
     }
-    if (!tr) {                                // eval mode without the fused epilogues: known affines, plain passes
-      FEDFR_TRY(apply(c, A + k.x_off, k.bn1, nullptr, nullptr, nullptr, A + k.a1_off, Mi, false));
-      FEDFR_TRY(conv_fwd(c, k.conv1, A + k.a1_off, A + k.c1_off, false));
-      FEDFR_TRY(apply(c, A + k.c1_off, k.bn2, params + k.alpha_off, nullptr, nullptr, A + k.a2_off, Mi, false));
-      FEDFR_TRY(conv_fwd(c, k.conv2, A + k.a2_off, A + k.c2_off, false));
-      if (k.has_ds) {
-        FEDFR_TRY(conv_fwd(c, k.ds, A + k.x_off, A + k.d_off, false));
-        FEDFR_TRY(apply(c, A + k.c2_off, k.bn3, nullptr, A + k.d_off, &k.bnds, A + k.out_off, Mo, false));
-      } else {
-        FEDFR_TRY(apply(c, A + k.c2_off, k.bn3, nullptr, A + k.x_off, nullptr, A + k.out_off, Mo, false));
-      }
-      continue;
-    }
     // a1 = bn1(x) -> conv1 -> a2 = prelu(bn2(c1)) -> conv2(stride) -> bn3(c2) + identity.  Statistics: the pass that produced x left
     // them in `prev`; a conv's epilogue leaves its output's in c.part()
     // round 3 (option fwd_xmom): where conv2 runs on an LDS-DMA kernel with the moment epilogue, out = bn3(c2) + x AND the next block's
@@ -570,7 +584,7 @@ int net_forward(const FedfrNet* n, const float* x, const float* params, float* b
     FEDFR_TRY(conv_fwd(c, k.conv1, A + k.a1_off, A + k.c1_off, true, &live));
     FEDFR_TRY(bn_apply_train(c, k.bn2, Rows{c.part(), live}, A + k.c1_off, params + k.alpha_off, nullptr, A + k.a2_off, Mi, nullptr));
     GemmNT pm = fwd_problem(c, k.conv2, A + k.a2_off, A + k.c2_off);      // conv2 with the moment epilogue
-    pm.bx = A + k.x_off; pm.bmean = c.save(k.bn3, 2); pm.brstd = c.save(k.bn3, 3); pm.bpart = c.part(); pm.bmom = 1;
+    conv_set_moments(pm, A + k.x_off, c.part());
     const NtPlan plm = gemm_nt_plan(pm, 1);
     // (x must have the output's shape; one partial row per workgroup, which the sliced pass reduces itself)
     const bool xmom = g_fwd_xmom && nxb && !k.has_ds && k.conv2.Cin == k.Cout && nxb->bn1.C == k.Cout && plm.part_rows > 0 &&
@@ -579,13 +593,11 @@ int net_forward(const FedfrNet* n, const float* x, const float* params, float* b
     if (xmom) {
       FEDFR_TRY(gemm_nt_launch(pm, 1, c.st));
       BnApply2S a{};
+      const BnPtrs q = bn_ptrs(c, k.bn3), qx = bn_ptrs(c, k.bn1), qn = bn_ptrs(c, nxb->bn1);
       a.part = c.part(); a.P = plm.part_rows; a.count = (double)Mo; a.momentum = kBnMomentum; a.eps = kBnEps;
-      a.gamma = c.gamma(k.bn3); a.beta = c.beta(k.bn3); a.rm = c.bufs + k.bn3.rm_off; a.rv = c.bufs + k.bn3.rv_off;
-      a.scale = c.save(k.bn3, 0); a.shift = c.save(k.bn3, 1); a.mean = c.save(k.bn3, 2); a.rstd = c.save(k.bn3, 3);
-      a.xmean = c.save(k.bn1, 2); a.xrstd = c.save(k.bn1, 3);
-      const BnD& nb = nxb->bn1;
-      a.ngamma = c.gamma(nb); a.nbeta = c.beta(nb); a.nrm = c.bufs + nb.rm_off; a.nrv = c.bufs + nb.rv_off;
-      a.nscale = c.save(nb, 0); a.nshift = c.save(nb, 1); a.nmean = c.save(nb, 2); a.nrstd = c.save(nb, 3);
+      a.gamma = q.gamma; a.beta = q.beta; a.rm = q.rm; a.rv = q.rv; a.scale = q.scale; a.shift = q.shift; a.mean = q.mean; a.rstd = q.rstd;
+      a.xmean = qx.mean; a.xrstd = qx.rstd;
+      a.ngamma = qn.gamma; a.nbeta = qn.beta; a.nrm = qn.rm; a.nrv = qn.rv; a.nscale = qn.scale; a.nshift = qn.shift; a.nmean = qn.mean; a.nrstd = qn.rstd;
       a.x1 = A + k.c2_off; a.x2 = A + k.x_off; a.y = A + k.out_off; a.y2 = A + nxb->a1_off; a.M = Mo; a.C = k.Cout;
       FEDFR_TRY(ew_bn_apply2_sliced(a, c.st));
       a1_ready = true;
@@ -612,15 +624,7 @@ int net_forward(const FedfrNet* n, const float* x, const float* params, float* b
   FEDFR_TRY(apply(c, A + last.out_off, n->bn2, nullptr, nullptr, nullptr, A + n->t_off, Mf, false, hw));
   if ((tr || frozen) && n->dropout_p > 0.f)            // nn.Dropout(p, inplace=True) on the flattened bn2 output (iresnet.py:169); identity in eval mode
     FEDFR_TRY(ew_dropout_fwd(A + n->t_off, act + n->mask_off_bytes, (size_t)B * n->fc_in, n->dropout_p, n->dropout_seed, n->dropout_step++, st));
-  {
-    GemmNT p{};
-    p.A = A + n->t_off; p.B = shadow + n->fc_w_off; p.M = B; p.N = n->F; p.K = n->fc_in; p.mode = 0; p.lda = n->fc_in;
-    p.Cb = nullptr; p.Cf = c.slab(); p.stats = nullptr;
-    const int splits = gemm_nt_pick_splits(B, n->F, n->fc_in);
-    FEDFR_REQUIRE((size_t)splits * B * n->F <= n->slab_floats, "net_forward: fc split-K slabs exceed the plan's slab workspace");
-    FEDFR_TRY(gemm_nt_launch(p, splits, st));
-    FEDFR_TRY(ew_reduce_slabs(c.actf + n->yfc_off, c.slab(), splits, (size_t)B * n->F, params + n->fc_b_off, n->F, st));
-  }
+  FEDFR_TRY(fc_forward(c, A + n->t_off, c.actf + n->yfc_off));
   FEDFR_TRY(ew_bn1d_fwd(c.actf + n->yfc_off, feats, B, n->F, params + n->feat_bn.g_off, params + n->feat_bn.b_off,
                         bufs + n->feat_bn.rm_off, bufs + n->feat_bn.rv_off, kBnMomentum, kBnEps, tr ? 1 : 0,
                         c.actf + n->feat_save_off, c.actf + n->feat_save_off + n->F, st));
@@ -647,59 +651,61 @@ static int dbg_capture(const bf16_t* src, size_t elems, size_t* off, hipStream_t
 }
 static const int g_wgrad_depth = kWgradDepth;   // generations of weight-gradient operands in flight (fewer: the main stream waits for the weight-gradient stream)
 int g_fuse_bnred_next = 1;   // option "fuse_bnred_next": a BN-backward apply pass also reduces its output for the BN that consumes it
-// BatchNorm (+PReLU) backward: dx = a dz + A x + B (+ addend).  `have`: partial rows that already exist (left by the pass that produced
-// dy); else a reduce pass runs first.  With next_bn, dx is also reduced as the dy of that BatchNorm's backward -> *next_rows.
-// Channel-sliced passes without a finalize launch where the shape allows (bn_sliced.hip), else reduce / finalize / apply of bn_rowslab.hip.
-static int bn_bwd(const Ctx& c, const BnD& b, const float* alpha, const bf16_t* dy, const bf16_t* x, int M, const bf16_t* add,
-                  const bf16_t* add_up, int H, bf16_t* dx, long long alpha_off, Rows have = Rows{nullptr, 0}, const BnD* next_bn = nullptr,
-                  const bf16_t* next_x = nullptr, Rows* next_rows = nullptr, const float* next_alpha = nullptr, bool coef_only = false) {
-  // (coef_only: reduce if needed + finalize, no apply pass — the consumer applies c.coef() itself: the stem's weight gradient; row-slab form only)
-  // (next_alpha: the consuming BatchNorm has a PReLU behind it — the stem's; served by the row-slab apply pass without own PReLU / addend)
+// BatchNorm (+PReLU) backward: dx = a dz + A x + B (+ addend).  This function decides which form runs and what rides along; the launches of
+// either form are ew_bn_bwd_sliced / ew_bn_bwd_rowslab (ew.h), which the C ABI entries call too.
+struct NextBn {               // the BatchNorm that consumes dx (no own addend): dx is also reduced as the dy of ITS backward
+  const BnD* bn = nullptr; const bf16_t* x = nullptr;      // ... and its input tensor, same [M][C] shape
+  long long slope_off = -1;   // >= 0: a PReLU follows it (the stem's) — served by the row-slab apply pass without own PReLU / addend
+  Rows* rows = nullptr;       // where the rows are reported
+};
+struct BnBwdArgs {
+  const BnD* bn;
+  long long slope_off = -1;   // >= 0: a PReLU with these slopes follows the BatchNorm
+  const bf16_t* dy; const bf16_t* x; int M; bf16_t* dx;
+  const bf16_t* add = nullptr;                // same-shape addend (identity-path gradient)
+  const bf16_t* add_up = nullptr; int H = 0;  // compact [img][H/2][H/2][C] addend placed at even (h, w)
+  Rows have{nullptr, 0};      // partial rows that already exist (left by the pass that produced dy); else a reduce pass runs first
+  NextBn next{};
+  bool coef_only = false;     // reduce if needed + finalize, no apply pass: the consumer applies c.coef() itself (the stem's weight gradient; row-slab form only)
+};
+static int bn_bwd(const Ctx& c, const BnBwdArgs& a) {
+  const BnD& b = *a.bn; const int M = a.M;
+  const float* alpha = a.slope_off >= 0 ? c.params + a.slope_off : nullptr;
+  float* dalpha = a.slope_off >= 0 ? c.grads + a.slope_off : nullptr;
 #ifdef FEDFR_DBG_SKIP14
   // timing experiment only (WRONG results; tools/build_ablate.sh net.hip FEDFR_DBG_SKIP14 1): the bn1 / bn3 backward passes of the 14x14 stage are free —
   // the upper bound of anything that takes them out of the dispatcher's hands
   if (FEDFR_DBG_SKIP14 && !alpha && !c.n->block_only && M == c.n->B * 196 && b.C == 256) return FEDFR_OK;
 #endif
-  const bool nxt = next_bn && next_x && next_rows && g_fuse_bnred_next && next_bn->C == b.C &&
-                   (!next_alpha || (!alpha && !add && !ew_bn_sliced_ok(M, b.C, have.P > 0 ? have.P : ew_bn_sliced_rows(M, b.C, true), true)));
+  const bool sliced_ok = ew_bn_sliced_ok(M, b.C, a.have.P > 0 ? a.have.P : ew_bn_sliced_rows(M, b.C, true), true);
+  const bool nxt = a.next.bn && a.next.x && a.next.rows && g_fuse_bnred_next && a.next.bn->C == b.C &&
+                   (a.next.slope_off < 0 || (!alpha && !a.add && !sliced_ok));
+  const BnPtrs q = bn_ptrs(c, b), qn = nxt ? bn_ptrs(c, *a.next.bn) : BnPtrs{};
+  float* rows = a.have.P > 0 ? a.have.ptr : c.part();
   // frozen BatchNorm (eval mode inside a training net): mean / rstd were constants, so dx = gamma rstd dz — the same passes with an infinite
   // count (the two mean terms vanish); dgamma / dbeta / dalpha are the same sums
   const double count = c.n->bn_frozen ? HUGE_VAL : (double)M;
-  if (!coef_only && !add_up && ew_bn_sliced_ok(M, b.C, have.P > 0 ? have.P : ew_bn_sliced_rows(M, b.C, true), true)) {
+  if (!a.coef_only && !a.add_up && sliced_ok) {
     BnBwdS p{};
-    p.dy = dy; p.x = x; p.mean = c.save(b, 2); p.rstd = c.save(b, 3); p.gamma = c.gamma(b); p.alpha = alpha;
-    p.sc = c.save(b, 0); p.sh = c.save(b, 1); p.M = M; p.C = b.C; p.count = count;
-    p.dgamma = c.grads + b.g_off; p.dbeta = c.grads + b.b_off; p.dalpha = alpha ? c.grads + alpha_off : nullptr;
-    p.add = add; p.dx = dx;
-    if (have.P > 0) {
-      p.part_in = have.ptr; p.P = have.P;
-    } else {
-      p.partials = c.part();
-      FEDFR_TRY(ew_bn_bwd_reduce_sliced(p, c.st));
-      p.part_in = c.part(); p.P = ew_bn_sliced_rows(M, b.C, true);
-    }
+    p.dy = a.dy; p.x = a.x; p.mean = q.mean; p.rstd = q.rstd; p.gamma = q.gamma; p.alpha = alpha; p.sc = q.scale; p.sh = q.shift;
+    p.M = M; p.C = b.C; p.count = count; p.partials = rows; p.dgamma = c.grads + b.g_off; p.dbeta = c.grads + b.b_off; p.dalpha = dalpha; p.add = a.add; p.dx = a.dx;
     if (nxt) {
-      p.nx = next_x; p.nmean = c.save(*next_bn, 2); p.nrstd = c.save(*next_bn, 3); p.npart = c.part_other(p.part_in);
-      *next_rows = Rows{p.npart, ew_bn_sliced_rows(M, b.C, true)};
+      p.nx = a.next.x; p.nmean = qn.mean; p.nrstd = qn.rstd; p.npart = c.part_other(rows);
+      *a.next.rows = Rows{p.npart, ew_bn_sliced_rows(M, b.C, true)};
     }
-    return ew_bn_bwd_apply_sliced(p, c.st);
+    return ew_bn_bwd_sliced(p, a.have.P, c.st);
   }
   BnBwd p{};
   if (nxt) {
-    // dx is the dy of next_bn's backward: its (sum, sum * xhat) partials ride along in this apply pass (one tensor read instead of
+    // dx is the dy of the next BatchNorm's backward: its (sum, sum * xhat) partials ride along in this apply pass (one tensor read instead of
     // a separate two-tensor reduce kernel); they land in the shared partial buffer, which this BN's finalize has finished reading
-    p.nx = next_x; p.nmean = c.save(*next_bn, 2); p.nrstd = c.save(*next_bn, 3); p.npart = c.part();
-    if (next_alpha) { p.nsc = c.save(*next_bn, 0); p.nsh = c.save(*next_bn, 1); p.nalpha = next_alpha; }
-    *next_rows = Rows{c.part(), ew_bn_bwd_apply_grid(M, b.C)};
+    p.nx = a.next.x; p.nmean = qn.mean; p.nrstd = qn.rstd; p.npart = c.part();
+    if (a.next.slope_off >= 0) { p.nsc = qn.scale; p.nsh = qn.shift; p.nalpha = c.params + a.next.slope_off; }
+    *a.next.rows = Rows{c.part(), ew_bn_bwd_apply_grid(M, b.C)};
   }
-  p.dy = dy; p.x = x; p.mean = c.save(b, 2); p.rstd = c.save(b, 3); p.gamma = c.gamma(b); p.beta = c.beta(b); p.alpha = alpha;
-  p.sc = c.save(b, 0); p.sh = c.save(b, 1);
-  p.M = M; p.C = b.C; p.partials = c.part(); p.coef = c.coef(); p.add = add; p.add_up = add_up; p.H = H; p.W = H; p.dx = dx;
-  if (have.P <= 0) FEDFR_TRY(ew_bn_bwd_reduce(p, c.st));      // else: the producing pass already wrote the partials
-  FEDFR_TRY(ew_bn_bwd_finalize(have.P > 0 ? have.ptr : c.part(), have.P > 0 ? have.P : ew_bn_bwd_grid(M, b.C), b.C, count, c.gamma(b), c.save(b, 2),
-                               c.save(b, 3), c.grads + b.g_off, c.grads + b.b_off, alpha ? c.grads + alpha_off : nullptr, c.coef(), c.st));
-  if (coef_only) return FEDFR_OK;
-  return ew_bn_bwd_apply(p, c.st);
+  p.dy = a.dy; p.x = a.x; p.mean = q.mean; p.rstd = q.rstd; p.gamma = q.gamma; p.beta = q.beta; p.alpha = alpha; p.sc = q.scale; p.sh = q.shift;
+  p.M = M; p.C = b.C; p.partials = rows; p.coef = c.coef(); p.add = a.add; p.add_up = a.add_up; p.H = a.H; p.W = a.H; p.dx = a.dx;
+  return ew_bn_bwd_rowslab(p, a.have.P, count, c.grads + b.g_off, c.grads + b.b_off, dalpha, a.coef_only, c.st);
 }
 
 int g_stem_fuse_wgrad = 1;   // option "stem_fuse_wgrad": the stem's BatchNorm + PReLU backward is applied by its weight-gradient kernel on load (no d(conv output) tensor)
@@ -770,24 +776,14 @@ int net_backward(const FedfrNet* n, const float* x, const float* dfeats, const f
   // the first fork: the weight-gradient stream starts behind the forward pass and the features' backward; fc's weight gradient is its first
   // kernel (round 3: it ran on the main stream, 20 us in front of everything else)
   fk.order(st, wst);
-  {  // fc.weight grad [F][fc_in] = dY^T X   (both operands batch-major -> TN kernel)
-    GemmTN p{};
-    p.P = c.dyb(); p.Q = A + n->t_off; p.Kp = B; p.NI = F; p.NJ = n->fc_in; p.mode = 0; p.ldp = F; p.ldq = n->fc_in;
-    p.out = grads + n->fc_w_off; p.use_tr = g_tn_use_tr;
-    FEDFR_TRY(gemm_tn_launch(p, 1, wst));
-  }
-  {  // dX [Bp][fc_in] = dY W   (reduction over F: P = dY^T [F][Bp], Q = W [F][fc_in])
-    GemmTN p{};
-    p.P = c.dybt(); p.Q = shadow + n->fc_w_off; p.Kp = F; p.NI = n->Bp; p.NJ = n->fc_in; p.mode = 0; p.ldp = n->Bp; p.ldq = n->fc_in;
-    p.out = dxfc; p.use_tr = g_tn_use_tr;
-    FEDFR_TRY(gemm_tn_launch(p, 1, st));
-  }
+  FEDFR_TRY(fc_backward(c, c.dyb(), c.dybt(), A + n->t_off, dxfc, wst));
   const BlockD& last = n->blocks.back();
   const int hw = n->final_hw * n->final_hw, Mf = B * hw;
   if (n->dropout_p > 0.f) FEDFR_TRY(ew_dropout_bwd(dxfc, act + n->mask_off_bytes, (size_t)B * n->fc_in, n->dropout_p, st));
   FEDFR_TRY(ew_nchw_f32_to_nhwc_bf16(dxfc, c.g(0), B, n->final_C, hw, st));
   if (g_dbg_grads && g_dbg_detail) FEDFR_TRY(dbg_capture(c.g(0), (size_t)Mf * n->final_C, &dbg_off, st));      // detail: the gradient entering bn2's backward, first
-  FEDFR_TRY(bn_bwd(c, n->bn2, nullptr, c.g(0), A + last.out_off, Mf, nullptr, nullptr, 0, c.g(1), 0, Rows{nullptr, 0}, &last.bn3, A + last.c2_off, &pend));
+  FEDFR_TRY(bn_bwd(c, {.bn = &n->bn2, .dy = c.g(0), .x = A + last.out_off, .M = Mf, .dx = c.g(1),
+                       .next = {.bn = &last.bn3, .x = A + last.c2_off, .rows = &pend}}));
   }
   int cur = 1;
   // fused SGD (NetSgd): [sgd_lo, sgd_hi) = parameter range whose gradients are complete on the main stream and whose weight gradients are
@@ -823,19 +819,19 @@ int net_backward(const FedfrNet* n, const float* x, const float* dfeats, const f
     };
     fk.wait(st, wdone[par]);                         // the weight GEMMs kWgradDepth blocks ago were the last readers of dc2/dc1/dd[par]
     // out = bn3(c2) + identity
-    FEDFR_TRY(bn_bwd(c, k.bn3, nullptr, g, A + k.c2_off, Mo, nullptr, nullptr, 0, dc2, 0, pend));
+    FEDFR_TRY(bn_bwd(c, {.bn = &k.bn3, .dy = g, .x = A + k.c2_off, .M = Mo, .dx = dc2, .have = pend}));
     FEDFR_TRY(detail(dc2, (size_t)Mo * k.Cout));
     pend = Rows{nullptr, 0};
     int f2 = 0, f1 = 0;
     FEDFR_TRY(conv_dgrad(c, k.conv2, dc2, da2, &k.bn2, A + k.c1_off, params + k.alpha_off, &f2));
     FEDFR_TRY(detail(da2, (size_t)Mi * k.Cout));
     // a2 = prelu(bn2(c1))
-    FEDFR_TRY(bn_bwd(c, k.bn2, params + k.alpha_off, da2, A + k.c1_off, Mi, nullptr, nullptr, 0, dc1, k.alpha_off, Rows{c.part(), f2}));
+    FEDFR_TRY(bn_bwd(c, {.bn = &k.bn2, .slope_off = k.alpha_off, .dy = da2, .x = A + k.c1_off, .M = Mi, .dx = dc1, .have = Rows{c.part(), f2}}));
     FEDFR_TRY(detail(dc1, (size_t)Mi * k.Cout));
     // identity path first (its BN reduction uses the shared partial buffer), then conv1's dgrad whose epilogue may
     // leave bn1's partial sums there for the bn_bwd that follows immediately
     if (k.has_ds) {
-      FEDFR_TRY(bn_bwd(c, k.bnds, nullptr, g, A + k.d_off, Mo, nullptr, nullptr, 0, dd, 0));
+      FEDFR_TRY(bn_bwd(c, {.bn = &k.bnds, .dy = g, .x = A + k.d_off, .M = Mo, .dx = dd}));
       FEDFR_TRY(detail(dd, (size_t)Mo * k.Cout));
     }
     // ONE fork per block: every event record costs the main stream a ~8 us bubble (kernel trace), so the block's two or three
@@ -853,19 +849,13 @@ int net_backward(const FedfrNet* n, const float* x, const float* dfeats, const f
     wdone[par] = fk.mark(wst);
     FEDFR_TRY(conv_dgrad(c, k.conv1, dc1, da1, &k.bn1, A + k.x_off, nullptr, &f1));
     FEDFR_TRY(detail(da1, (size_t)Mi * k.Cin));
-    // a1 = bn1(x)
-    const BlockD* prev = bi > 0 ? &n->blocks[bi - 1] : nullptr;      // its bn3 consumes gin next
-    if (k.has_ds && !prev && !n->block_only && g_stem_bnred) {
-      // the first block: its input gradient is the dy of the STEM's BatchNorm (+PReLU) backward, reduced here (one pass over two 205 MB tensors fewer)
-      FEDFR_TRY(bn_bwd(c, k.bn1, nullptr, da1, A + k.x_off, Mi, nullptr, dxd, k.Hin, gin, 0, Rows{c.part(), f1}, &n->stem_bn, A + n->c0_off, &pend,
-                       params + n->stem_alpha_off));
-    } else if (k.has_ds) {
-      FEDFR_TRY(bn_bwd(c, k.bn1, nullptr, da1, A + k.x_off, Mi, nullptr, dxd, k.Hin, gin, 0, Rows{c.part(), f1}, prev ? &prev->bn3 : nullptr,
-                       prev ? A + prev->c2_off : nullptr, &pend));
-    } else {
-      FEDFR_TRY(bn_bwd(c, k.bn1, nullptr, da1, A + k.x_off, Mi, g, nullptr, 0, gin, 0, Rows{c.part(), f1}, prev ? &prev->bn3 : nullptr,
-                       prev ? A + prev->c2_off : nullptr, &pend));
-    }
+    // a1 = bn1(x).  The identity path's gradient joins here: g itself, or the downsample conv's compact dxd.  gin is then the dy of the previous
+    // block's bn3 — or, behind the first block, of the STEM's BatchNorm (+PReLU) backward, reduced here (one pass over two 205 MB tensors fewer)
+    BnBwdArgs b1{.bn = &k.bn1, .dy = da1, .x = A + k.x_off, .M = Mi, .dx = gin, .have = Rows{c.part(), f1}};
+    if (k.has_ds) { b1.add_up = dxd; b1.H = k.Hin; } else b1.add = g;
+    if (bi > 0) b1.next = {.bn = &n->blocks[bi - 1].bn3, .x = A + n->blocks[bi - 1].c2_off, .rows = &pend};
+    else if (k.has_ds && !n->block_only && g_stem_bnred) b1.next = {.bn = &n->stem_bn, .x = A + n->c0_off, .slope_off = n->stem_alpha_off, .rows = &pend};
+    FEDFR_TRY(bn_bwd(c, b1));
     cur ^= 1;
     if (sgd && !n->block_only && k.has_ds && bi > 0) sgd_lo = k.bn1.g_off;      // a stage is complete: its range goes out behind the next fork
   }
@@ -885,11 +875,10 @@ int net_backward(const FedfrNet* n, const float* x, const float* dfeats, const f
   // ---- stem: a0 = prelu(bn1(conv1(x))) ----
   bf16_t* dz0 = c.t(1);
   const bool fuse = g_stem_fuse_wgrad != 0;
-  FEDFR_TRY(bn_bwd(c, n->stem_bn, params + n->stem_alpha_off, c.g(cur), A + n->c0_off, M0, nullptr, nullptr, 0, dz0, n->stem_alpha_off, pend, nullptr, nullptr,
-                   nullptr, nullptr, fuse));
+  FEDFR_TRY(bn_bwd(c, {.bn = &n->stem_bn, .slope_off = n->stem_alpha_off, .dy = c.g(cur), .x = A + n->c0_off, .M = M0, .dx = dz0, .have = pend, .coef_only = fuse}));
   if (fuse)     // the only reader of d(conv output) is the weight gradient: it applies the backward to its operand tile (two 205 MB streams fewer at batch 128)
     FEDFR_TRY(ew_stem_wgrad(x, c.g(cur), grads + n->stem.w_off, reinterpret_cast<float*>(ws + n->ws_stem), B, HW, HW, st, A + n->c0_off, c.coef(),
-                            c.save(n->stem_bn, 0), c.save(n->stem_bn, 1), params + n->stem_alpha_off));
+                            bn_ptrs(c, n->stem_bn).scale, bn_ptrs(c, n->stem_bn).shift, params + n->stem_alpha_off));
   else
   FEDFR_TRY(ew_stem_wgrad(x, dz0, grads + n->stem.w_off, reinterpret_cast<float*>(ws + n->ws_stem), B, HW, HW, st));
   fk.order(wst, st);

@@ -205,13 +205,7 @@ static int sph_forward(const FedfrNet* n, const float* x, const float* params, c
       FEDFR_TRY(sph_conv_act(c, k.u2, A + k.u1.in_off, A + k.u2.t_off, last ? stg.H * stg.H : 0));
     }
   }
-  GemmNT p{};
-  p.A = A + n->sph_flat_off; p.B = shadow + n->fc_w_off; p.M = B; p.N = n->F; p.K = n->fc_in; p.mode = 0; p.lda = n->fc_in;
-  p.Cb = nullptr; p.Cf = c.slab(); p.stats = nullptr;
-  const int splits = gemm_nt_pick_splits(B, n->F, n->fc_in);
-  FEDFR_REQUIRE((size_t)splits * B * n->F <= n->slab_floats, "sph_forward: fc split-K slabs exceed the plan's slab workspace");
-  FEDFR_TRY(gemm_nt_launch(p, splits, st));
-  return ew_reduce_slabs(feats, c.slab(), splits, (size_t)B * n->F, params + n->fc_b_off, n->F, st);
+  return fc_forward(c, A + n->sph_flat_off, feats);
 }
 
 static int sph_backward(const FedfrNet* n, const float* dfeats, const float* params, const bf16_t* shadow, unsigned char* act, unsigned char* ws,
@@ -230,18 +224,7 @@ static int sph_backward(const FedfrNet* n, const float* dfeats, const float* par
   FEDFR_LAUNCH_CHECK("sph_dfeats");
   FEDFR_TRY(head_colsum_f32(dfeats, B, F, grads + n->fc_b_off, st));
   float* dxfc = reinterpret_cast<float*>(ws + n->ws_fc);
-  {
-    GemmTN p{};
-    p.P = dyb; p.Q = A + n->sph_flat_off; p.Kp = B; p.NI = F; p.NJ = n->fc_in; p.mode = 0; p.ldp = F; p.ldq = n->fc_in;
-    p.out = grads + n->fc_w_off; p.use_tr = g_tn_use_tr;
-    FEDFR_TRY(gemm_tn_launch(p, 1, st));
-  }
-  {
-    GemmTN p{};
-    p.P = dybt; p.Q = shadow + n->fc_w_off; p.Kp = F; p.NI = n->Bp; p.NJ = n->fc_in; p.mode = 0; p.ldp = n->Bp; p.ldq = n->fc_in;
-    p.out = dxfc; p.use_tr = g_tn_use_tr;
-    FEDFR_TRY(gemm_tn_launch(p, 1, st));
-  }
+  FEDFR_TRY(fc_backward(c, dyb, dybt, A + n->sph_flat_off, dxfc, st));      // (sphnet keeps the weight gradient on the main stream)
   auto G = [&](int i) { return reinterpret_cast<bf16_t*>(ws + n->sph_ws_g[i]); };
   int cur = 0;
   FEDFR_TRY(ew_nchw_f32_to_nhwc_bf16(dxfc, G(cur), B, 512, 49, st));       // gradient wrt the last activation, NHWC bf16
@@ -281,9 +264,7 @@ static int sph_backward(const FedfrNet* n, const float* dfeats, const float* par
     *fused = 0;
     GemmNT p = conv_dgrad_problem(B, cv.Hin, cv.Cin, cv.Cout, cv.R, cv.stride);
     p.A = dy; p.B = c.shadow + cv.wd_off; p.Cb = reinterpret_cast<bf16_t*>(ws + pu.dz_off);
-    p.bx = A + pu.c_off; p.bbeta = pu.b_off >= 0 ? params + pu.b_off : nullptr; p.balpha = params + pu.a_off;
-    p.bmean = params + pu.a_off; p.brstd = params + pu.a_off;      // (read, never used in this mode)
-    p.bpart = reinterpret_cast<float*>(ws + pu.rows_off); p.bmom = 2;
+    conv_set_papply(p, A + pu.c_off, pu.b_off >= 0 ? params + pu.b_off : nullptr, params + pu.a_off, reinterpret_cast<float*>(ws + pu.rows_off));
     const NtPlan pl = gemm_nt_plan(p, 1);
     if (!g_sph_fuse_prelu_bwd || p.N != pu.conv.Cout || (pl.kernel != NtKernel::glds8_papply_w14 && pl.kernel != NtKernel::glds8_papply_w28s) ||
         (size_t)pl.part_rows * 3 > (size_t)ew_prelu_bwd_rows(p.M, pu.conv.Cout) * 2) return FEDFR_OK;

@@ -66,8 +66,8 @@ int main(int argc, char** argv) {
   std::vector<float> hc((size_t)5 * N, 0.5f);
   CK(hipMemcpy(coef, hc.data(), hc.size() * 4, hipMemcpyHostToDevice));
   CK(hipMalloc(&bpart, (size_t)(M / 196) * 3 * N * 4));
-  p.stats = nullptr; p.bx = X; p.bmean = coef; p.brstd = coef + N; p.bgamma = coef + 2 * N; p.bbeta = coef + 3 * N; p.bpart = bpart;
-  p.balpha = PROBE_FUSED == 2 ? coef + 4 * N : nullptr;
+  p.stats = nullptr;
+  conv_set_bnbwd(p, X, coef, coef + N, coef + 2 * N, coef + 3 * N, PROBE_FUSED == 2 ? coef + 4 * N : nullptr, bpart);
 #endif
   hipStream_t st;
   CK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
