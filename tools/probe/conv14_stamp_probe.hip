@@ -1,6 +1,6 @@
 // Hardware probe (diagnostics, not product): where does a launch of the 14x14 LDS-DMA conv kernel spend its time?
 //
-// Compiles conv3x3_glds_kernel<14, 14, 32, 4, false> (fedfr_amd/csrc/conv_glds_impl.h) with its in-kernel phase stamps (FEDFR_HALO2_STAMPS:
+// Compiles conv3x3_glds_kernel<14, 14, 32, 4, Epi::plain> (fedfr_amd/csrc/conv_glds_impl.h) with its in-kernel phase stamps (FEDFR_HALO2_STAMPS:
 // wave 0 of every workgroup stores wall_clock64() — the 100 MHz constant clock, comparable across CUs — at kernel entry, behind the prologue's
 // first barrier, behind the K loop and at the end of the epilogue), runs the headline layer (128 images, 256 -> 256 channels) back to back and
 // prints, over the 256 workgroups of the LAST launch, the phase durations and the launch's own timeline (first entry -> last exit).
@@ -78,9 +78,9 @@ int main(int argc, char** argv) {
   plan.part_rows = PROBE_FUSED ? M / 196 / (PROBE_W == 14 ? 1 : 2) : 0;
   auto launch = [&]() {
 #if PROBE_W == 14
-    return launch_glds<14, 14, 32, 4, PROBE_FUSED != 0>(p, plan, st);
+    return launch_glds<14, 14, 32, 4, PROBE_FUSED ? Epi::bnbwd : Epi::plain>(p, plan, st);
 #else
-    return launch_glds<28, 7, 40, 4, PROBE_FUSED != 0, 128, false, 2>(p, plan, st);
+    return launch_glds<28, 7, 40, 4, PROBE_FUSED ? Epi::bnbwd : Epi::plain, 128, false, 2>(p, plan, st);
 #endif
   };
   for (int i = 0; i < 10; ++i) if (launch()) { printf("launch refused\n"); return 1; }
@@ -91,7 +91,7 @@ int main(int argc, char** argv) {
   CK(hipStreamSynchronize(st));
   float ms = 0.f;
   CK(hipEventElapsedTime(&ms, e0, e1));
-  printf("conv3x3_glds<%d, fused %d, GLDS_MFMA_STATS %d> %d -> %d channels, %d images: %.2f us per launch back to back (HIP events over %d launches)\n", W, PROBE_FUSED, GLDS_MFMA_STATS, C, N, imgs, ms * 1e3f / reps, reps);
+  printf("conv3x3_glds<%d, fused %d> %d -> %d channels, %d images: %.2f us per launch back to back (HIP events over %d launches)\n", W, PROBE_FUSED, C, N, imgs, ms * 1e3f / reps, reps);
   std::vector<unsigned long long> h((size_t)nwg * 16);
   CK(hipMemcpy(h.data(), dbg, h.size() * 8, hipMemcpyDeviceToHost));
   int used = 0;
