@@ -176,6 +176,11 @@ SIGNATURES = {
     "fedfr_topk_workspace_bytes": (sz, [sz, i32]),
     "fedfr_topk_sparsify": (i32, [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]),
     "fedfr_sparse_aggregate": (i32, [vp, vp, vp, vp, vp, vp, i32, sz, i32, vp]),
+    "fedfr_upload_sqnorm_workspace_bytes": (sz, [i32, sz]),
+    "fedfr_delta_sqnorm": (i32, [vp, vp, vp, i32, i32, sz, f32, vp, vp, vp, sz, vp]),
+    "fedfr_sparse_sqnorm": (i32, [vp, vp, vp, vp, i32, sz, f32, vp, vp, vp, vp, sz, vp]),
+    "fedfr_delta_aggregate_dp": (i32, [vp, vp, vp, vp, vp, i32, i32, sz, i32, i32, f32, u64, u64, u32, u64, vp]),
+    "fedfr_sparse_aggregate_dp": (i32, [vp, vp, vp, vp, vp, vp, i32, sz, i32, i32, f32, u64, u64, u32, u64, vp]),
     "fedfr_pfc_rand": (i32, [vp, i32, u64, u64, vp]),
     "fedfr_pfc_localize": (i32, [vp, i32, i64, i32, vp, vp]),
     "fedfr_pfc_topk": (i32, [vp, i32, i32, vp, vp, vp]),

@@ -10,9 +10,13 @@ Two formats, both fixed in include/fedfr_hip.h, both with the residual of what w
   (``fedfr_topk_sparsify``, csrc/sparse.hip; ``server.FedSparse`` aggregates the uploads).
 
 The BN running statistics and ``num_batches_tracked`` counters travel uncompressed (69,786 values for iresnet100): they are statistics,
-not optimisation variables — the stance ``server.FedOpt`` takes.  Not provided: fp8 element types, quantising the kept values of a
-top-k upload, delta-coding its indices, and the RCCL path (an all-gather of eight 8.25-bit payloads moves about what the ring
-all-reduce of one fp32 state already moves, so ``server.fedavg_all_reduce`` gains nothing at world 8 and is left alone)."""
+not optimisation variables — the stance ``server.FedOpt`` takes.  The server can clip either kind of upload by its norm as it will be
+applied, and add the Gaussian mechanism's noise to the clipped sum (``server.UploadClip``, the ``clip`` / ``mech`` arguments of
+``server.FedCompressed`` / ``server.FedSparse``, ``clip_uploads`` in ``Server.train``); the client's residual still follows what was
+SENT, not what the clip let through.  Not provided: a clip on the client before quantisation, norms under secure aggregation (the masks
+hide them by design), fp8 element types, quantising the kept values of a top-k upload, delta-coding its indices, and the RCCL path (an
+all-gather of eight 8.25-bit payloads moves about what the ring all-reduce of one fp32 state already moves, so
+``server.fedavg_all_reduce`` gains nothing at world 8 and is left alone)."""
 from __future__ import annotations
 
 import math

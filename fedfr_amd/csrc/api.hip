@@ -974,6 +974,25 @@ int fedfr_sparse_aggregate(float* dst, const float* base, const unsigned* const*
                            int k, size_t n, int accumulate, void* stream) {
   return sparse_aggregate(dst, base, idx, val, keeps, ws, k, n, accumulate, ST(stream));
 }
+size_t fedfr_upload_sqnorm_workspace_bytes(int k, size_t n_or_max_keep) { return upload_sqnorm_ws_bytes(k, n_or_max_keep); }
+int fedfr_delta_sqnorm(const void* const* codes, const unsigned char* const* scales, const float* ws, int k, int bits, size_t n, float clip, double* sq,
+                       float* coef, void* workspace, size_t workspace_bytes, void* stream) {
+  return delta_sqnorm(codes, scales, ws, k, bits, n, clip, sq, coef, workspace, workspace_bytes, ST(stream));
+}
+int fedfr_sparse_sqnorm(const unsigned* const* idx, const float* const* val, const size_t* keeps, const float* ws, int k, size_t n, float clip,
+                        double* sq, float* coef, int* violations, void* workspace, size_t workspace_bytes, void* stream) {
+  return sparse_sqnorm(idx, val, keeps, ws, k, n, clip, sq, coef, violations, workspace, workspace_bytes, ST(stream));
+}
+int fedfr_delta_aggregate_dp(float* dst, const float* base, const void* const* codes, const unsigned char* const* scales, const float* coef, int k,
+                             int bits, size_t n, int accumulate, int last, float noise_std, unsigned long long seed, unsigned long long round,
+                             unsigned stream_id, unsigned long long offset, void* stream) {
+  return delta_aggregate_dp(dst, base, codes, scales, coef, k, bits, n, accumulate, last, noise_std, seed, round, stream_id, offset, ST(stream));
+}
+int fedfr_sparse_aggregate_dp(float* dst, const float* base, const unsigned* const* idx, const float* const* val, const size_t* keeps, const float* coef,
+                              int k, size_t n, int accumulate, int last, float noise_std, unsigned long long seed, unsigned long long round,
+                              unsigned stream_id, unsigned long long offset, void* stream) {
+  return sparse_aggregate_dp(dst, base, idx, val, keeps, coef, k, n, accumulate, last, noise_std, seed, round, stream_id, offset, ST(stream));
+}
 int fedfr_pfc_rand(float* perm, int n, unsigned long long seed, unsigned long long step, void* stream) {
   return optim_pfc_rand(perm, n, seed, step, ST(stream));
 }

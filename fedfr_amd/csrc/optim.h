@@ -9,6 +9,10 @@ int optim_fedavg_multi(float* dst, const float* const* srcs, const float* ws, in
 size_t optim_fedopt_sqnorm_ws_bytes(int k, size_t n);
 int optim_fedopt_sqnorm(const float* x, const float* const* xs, const float* ws, int k, size_t n, float clip, double* sq, float* coef,
                         void* workspace, size_t ws_bytes, hipStream_t st);
+// the last step of every squared-norm pass (fedopt_sqnorm_final_kernel, launched here and nowhere else): sq_i = the `grid` fp64 partials of row
+// i of `part` in ascending order, coef_i = ws[i] min(1, clip / sqrt(sq_i)) in fp64, rounded once.  The callers (optim_fedopt_sqnorm,
+// compress.hip: delta_sqnorm, sparse.hip: sparse_sqnorm) have checked the arguments
+int optim_fedopt_sqnorm_final(const double* part, int grid, int k, const float* ws, float clip, double* sq, float* coef, hipStream_t st);
 int optim_fedopt_multi(int kind, float* x_out, const float* x, const float* const* xs, const float* coef, int k, size_t n, float* m, float* v,
                        float* scratch, int first, int last, float lr, float beta1, float one_minus_beta1, float beta2, float one_minus_beta2,
                        float tau, hipStream_t st);

@@ -246,6 +246,14 @@ __global__ __launch_bounds__(512) void fedopt_sqnorm_final_kernel(const double* 
   }
   coef[i] = (float)c;
 }
+// THE launch of that kernel, for every squared-norm pass of the library (optim.h)
+int optim_fedopt_sqnorm_final(const double* part, int grid, int k, const float* ws, float clip, double* sq, float* coef, hipStream_t st) {
+  StateWeights wt{};
+  for (int i = 0; i < k; ++i) wt.w[i] = ws[i];
+  hipLaunchKernelGGL(fedopt_sqnorm_final_kernel, dim3(1), dim3(512), 0, st, part, grid, k, wt, clip, sq, coef);
+  FEDFR_LAUNCH_CHECK("fedopt_sqnorm_final");
+  return FEDFR_OK;
+}
 size_t optim_fedopt_sqnorm_ws_bytes(int k, size_t n) {
   if (k < 1 || k > 8 || n == 0) return 0;
   return (size_t)k * multi_state_grid(n) * sizeof(double);
@@ -255,10 +263,8 @@ int optim_fedopt_sqnorm(const float* x, const float* const* xs, const float* ws,
   FEDFR_REQUIRE(x && xs && ws && sq && coef && wsp && n > 0 && k >= 1 && k <= 8, "fedopt_sqnorm: bad args (k=%d)", k);
   FEDFR_REQUIRE(clip == clip, "fedopt_sqnorm: clip is NaN");
   StatePtrs<8> p{};
-  StateWeights wt{};
   uintptr_t al = (uintptr_t)x;
   FEDFR_TRY(state_ptrs_fill(p, xs, k, "fedopt_sqnorm", "client state", al));
-  for (int i = 0; i < k; ++i) wt.w[i] = ws[i];
   FEDFR_REQUIRE((al & 15) == 0, "fedopt_sqnorm: parameter buffers must be 16-byte aligned");
   FEDFR_REQUIRE((((uintptr_t)sq | (uintptr_t)wsp) & 7) == 0 && ((uintptr_t)coef & 3) == 0, "fedopt_sqnorm: sq / workspace must be 8-byte, coef 4-byte aligned");
   const int grid = multi_state_grid(n);
@@ -271,9 +277,7 @@ int optim_fedopt_sqnorm(const float* x, const float* const* xs, const float* ws,
     hipLaunchKernelGGL(fedopt_sqnorm_kernel<decltype(kc)::value>, dim3(grid), dim3(MULTI_STATE_BLOCK), 0, st, x, p, n, part);
   });
   FEDFR_LAUNCH_CHECK("fedopt_sqnorm");
-  hipLaunchKernelGGL(fedopt_sqnorm_final_kernel, dim3(1), dim3(512), 0, st, part, grid, k, wt, clip, sq, coef);
-  FEDFR_LAUNCH_CHECK("fedopt_sqnorm_final");
-  return FEDFR_OK;
+  return optim_fedopt_sqnorm_final(part, grid, k, ws, clip, sq, coef, st);
 }
 
 // the pass without noise: fedopt_pass (fedopt_step.h; first / last / scratch and the aliasing rules: see there)

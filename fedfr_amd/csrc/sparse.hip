@@ -14,7 +14,10 @@
 // LANE MAPPING (as compress.hip).  A lane owns 8 consecutive elements (two 16-byte accesses), a wave 512, a workgroup of 4 waves one TILE of
 // 2048; workgroups take tiles grid-stride.  The last, partial tile goes through the same code with guarded 4-byte accesses.
 #include "sparse.h"
+#include "dp.h"            // DpStream, dp_gauss4: the noise of fedfr_sparse_aggregate_dp's last pass
 #include "multi_state.h"
+#include "optim.h"         // optim_fedopt_sqnorm_final: the last step of the norm pass
+#include <cmath>
 
 constexpr int TOPK_EPT = 8;                               // elements per lane
 constexpr int TOPK_WAVE = 64 * TOPK_EPT;                  // elements per wave
@@ -422,8 +425,13 @@ struct SparseUploads {
   float w[8];
 };
 
-template <int K>
-__global__ __launch_bounds__(MULTI_STATE_BLOCK) void sparse_aggregate_kernel(float* dst, const float* base, SparseUploads up, unsigned n, int accumulate) {
+// The body, written ONCE for the two shells below it: wt[] are the K weights wherever they came from (up.w is not read here); with NOISE,
+// noise_std z of the stream rs is added to EVERY element of the tile before base (the host selects NOISE only for the last pass of a chain
+// with noise_std > 0).  A thread's float4 at element ts + pos is Philox block (ts + pos) / 4 of the buffer: the value depends on the
+// element's index alone.
+template <int K, bool NOISE>
+__device__ __forceinline__ void sparse_aggregate_body(float* dst, const float* base, const SparseUploads& up, const float (&wt)[K], unsigned n, int accumulate,
+                                                      float noise_std, const DpStream& rs) {
   __shared__ float s[SAGG_TILE];
   __shared__ unsigned start[8];
   __shared__ unsigned wc[2][TOPK_WPB];
@@ -490,7 +498,7 @@ __global__ __launch_bounds__(MULTI_STATE_BLOCK) void sparse_aggregate_kernel(flo
       bool more;
       do {
         const bool inr = ix >= ts && ix < te;      // (the filler 0xFFFFFFFF is never inside: te <= n < 2^31)
-        if (inr) s[ix - ts] = __fadd_rn(s[ix - ts], __fmul_rn(up.w[i], vv));
+        if (inr) s[ix - ts] = __fadd_rn(s[ix - ts], __fmul_rn(wt[i], vv));
         const unsigned long long m = __ballot(inr);
         if (lane == 0) wc[par][w] = (unsigned)__popcll(m);
         __syncthreads();
@@ -511,6 +519,19 @@ __global__ __launch_bounds__(MULTI_STATE_BLOCK) void sparse_aggregate_kernel(flo
     fvec<4> o[SAGG_PER];
 #pragma unroll
     for (int q = 0; q < SAGG_PER; ++q) o[q] = *reinterpret_cast<const fvec<4>*>(&s[(q * MULTI_STATE_BLOCK + tid) * 4]);
+    if (NOISE) {
+#pragma unroll
+      for (int q = 0; q < SAGG_PER; ++q) {
+        const unsigned e = ts + (unsigned)(q * MULTI_STATE_BLOCK + tid) * 4;
+        if (e < te) {      // (a float4 that lies behind n altogether is never stored)
+          const float4 z = dp_gauss4(rs, e / 4);
+          o[q][0] = __fadd_rn(o[q][0], __fmul_rn(noise_std, z.x));
+          o[q][1] = __fadd_rn(o[q][1], __fmul_rn(noise_std, z.y));
+          o[q][2] = __fadd_rn(o[q][2], __fmul_rn(noise_std, z.z));
+          o[q][3] = __fadd_rn(o[q][3], __fmul_rn(noise_std, z.w));
+        }
+      }
+    }
     if (base) {
       fvec<4> b[SAGG_PER];
 #pragma unroll
@@ -543,24 +564,138 @@ __global__ __launch_bounds__(MULTI_STATE_BLOCK) void sparse_aggregate_kernel(flo
   }
 }
 
+// the shell of fedfr_sparse_aggregate: the weights travel by value, inside `up`
+template <int K>
+__global__ __launch_bounds__(MULTI_STATE_BLOCK) void sparse_aggregate_kernel(float* dst, const float* base, SparseUploads up, unsigned n, int accumulate) {
+  float w[K];
+#pragma unroll
+  for (int i = 0; i < K; ++i) w[i] = up.w[i];
+  sparse_aggregate_body<K, false>(dst, base, up, w, n, accumulate, 0.f, DpStream{});
+}
+// the shell of fedfr_sparse_aggregate_dp: the weights are what a norm pass left on the device, read once per thread
+template <int K, bool NOISE>
+__global__ __launch_bounds__(MULTI_STATE_BLOCK) void sparse_aggregate_dp_kernel(float* dst, const float* base, SparseUploads up, const float* __restrict__ coef, unsigned n,
+                                                                                int accumulate, float noise_std, DpStream rs) {
+  float w[K];
+#pragma unroll
+  for (int i = 0; i < K; ++i) w[i] = coef[i];
+  sparse_aggregate_body<K, NOISE>(dst, base, up, w, n, accumulate, noise_std, rs);
+}
+
+// what both aggregates and the norm pass check of their uploads, and fill; `w` (the weights, `wname`) may be a device pointer: not read here
+static int sparse_uploads_fill(const char* who, const char* wname, SparseUploads& up, uintptr_t& al, const unsigned* const* idx, const float* const* val,
+                               const size_t* keeps, const float* w, int k, size_t n) {
+  FEDFR_REQUIRE(k >= 1 && k <= 8, "%s: 1 to 8 uploads per call (k=%d)", who, k);
+  FEDFR_REQUIRE(idx && val && keeps && w, "%s: null pointer (idx=%p val=%p keeps=%p %s=%p)", who, (const void*)idx, (const void*)val, (const void*)keeps, wname,
+                (const void*)w);
+  FEDFR_REQUIRE(n < ((size_t)1 << 31), "%s: n must be below 2^31 (n=%zu)", who, n);
+  for (int i = 0; i < k; ++i) {
+    FEDFR_REQUIRE(idx[i] != nullptr, "%s: index buffer %d is null", who, i);
+    FEDFR_REQUIRE(val[i] != nullptr, "%s: value buffer %d is null", who, i);
+    FEDFR_REQUIRE(keeps[i] <= n, "%s: upload %d holds more entries than there are elements (keep=%zu n=%zu)", who, i, keeps[i], n);
+    up.idx[i] = idx[i];
+    up.val[i] = val[i];
+    up.keep[i] = (unsigned)keeps[i];
+    al |= (uintptr_t)idx[i] | (uintptr_t)val[i];
+  }
+  return FEDFR_OK;
+}
+
+int sparse_aggregate_dp(float* dst, const float* base, const unsigned* const* idx, const float* const* val, const size_t* keeps, const float* coef,
+                        int k, size_t n, int accumulate, int last, float noise_std, unsigned long long seed, unsigned long long round,
+                        unsigned stream_id, unsigned long long offset, hipStream_t st) {
+  SparseUploads up{};
+  uintptr_t al = 0;
+  FEDFR_REQUIRE(dst, "sparse_aggregate_dp: null pointer (dst=%p)", (void*)dst);
+  FEDFR_TRY(sparse_uploads_fill("sparse_aggregate_dp", "coef", up, al, idx, val, keeps, coef, k, n));
+  FEDFR_REQUIRE((((uintptr_t)dst | (uintptr_t)base | al) & 15) == 0, "sparse_aggregate_dp: dst, base and the index and value buffers must be 16-byte aligned");
+  FEDFR_REQUIRE(((uintptr_t)coef & 3) == 0, "sparse_aggregate_dp: coef must be 4-byte aligned");
+  FEDFR_REQUIRE(std::isfinite(noise_std) && noise_std >= 0.f, "sparse_aggregate_dp: noise_std must be finite and >= 0 (got %g)", (double)noise_std);
+  FEDFR_REQUIRE(offset % 4 == 0, "sparse_aggregate_dp: offset %llu is not a multiple of 4", offset);
+  if (n == 0) return FEDFR_OK;
+  accumulate = accumulate ? 1 : 0;
+  const size_t ntiles = (n + SAGG_TILE - 1) / SAGG_TILE;
+  const int grid = (int)(ntiles > TOPK_GRID_CAP ? TOPK_GRID_CAP : ntiles);
+  const DpStream rs = dp_stream(seed, round, stream_id, offset);
+  dispatch_int<0, 1>(last && noise_std > 0.f ? 1 : 0, [&](auto nc) {
+    dispatch_int<1, 8>(k, [&](auto kc) {
+      hipLaunchKernelGGL((sparse_aggregate_dp_kernel<decltype(kc)::value, decltype(nc)::value != 0>), dim3(grid), dim3(MULTI_STATE_BLOCK), 0, st, dst, base, up, coef,
+                         (unsigned)n, accumulate, noise_std, rs);
+    });
+  });
+  FEDFR_LAUNCH_CHECK("sparse_aggregate_dp");
+  return FEDFR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// squared norms of <= 8 top-k uploads: sq_i = sum_e double(val_e)^2 (the square of an fp32 value is exact in fp64: fma(v, v, acc) rounds
+// once), one entry per thread and step, grid-stride, on the launch rule of compress.hip's norm pass for m = the largest keep; then
+// block_partial_d and fedopt_sqnorm_final_kernel (optim.hip): the fixed order of fedopt_sqnorm, no float atomics, every partial written by
+// its block.  The scattered vector has norm sqrt(sq_i) only if the indices are distinct and inside n: an entry with idx_e >= n or
+// idx_e <= idx_(e-1) is a violation, counted per upload (an integer sum: one atomic per wave that found any).
+// ---------------------------------------------------------------------------------------------------------
+template <int K>
+__global__ __launch_bounds__(MULTI_STATE_BLOCK) void sparse_sqnorm_kernel(SparseUploads up, unsigned n, double* __restrict__ part, int* __restrict__ violations) {
+  __shared__ double red[4][8];
+  double acc[K];
+  unsigned bad[K];
+  const size_t stride = (size_t)gridDim.x * blockDim.x, t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+#pragma unroll
+  for (int i = 0; i < K; ++i) {
+    acc[i] = 0.0;
+    bad[i] = 0u;
+    const unsigned keep = up.keep[i];
+    for (size_t e = t; e < keep; e += stride) {
+      const double v = (double)__builtin_nontemporal_load(up.val[i] + e);
+      acc[i] = __fma_rn(v, v, acc[i]);
+      const unsigned ix = up.idx[i][e];
+      bad[i] += (ix >= n || (e > 0 && ix <= up.idx[i][e - 1])) ? 1u : 0u;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < K; ++i) {
+    const unsigned b = wave_sum_u(bad[i]);
+    if ((threadIdx.x & 63) == 0 && b) atomicAdd(&violations[i], (int)b);
+  }
+  block_partial_d<K>(acc, red, part, [](int i) { return i; });
+}
+
+int sparse_sqnorm(const unsigned* const* idx, const float* const* val, const size_t* keeps, const float* ws, int k, size_t n, float clip, double* sq,
+                  float* coef, int* violations, void* wsp, size_t ws_bytes, hipStream_t st) {
+  SparseUploads up{};
+  uintptr_t al = 0;
+  FEDFR_REQUIRE(sq && coef && violations && wsp, "sparse_sqnorm: null pointer (sq=%p coef=%p violations=%p workspace=%p)", (void*)sq, (void*)coef, (void*)violations,
+                wsp);
+  FEDFR_TRY(sparse_uploads_fill("sparse_sqnorm", "ws", up, al, idx, val, keeps, ws, k, n));
+  FEDFR_REQUIRE(n > 0, "sparse_sqnorm: n must be positive");
+  FEDFR_REQUIRE(clip == clip, "sparse_sqnorm: clip is NaN");
+  FEDFR_REQUIRE((al & 15) == 0, "sparse_sqnorm: the index and value buffers must be 16-byte aligned");
+  FEDFR_REQUIRE((((uintptr_t)sq | (uintptr_t)wsp) & 7) == 0 && (((uintptr_t)coef | (uintptr_t)violations) & 3) == 0,
+                "sparse_sqnorm: sq / workspace must be 8-byte, coef / violations 4-byte aligned");
+  size_t m = 0;
+  for (int i = 0; i < k; ++i) m = keeps[i] > m ? keeps[i] : m;
+  const int grid = multi_state_grid_per<TOPK_EPT>(m);
+  if (ws_bytes < (size_t)k * grid * sizeof(double)) {
+    fedfr_set_error("sparse_sqnorm: workspace of %zu bytes, %zu needed", ws_bytes, (size_t)k * grid * sizeof(double));
+    return FEDFR_ERR_WORKSPACE;
+  }
+  double* part = reinterpret_cast<double*>(wsp);
+  dispatch_int<1, 8>(k, [&](auto kc) {
+    hipLaunchKernelGGL((sparse_sqnorm_kernel<decltype(kc)::value>), dim3(grid), dim3(MULTI_STATE_BLOCK), 0, st, up, (unsigned)n, part, violations);
+  });
+  FEDFR_LAUNCH_CHECK("sparse_sqnorm");
+  return optim_fedopt_sqnorm_final(part, grid, k, ws, clip, sq, coef, st);
+}
+
 int sparse_aggregate(float* dst, const float* base, const unsigned* const* idx, const float* const* val, const size_t* keeps, const float* ws, int k,
                      size_t n, int accumulate, hipStream_t st) {
   FEDFR_REQUIRE(k >= 1 && k <= 8, "sparse_aggregate: 1 to 8 uploads per call (k=%d)", k);
   FEDFR_REQUIRE(dst && idx && val && keeps && ws, "sparse_aggregate: null pointer (dst=%p idx=%p val=%p keeps=%p ws=%p)", (void*)dst, (const void*)idx,
                 (const void*)val, (const void*)keeps, (const void*)ws);
-  FEDFR_REQUIRE(n < ((size_t)1 << 31), "sparse_aggregate: n must be below 2^31 (n=%zu)", n);
   SparseUploads up{};
   uintptr_t al = 0;
-  for (int i = 0; i < k; ++i) {
-    FEDFR_REQUIRE(idx[i] != nullptr, "sparse_aggregate: index buffer %d is null", i);
-    FEDFR_REQUIRE(val[i] != nullptr, "sparse_aggregate: value buffer %d is null", i);
-    FEDFR_REQUIRE(keeps[i] <= n, "sparse_aggregate: upload %d holds more entries than there are elements (keep=%zu n=%zu)", i, keeps[i], n);
-    up.idx[i] = idx[i];
-    up.val[i] = val[i];
-    up.keep[i] = (unsigned)keeps[i];
-    up.w[i] = ws[i];
-    al |= (uintptr_t)idx[i] | (uintptr_t)val[i];
-  }
+  FEDFR_TRY(sparse_uploads_fill("sparse_aggregate", "ws", up, al, idx, val, keeps, ws, k, n));
+  for (int i = 0; i < k; ++i) up.w[i] = ws[i];
   FEDFR_REQUIRE((((uintptr_t)dst | (uintptr_t)base | al) & 15) == 0, "sparse_aggregate: dst, base and the index and value buffers must be 16-byte aligned");
   if (n == 0) return FEDFR_OK;
   accumulate = accumulate ? 1 : 0;

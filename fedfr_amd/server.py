@@ -5,6 +5,7 @@ xGMI when every client is its own rank (one client = one MI355X); the spread-out
 checkpoints (reference server.py:135-148).  Build extensions beyond the reference's FedAvg, one module-level round function each: the
 server optimisers (``FedOpt``), the robust rules (``FedRobust``), client-level differential privacy (``FedDP``; privacy.py), and the
 rounds from UPLOADS instead of states: 8 / 4-bit and top-k deltas with error feedback (``FedCompressed``, ``FedSparse``; compress.py),
+optionally clipped by their norm as the server applies them and noised by the Gaussian mechanism (``UploadClip``),
 pairwise-masked fixed-point updates (``FedSecAgg``; secagg.py) and those with the clients' own clip and discrete Gaussian noise
 (``FedSecAggDP``).  What these share exists once: the chained delta step (``ServerOptimizer._chain``), the head, the tail and the masked
 sum of a round from uploads (``_upload_round_head``, ``_upload_round_tail``, ``_masked_sum``).  ``Server.train`` runs a round in four
@@ -445,11 +446,13 @@ class _StatsOnly:
         self.flat = (None, stats, counters)
 
 
-def _upload_round_head(what, global_state, uploads, is_upload, noun, expected, weights, server_opt, robust_why, clip_refusal):
+def _upload_round_head(what, global_state, uploads, is_upload, noun, expected, weights, server_opt, robust_why, clip_refusal, clip=None, mech=None):
     """What every round from uploads refuses, in this order: a global state that is no FlatStateDict with its flat buffers; uploads that
     are empty or not all ``is_upload`` (``noun``: "updates" / "uploads", ``expected``: what they must be); another number of ``weights``
     (None: the round takes none); a robust rule (``robust_why``); a server optimiser that clips (``clip_refusal``: the sentence that says
-    why not); global parameters off the GPU.  Returns those parameters and the weights, normalised (``weights`` None: uniform)."""
+    why not) unless ``clip`` (an ``UploadClip``) measures the uploads at the optimiser's own clip_norm; a ``clip`` that is no
+    ``UploadClip`` or clips elsewhere than the optimiser; a ``mech`` without ``clip``, or whose sensitivity bound is another clip_norm;
+    global parameters off the GPU.  Returns those parameters and the weights, normalised (``weights`` None: uniform)."""
     if not isinstance(global_state, FlatStateDict) or global_state.flat is None:
         raise RuntimeError("fedfr_amd.%s: the global state must be a FlatStateDict (client.flat_state_dict)" % what)
     if not uploads or not all(is_upload(u) for u in uploads):
@@ -458,11 +461,78 @@ def _upload_round_head(what, global_state, uploads, is_upload, noun, expected, w
         raise RuntimeError("fedfr_amd.%s: %d weights for %d client %s" % (what, len(weights), len(uploads), noun))
     if isinstance(server_opt, RobustAggregator):
         raise ValueError("%s: a robust rule (%s) needs whole client states, %s" % (what, server_opt.kind, robust_why))
-    if server_opt is not None and server_opt.clip_norm > 0:
+    if server_opt is not None and server_opt.clip_norm > 0 and clip is None:
         raise ValueError("%s: %s" % (what, clip_refusal))
+    if clip is not None:
+        if not isinstance(clip, UploadClip):
+            raise ValueError("%s: clip must be a server.UploadClip (got %r)" % (what, clip))
+        if server_opt is not None and server_opt.clip_norm > 0 and np.float32(server_opt.clip_norm) != np.float32(clip.clip_norm):
+            raise ValueError("%s: the server optimiser clips at %r, the uploads are clipped at clip_norm=%r" % (what, server_opt.clip_norm, clip.clip_norm))
+    if mech is not None:
+        if clip is None:
+            raise ValueError("%s: mech needs clip: the clip of the uploads is the sensitivity bound of the mechanism" % what)
+        if np.float32(clip.clip_norm) != np.float32(mech.clip_norm):
+            raise ValueError("%s: the uploads are clipped at %r, the mechanism's sensitivity bound is clip_norm=%r" % (what, clip.clip_norm, mech.clip_norm))
     x = global_state.flat[0]
     _check_states(x, [], what)
     return x, _normalised(weights if weights is not None else [1.0] * len(uploads))
+
+
+class UploadClip:
+    """The clip of a round from compressed or top-k uploads: what ``ServerOptimizer.coefficients`` is for fp32 states.  ``clip_norm`` > 0
+    scales an upload whose norm AS THE SERVER WILL APPLY IT (the dequantised codes, the scattered entries) exceeds it down to that norm.
+    One pass over <= 8 uploads at a time that reads their bytes once and no fp32 state (fedfr_delta_sqnorm, fedfr_sparse_sqnorm), no host
+    synchronisation: after a call ``last_update_sqnorm`` (fp64), ``last_coef`` (fp32, w_i min(1, clip_norm / norm_i)) and, for top-k
+    uploads, ``last_violations`` (int32: entries whose index is out of range or not ascending, without which alone the norm is the
+    scattered vector's) hold one value per upload ON THE DEVICE; nothing reads them back unless the caller does.  Owns the workspace of
+    the norm pass."""
+
+    def __init__(self, clip_norm):
+        self.clip_norm = float(clip_norm)
+        if not self.clip_norm > 0.0:                   # (NaN fails the comparison too)
+            raise ValueError("UploadClip: clip_norm must be > 0 (got %r)" % (clip_norm,))
+        self._ws = _Workspace()
+        self.last_update_sqnorm = self.last_coef = self.last_violations = None
+
+    def _outputs(self, k: int, dev, violations: bool):
+        self.last_update_sqnorm = torch.zeros(k, dtype=torch.float64, device=dev)
+        self.last_coef = torch.empty(k, dtype=f32, device=dev)
+        self.last_violations = torch.zeros(k, dtype=torch.int32, device=dev) if violations else None
+        return self.last_update_sqnorm, self.last_coef, self.last_violations
+
+    def compressed(self, updates, ws: Sequence[float], bits: int, n: int, dev) -> torch.Tensor:
+        """coef as a DEVICE tensor for the ``compress.CompressedDelta``s ``updates`` (checked by the caller) at weights ``ws``"""
+        sq, coef, _ = self._outputs(len(updates), dev, False)
+        if n == 0:                                     # nothing to measure: sq = 0, coef = w
+            coef.copy_(torch.tensor([float(np.float32(w)) for w in ws], dtype=f32))
+            return coef
+        wsp = self._ws.ensure(int(_C.lib().fedfr_upload_sqnorm_workspace_bytes(min(8, len(updates)), n)), dev)
+        for c0 in range(0, len(updates), 8):
+            grp = updates[c0:c0 + 8]
+            _C.call("fedfr_delta_sqnorm", _C.ptr_array([u.codes for u in grp]), _C.ptr_array([u.scales for u in grp]), _f32_vector(ws[c0:c0 + 8]), len(grp),
+                    bits, n, float(np.float32(self.clip_norm)), sq.data_ptr() + 8 * c0, coef.data_ptr() + 4 * c0, *wsp, _C.stream())
+        return coef
+
+    def sparse(self, updates, ws: Sequence[float], n: int, dev) -> torch.Tensor:
+        """coef as a DEVICE tensor for the ``compress.SparseDelta``s ``updates`` (checked by the caller) at weights ``ws``"""
+        sq, coef, viol = self._outputs(len(updates), dev, True)
+        if n == 0:
+            coef.copy_(torch.tensor([float(np.float32(w)) for w in ws], dtype=f32))
+            return coef
+        wsp = self._ws.ensure(int(_C.lib().fedfr_upload_sqnorm_workspace_bytes(min(8, len(updates)), max(u.keep for u in updates))), dev)
+        for c0 in range(0, len(updates), 8):
+            grp = updates[c0:c0 + 8]
+            keeps = (ctypes.c_size_t * len(grp))(*[u.keep for u in grp])
+            _C.call("fedfr_sparse_sqnorm", _C.ptr_array([u.idx for u in grp]), _C.ptr_array([u.val for u in grp]), keeps, _f32_vector(ws[c0:c0 + 8]), len(grp),
+                    n, float(np.float32(self.clip_norm)), sq.data_ptr() + 8 * c0, coef.data_ptr() + 4 * c0, viol.data_ptr() + 4 * c0, *wsp, _C.stream())
+        return coef
+
+
+def _upload_noise(mech, ws):
+    """(noise_std, seed, round, stream_id, offset) of a chain of ``_dp`` aggregates: ``mech``'s stream at its current round, or no noise"""
+    if mech is None:
+        return (0.0, 0, 0, 0, 0)
+    return (mech.noise_std([float(np.float32(w)) for w in ws]), mech.seed, mech.round, mech.stream_id, 0)
 
 
 def _upload_round_tail(global_state, P: torch.Tensor, x: torch.Tensor, uploads, ws: Sequence[float], server_opt):
@@ -475,7 +545,7 @@ def _upload_round_tail(global_state, P: torch.Tensor, x: torch.Tensor, uploads, 
     return FlatStateDict.from_flat((P, *stats), global_state.table, global_state.layers)
 
 
-def FedCompressed(global_state, updates, weights: Sequence[float], server_opt=None):
+def FedCompressed(global_state, updates, weights: Sequence[float], server_opt=None, *, clip=None, mech=None):
     """One round from compressed uploads (``compress.CompressedDelta``, all of one width): the PARAMETERS of the new global state are
     x + Σ_i (n_i/Σn)·dq_i with x = ``global_state``'s parameters and dq_i the dequantised upload of client i (fedfr_delta_aggregate: ≤ 8
     uploads per pass, every code and scale byte read once; more clients chain passes with ``accumulate``, and x is added by the last pass
@@ -483,12 +553,17 @@ def FedCompressed(global_state, updates, weights: Sequence[float], server_opt=No
     pseudo-gradient Δ and goes through ``server_opt.apply_delta``; ``clip_norm`` > 0 raises ``ValueError`` (the clip needs per-client norms
     of the dequantised deltas: not provided).  BN running statistics and ``num_batches_tracked`` arrive uncompressed and are averaged
     exactly as ``FedPavg`` averages them.  A block a client sent as non-finite is NaN in the result, as it would be with fp32 uploads.
-    Only a GPU ``FlatStateDict`` is accepted as ``global_state``."""
+    Only a GPU ``FlatStateDict`` is accepted as ``global_state``.
+    ``clip`` (an ``UploadClip``): the weights become c_i = (n_i/Σn) min(1, clip_norm / ||dq_i||), formed on the device from the codes
+    and scale bytes (fedfr_delta_sqnorm) and read from there by the same chain (fedfr_delta_aggregate_dp); a ``server_opt`` that clips
+    must clip at the same norm.  ``mech`` (a ``privacy.GaussianMechanism`` of that clip_norm; needs ``clip``): the last pass adds
+    ``mech.noise_std(w)`` z of the mechanism's stream at its current round to the sum before x (or before ``server_opt``'s step), and the
+    round counter advances by one.  BN running statistics and counters stay outside the clip and the mechanism."""
     from .compress import CompressedDelta
     x, ws = _upload_round_head("FedCompressed", global_state, updates, lambda u: isinstance(u, CompressedDelta), "updates",
                                "CompressedDeltas (Client.get_compressed_update)", weights, server_opt, "not compressed uploads",
                                "clip_norm > 0 needs per-client norms of the dequantised deltas, which compressed uploads do not provide; use "
-                               "FedOpt on uncompressed states")
+                               "FedOpt on uncompressed states", clip, mech)
     n, bits = x.numel(), updates[0].bits
     lib = _C.lib()
     for u in updates:
@@ -503,8 +578,17 @@ def FedCompressed(global_state, updates, weights: Sequence[float], server_opt=No
         grp = updates[c0:c0 + 8]
         last = c0 + 8 >= len(updates)
         if n:
-            _C.call("fedfr_delta_aggregate", P.data_ptr(), x.data_ptr() if last and server_opt is None else None, _C.ptr_array([u.codes for u in grp]),
-                    _C.ptr_array([u.scales for u in grp]), _f32_vector(ws[c0:c0 + 8]), len(grp), bits, n, 1 if c0 > 0 else 0, _C.stream())
+            base = x.data_ptr() if last and server_opt is None else None
+            if clip is None:
+                _C.call("fedfr_delta_aggregate", P.data_ptr(), base, _C.ptr_array([u.codes for u in grp]), _C.ptr_array([u.scales for u in grp]),
+                        _f32_vector(ws[c0:c0 + 8]), len(grp), bits, n, 1 if c0 > 0 else 0, _C.stream())
+            else:
+                if c0 == 0:
+                    coef, noise = clip.compressed(updates, ws, bits, n, x.device), _upload_noise(mech, ws)
+                _C.call("fedfr_delta_aggregate_dp", P.data_ptr(), base, _C.ptr_array([u.codes for u in grp]), _C.ptr_array([u.scales for u in grp]),
+                        coef.data_ptr() + 4 * c0, len(grp), bits, n, 1 if c0 > 0 else 0, 1 if last else 0, *noise, _C.stream())
+    if mech is not None:
+        mech.advance()
     return _upload_round_tail(global_state, P, x, updates, ws, server_opt)
 
 
@@ -590,7 +674,7 @@ def FedSecAggDP(global_state, uploads, recovery_streams, mech, server_opt=None):
 
 
 # ---- top-k uploads: csrc/sparse.hip topk_* kernels (client side, compress.py) / sparse_aggregate_kernel
-def FedSparse(global_state, updates, weights: Sequence[float], server_opt=None):
+def FedSparse(global_state, updates, weights: Sequence[float], server_opt=None, *, clip=None, mech=None):
     """One round from top-k uploads (``compress.SparseDelta``): the PARAMETERS of the new global state are x + Σ_i (n_i/Σn)·sparse_i with
     x = ``global_state``'s parameters and sparse_i the scattered upload of client i (fedfr_sparse_aggregate: ≤ 8 uploads per pass, x read
     and the result written once, no float atomics; the sorted entries are walked 256 at a time, so an entry is loaded again for every
@@ -599,12 +683,16 @@ def FedSparse(global_state, updates, weights: Sequence[float], server_opt=None):
     ``ServerOptimizer``) the same sum WITHOUT x is the pseudo-gradient Δ and goes through ``server_opt.apply_delta``; ``clip_norm`` > 0
     raises ``ValueError`` (the clip needs per-client norms of the deltas: not provided).  BN running statistics and
     ``num_batches_tracked`` arrive uncompressed and are averaged exactly as ``FedPavg`` averages them.  An element a client sent as
-    non-finite is NaN in the result, as it would be with fp32 uploads.  Only a GPU ``FlatStateDict`` is accepted as ``global_state``."""
+    non-finite is NaN in the result, as it would be with fp32 uploads.  Only a GPU ``FlatStateDict`` is accepted as ``global_state``.
+    ``clip`` (an ``UploadClip``) and ``mech`` (a ``privacy.GaussianMechanism``): as in ``FedCompressed``, through fedfr_sparse_sqnorm and
+    fedfr_sparse_aggregate_dp.  The noise is dense: every parameter receives it, not only the ones an upload touches.  The norm is the
+    scattered vector's only if no entry breaks the format: ``clip.last_violations`` counts those per upload, and a caller who relies on
+    the bound must read it (``Server.train`` does, and voids the round)."""
     from .compress import SparseDelta
     x, ws = _upload_round_head("FedSparse", global_state, updates, lambda u: isinstance(u, SparseDelta), "updates",
                                "SparseDeltas (Client.get_sparse_update)", weights, server_opt, "not top-k uploads",
                                "clip_norm > 0 needs per-client norms of the deltas, which top-k uploads do not provide; use FedOpt on uncompressed "
-                               "states")
+                               "states", clip, mech)
     n = x.numel()
     for u in updates:
         if u.n != n:
@@ -621,8 +709,17 @@ def FedSparse(global_state, updates, weights: Sequence[float], server_opt=None):
         last = c0 + 8 >= len(updates)
         keeps = (ctypes.c_size_t * len(grp))(*[u.keep for u in grp])
         if n:
-            _C.call("fedfr_sparse_aggregate", P.data_ptr(), x.data_ptr() if last and server_opt is None else None, _C.ptr_array([u.idx for u in grp]),
-                    _C.ptr_array([u.val for u in grp]), keeps, _f32_vector(ws[c0:c0 + 8]), len(grp), n, 1 if c0 > 0 else 0, _C.stream())
+            base = x.data_ptr() if last and server_opt is None else None
+            if clip is None:
+                _C.call("fedfr_sparse_aggregate", P.data_ptr(), base, _C.ptr_array([u.idx for u in grp]), _C.ptr_array([u.val for u in grp]), keeps,
+                        _f32_vector(ws[c0:c0 + 8]), len(grp), n, 1 if c0 > 0 else 0, _C.stream())
+            else:
+                if c0 == 0:
+                    coef, noise = clip.sparse(updates, ws, n, x.device), _upload_noise(mech, ws)
+                _C.call("fedfr_sparse_aggregate_dp", P.data_ptr(), base, _C.ptr_array([u.idx for u in grp]), _C.ptr_array([u.val for u in grp]), keeps,
+                        coef.data_ptr() + 4 * c0, len(grp), n, 1 if c0 > 0 else 0, 1 if last else 0, *noise, _C.stream())
+    if mech is not None:
+        mech.advance()
     return _upload_round_tail(global_state, P, x, updates, ws, server_opt)
 
 
@@ -782,6 +879,8 @@ class Server(object):
         self.robust_agg = None                       # RobustAggregator of aggr_alg TrimmedMean / CoordMedian / Krum / MultiKrum (built in train())
         self.dp_mech = self.dp_accountant = None     # privacy.GaussianMechanism / RDPAccountant of dp_noise_multiplier > 0 (built in train())
         self.dp_epsilon = None                       # the (epsilon, dp_delta) guarantee after the rounds aggregated so far
+        self.upload_clip = None                      # the UploadClip of clip_uploads (built in train()) and what the last round read of it
+        self.upload_sqnorms = self.upload_coefs = self.upload_violations = None
         self.dp_last_sqnorms = None                  # distributed_dp: the survivors' sums of squared codes of the last round (each <= delta_int^2)
         self.secagg_rng = None                       # n -> n random bytes for the secure-aggregation secrets (None: os.urandom)
 
@@ -854,11 +953,19 @@ class Server(object):
         topk_ratio = getattr(a, "topk_ratio", 0) or 0                        # top-k uploads (a build extension): absent or 0 = off
         secagg_on = bool(getattr(a, "secure_aggregation", False))            # secure aggregation (a build extension): absent or False = off
         return_all = bool(getattr(a, "return_all", False))
+        clip_uploads = bool(getattr(a, "clip_uploads", False))               # the clip (and DP noise) ON compressed / top-k uploads: absent or False = off
         dp_delta = ddp_mech = secagg_frac_bits = secagg_threshold = None     # (resolved below where their feature is on)
         secagg_drop = []
         if aggr_alg not in ("FedAvg", "FedProx") and aggr_alg not in AGGR_ALG_KINDS and aggr_alg not in ROBUST_ALG_KINDS:      # before a round of client training is spent on it
             raise ValueError("Server.train: unknown aggr_alg %r (FedAvg, FedProx, %s, %s)"
                              % (aggr_alg, ", ".join(AGGR_ALG_KINDS), ", ".join(sorted(ROBUST_ALG_KINDS))))
+        if clip_uploads:                                                     # what the setting itself cannot serve; the pairings follow below
+            if secagg_on:
+                raise ValueError("Server.train: clip_uploads cannot be combined with secure_aggregation: the clip needs per-client norms of the "
+                                 "uploads, which masks hide by design")
+            if not compress_bits and not topk_ratio:
+                raise ValueError("Server.train: clip_uploads needs compress_bits or topk_ratio: it clips compressed and top-k uploads; fp32 "
+                                 "states are clipped by clip_norm with a server optimiser or dp_noise_multiplier")
         if ddp_on:
             if not secagg_on:
                 raise ValueError("Server.train: distributed_dp needs secure_aggregation: the clients' noise shares protect only a sum that "
@@ -877,10 +984,10 @@ class Server(object):
             if aggr_alg in ROBUST_ALG_KINDS:
                 raise ValueError("Server.train: dp_noise_multiplier=%r cannot be combined with aggr_alg=%r: a robust rule provides no per-client "
                                  "norms to clip" % (dp_sigma, aggr_alg))
-            if compress_bits:
+            if compress_bits and not clip_uploads:
                 raise ValueError("Server.train: dp_noise_multiplier=%r cannot be combined with compress_bits=%d: the clip needs per-client norms "
                                  "of the dequantised deltas, which are not provided" % (dp_sigma, compress_bits))
-            if topk_ratio:
+            if topk_ratio and not clip_uploads:
                 raise ValueError("Server.train: dp_noise_multiplier=%r cannot be combined with topk_ratio=%r: the clip needs per-client norms of "
                                  "the deltas, which are not provided" % (dp_sigma, topk_ratio))
             if return_all:
@@ -903,7 +1010,7 @@ class Server(object):
             if aggr_alg in ROBUST_ALG_KINDS:
                 raise ValueError("Server.train: compress_bits=%d cannot be combined with aggr_alg=%r: a robust rule needs whole client states"
                                  % (compress_bits, aggr_alg))
-            if clip_norm > 0:
+            if clip_norm > 0 and not clip_uploads:
                 raise ValueError("Server.train: compress_bits=%d cannot be combined with clip_norm=%r: the clip needs per-client norms of the "
                                  "dequantised deltas, which are not provided" % (compress_bits, a.clip_norm))
         if topk_ratio:                                                       # the same: before anybody trains
@@ -918,7 +1025,7 @@ class Server(object):
             if aggr_alg in ROBUST_ALG_KINDS:
                 raise ValueError("Server.train: topk_ratio=%r cannot be combined with aggr_alg=%r: a robust rule needs whole client states"
                                  % (topk_ratio, aggr_alg))
-            if clip_norm > 0:
+            if clip_norm > 0 and not clip_uploads:
                 raise ValueError("Server.train: topk_ratio=%r cannot be combined with clip_norm=%r: the clip needs per-client norms of the "
                                  "deltas, which are not provided" % (topk_ratio, a.clip_norm))
         if secagg_on:                                                        # the same: before anybody trains
@@ -969,7 +1076,8 @@ class Server(object):
         return SimpleNamespace(aggr_alg=aggr_alg, dp_sigma=dp_sigma, clip_norm=clip_norm, dp_delta=dp_delta, ddp_on=ddp_on, ddp_mech=ddp_mech,
                                compress_bits=compress_bits, topk_ratio=topk_ratio, feedback=bool(getattr(a, "error_feedback", True)),
                                secagg_on=secagg_on, secagg_frac_bits=secagg_frac_bits, secagg_threshold=secagg_threshold, secagg_drop=secagg_drop,
-                               public=bool(getattr(a, "add_pretrained_data", False)), return_all=return_all)
+                               public=bool(getattr(a, "add_pretrained_data", False)), return_all=return_all,
+                               clip_uploads=clip_uploads and clip_norm > 0)
 
     def _train_clients(self, s) -> List[int]:
         """Stage 2: every client of ``current_client_list`` receives the global model and trains, one after another or
@@ -1076,13 +1184,28 @@ class Server(object):
         self.avg_loss = sum(losses_) / len(losses_)
         return up
 
-    def _report_uploads(self, label, uploads, tail, senders, counters, warning):
+    def _report_uploads(self, label, uploads, tail, senders, counters, warning, clip=None):
         """The log lines of a round from uploads: "``label``: N bytes from K clients, ... of the D bytes of fp32 states``tail``" over all
         ``uploads``; then ``counters`` (one small device tensor per aggregated upload, of the clients ``senders``) in ONE copy, the round's one
-        read of them, and ``warning`` % (client, the counters it names) where one of those is not 0.  Returns the counters as lists."""
+        read of them, and ``warning`` % (client, the counters it names) where one of those is not 0.  Returns the counters as lists.
+        With ``clip`` (the round's ``UploadClip``) the same copy brings its squared norms, coefficients and, for top-k, violation counts
+        (as fp64, which holds all of them exactly): they are logged per client and left on ``self.upload_sqnorms`` / ``upload_coefs`` /
+        ``upload_violations`` (None where the clip counts none)."""
         sent, dense = sum(u.nbytes for u in uploads), sum(u.dense_nbytes for u in uploads)
         self.logger.info('%s: %d bytes from %d clients, %.4f of the %d bytes of fp32 states%s' % (label, sent, len(uploads), sent / dense, dense, tail))
-        rows = torch.stack([c.reshape(-1) for c in counters]).cpu().tolist()
+        table = torch.stack([c.reshape(-1) for c in counters])
+        if clip is not None:
+            extra = [clip.last_update_sqnorm, clip.last_coef.double()] + ([] if clip.last_violations is None else [clip.last_violations.double()])
+            table = torch.cat([table.double(), torch.stack(extra, dim=1)], dim=1)
+        rows = table.cpu().tolist()
+        if clip is not None:
+            ncnt = counters[0].numel()
+            self.upload_sqnorms, self.upload_coefs = [r[ncnt] for r in rows], [r[ncnt + 1] for r in rows]
+            self.upload_violations = None if clip.last_violations is None else [int(r[ncnt + 2]) for r in rows]
+            rows = [[int(v) for v in r[:ncnt]] for r in rows]
+            for pos, i in enumerate(senders):
+                self.logger.info('Client %s: squared upload norm %.9g, coefficient %.9g (clip_norm %g)'
+                                 % (getattr(self.clients[i], "cid", i), self.upload_sqnorms[pos], self.upload_coefs[pos], clip.clip_norm))
         shown = warning.count('%d')
         for i, row in zip(senders, rows):
             if any(v > 0 for v in row[:shown]):
@@ -1100,14 +1223,21 @@ class Server(object):
                                               clip_norm=0.0 if s.ddp_on else getattr(a, "clip_norm", 0.0))      # (distributed DP: the clients clip)
         opt = self.server_opt if s.aggr_alg in AGGR_ALG_KINDS else None
         models, data_sizes, aggr_alg = up.models, up.data_sizes, s.aggr_alg
-        if s.compress_bits:
-            aggr_state_dict = FedCompressed(up.global_state, models, data_sizes, opt)
-            self._report_uploads('Compressed uploads (%d bits%s)' % (s.compress_bits, ", error feedback" if s.feedback else ""), models, '', order,
-                                 [u.nonfinite_blocks for u in models], 'Client %s sent %d non-finite blocks (NaN in the aggregate there)')
-        elif s.topk_ratio:
-            aggr_state_dict = FedSparse(up.global_state, models, data_sizes, opt)
-            self._report_uploads('Top-k uploads (ratio %g%s)' % (s.topk_ratio, ", error feedback" if s.feedback else ""), models, '', order,
-                                 [u.nonfinite for u in models], 'Client %s sent %d non-finite elements (NaN in the aggregate there)')
+        if s.compress_bits or s.topk_ratio:
+            clip, mech, weights = self._upload_clip(s, data_sizes)
+            extra = {} if clip is None else {"clip": clip, "mech": mech}       # (clip_uploads off: today's call, argument for argument)
+            if s.compress_bits:
+                aggr_state_dict = FedCompressed(up.global_state, models, weights, opt, **extra)
+                self._report_uploads('Compressed uploads (%d bits%s)' % (s.compress_bits, ", error feedback" if s.feedback else ""), models, '', order,
+                                     [u.nonfinite_blocks for u in models], 'Client %s sent %d non-finite blocks (NaN in the aggregate there)', clip)
+            else:
+                aggr_state_dict = FedSparse(up.global_state, models, weights, opt, **extra)
+                self._report_uploads('Top-k uploads (ratio %g%s)' % (s.topk_ratio, ", error feedback" if s.feedback else ""), models, '', order,
+                                     [u.nonfinite for u in models], 'Client %s sent %d non-finite elements (NaN in the aggregate there)', clip)
+            if clip is not None:
+                self._check_clipped_uploads(order, mech is not None)
+            if mech is not None:
+                self._dp_account(s.dp_sigma, s.clip_norm, s.dp_delta)
         elif s.secagg_on:
             from .secagg import survivor_rescale
             keep = [pos for pos, i in enumerate(order) if i not in s.secagg_drop]      # (a dropped client's upload is discarded after masking)
@@ -1166,25 +1296,66 @@ class Server(object):
                          % (self.dp_epsilon, delta, acc.steps, mech.z_eff, mech.noise_multiplier, mech.sigma_int, mech.delta_int, mech.threshold,
                             mech.realised_multiplier(len(survivors)), len(survivors)))
 
-    def _aggregate_dp(self, models, data_sizes, aggr_alg, sigma, clip_norm, delta):
-        """the round's aggregation under ``dp_noise_multiplier`` > 0: ``FedDP`` with the server's mechanism (one per server: it holds the
-        round counter of the noise stream), then the accountant's step and the (epsilon, delta) after the rounds so far, on
-        ``self.dp_epsilon``.  q = len(current_client_list) / num_client; the rate only ever grows in the accountant (rdp is monotone in q,
-        so the largest rate of the run bounds every round)."""
+    def _upload_clip(self, s, data_sizes):
+        """(clip, mech, weights) of a round from compressed or top-k uploads: (None, None, ``data_sizes``) unless ``clip_uploads`` is on; then
+        the server's ``UploadClip`` (one per server and clip_norm: it keeps the workspace), and under ``dp_noise_multiplier`` > 0 the
+        mechanism and the weights of ``_aggregate_dp``"""
+        if not s.clip_uploads:
+            return None, None, data_sizes
+        clip = getattr(self, "upload_clip", None)
+        if clip is None or clip.clip_norm != s.clip_norm:
+            clip = self.upload_clip = UploadClip(s.clip_norm)
+        if not s.dp_sigma:
+            return clip, None, data_sizes
+        return clip, self._dp_mechanism(s.dp_sigma, s.clip_norm), self._dp_weights(data_sizes)
+
+    def _check_clipped_uploads(self, order, dp: bool):
+        """what ``clip_uploads`` checks after the round's one read (``_report_uploads``), before the state is installed or the round
+        accounted: a top-k upload with entries out of range or out of order does not have the norm the clip measured, and under DP an
+        upload whose norm is not finite was not clipped at all (its coefficient is its weight): either voids the round"""
+        for i, nv in zip(order, self.upload_violations or []):
+            if nv > 0:
+                raise RuntimeError("Server.train: the top-k upload of client %s holds %d entries whose index is out of range or not ascending; "
+                                   "the clip measured another vector than the server applies and bounds nothing: the round is void"
+                                   % (getattr(self.clients[i], "cid", i), nv))
+        if dp:
+            for i, sq in zip(order, self.upload_sqnorms):
+                if not np.isfinite(sq):
+                    raise RuntimeError("Server.train: the upload of client %s has squared norm %r: it was not clipped, so the sensitivity bound of "
+                                       "the mechanism does not hold: the round is void" % (getattr(self.clients[i], "cid", i), sq))
+
+    def _dp_mechanism(self, sigma, clip_norm):
+        """the server's Gaussian mechanism (one per server: it holds the round counter of the noise stream), renewed when the settings change"""
         import secrets
-        from .privacy import GaussianMechanism, RDPAccountant
+        from .privacy import GaussianMechanism
         if self.dp_mech is None or (self.dp_mech.noise_multiplier, self.dp_mech.clip_norm) != (sigma, clip_norm):
             seed = getattr(self.args, "dp_seed", None)
             rnd = 0 if self.dp_mech is None else self.dp_mech.round
             self.dp_mech = GaussianMechanism(sigma, clip_norm, secrets.randbits(64) if seed is None else seed)
             self.dp_mech.round = rnd
+        return self.dp_mech
+
+    def _dp_weights(self, data_sizes):
+        """the weights of a round under the central mechanism: uniform unless ``dp_uniform_weights`` is off (then a warning)"""
         uniform = bool(getattr(self.args, "dp_uniform_weights", True))
         if not uniform:
             self.logger.warning('dp_uniform_weights is off: data-size weights are client-reported; the sensitivity bound clip_norm * max w_i '
                                 'holds for the weights of this round only')
-        weights = [1.0] * len(models) if uniform else data_sizes
+        return [1.0] * len(data_sizes) if uniform else data_sizes
+
+    def _aggregate_dp(self, models, data_sizes, aggr_alg, sigma, clip_norm, delta):
+        """the round's aggregation under ``dp_noise_multiplier`` > 0: ``FedDP`` with the server's mechanism, then the accountant's step
+        (``_dp_account``)."""
         opt = self.server_opt if aggr_alg in AGGR_ALG_KINDS else None
-        out = FedDP(flat_state_dict(self.federated_model), models, weights, self.dp_mech, opt)
+        out = FedDP(flat_state_dict(self.federated_model), models, self._dp_weights(data_sizes), self._dp_mechanism(sigma, clip_norm), opt)
+        self._dp_account(sigma, clip_norm, delta)
+        return out
+
+    def _dp_account(self, sigma, clip_norm, delta):
+        """the accountant's step for one round of the central mechanism and the (epsilon, delta) after the rounds so far, on
+        ``self.dp_epsilon``.  q = len(current_client_list) / num_client; the rate only ever grows in the accountant (rdp is monotone in q,
+        so the largest rate of the run bounds every round)."""
+        from .privacy import RDPAccountant
         q = len(self.current_client_list) / float(self.num_client)
         acc = self.dp_accountant
         if acc is None or q > acc.q:
@@ -1195,7 +1366,6 @@ class Server(object):
         self.dp_epsilon = acc.epsilon(delta)
         self.logger.info('Differential privacy: (epsilon, delta) = (%.4f, %g) after %d rounds (noise multiplier %g, clip_norm %g, q = %g)'
                          % (self.dp_epsilon, delta, acc.steps, sigma, clip_norm, acc.q))
-        return out
 
     @torch.no_grad()
     @_C.on_device(lambda self: self.device)

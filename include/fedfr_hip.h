@@ -896,6 +896,58 @@ int fedfr_topk_sparsify(const float* x, const float* xi, float* resid, size_t n,
 int fedfr_sparse_aggregate(float* dst, const float* base, const unsigned* const* idx, const float* const* val, const size_t* keeps,
                            const float* ws, int k, size_t n, int accumulate, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * clip and Gaussian noise for compressed and top-k uploads — no reference counterpart.  The server bounds one client's influence on the
+ * round by the norm of its upload AS THE SERVER WILL APPLY IT (the dequantised codes, the scattered entries), and may add the noise of
+ * THE NOISE STREAM above.  Two steps, no host round trip between them: a norm pass that leaves the clipped weights on the device, and
+ * the aggregates of the two sections above with their weights read from there.
+ * THE NORMS.
+ *   compressed   per block b of 32 elements S_b = sum q_j^2, an integer (<= 32 * 128^2: exact), T_b = double(S_b) 4^(eb_b - 127), exact
+ *                in fp64 for every scale byte 0..254 (a 20-bit integer times a power of two between 2^-254 and 2^254); sq_i = sum_b T_b.
+ *                A block with scale byte 255 contributes NaN.  Elements at index >= n of the last block (the pad nibble of an odd 4-bit
+ *                n included) are not counted, whatever the upload holds there.  Code -128 (8 bits) and -8 (4 bits), which
+ *                fedfr_delta_quantize never produces, count as 128^2 and 8^2: what fedfr_delta_aggregate would apply.
+ *   top-k        sq_i = sum_e double(val_e)^2 (the square of an fp32 value is exact in fp64).  The scattered vector has this norm only if
+ *                the indices are distinct and in range: violations_i counts the entries with idx_e >= n or idx_e <= idx_(e-1).
+ *   order        the sums are fp64 in ONE fixed order, as fedfr_fedopt_sqnorm's: a thread's terms in its grid-stride order, the lanes of
+ *                a wave by the xor-shuffle tree, the four waves ((w0 + w1) + w2) + w3, one partial per upload and block in `workspace`,
+ *                the blocks ascending.  No float atomics; two runs give identical bits whatever the workspace held before.
+ *   coefficient  coef_i = ws[i] min(1, clip / sqrt(sq_i)) in fp64, rounded to fp32 once (the final kernel of fedfr_fedopt_sqnorm itself);
+ *                clip <= 0, sq_i = 0 or a NaN sq_i (the comparison fails) leave coef_i = ws[i].
+ * ------------------------------------------------------------------------------------------------ */
+/* bytes of the workspace of fedfr_delta_sqnorm (second argument: n) and fedfr_sparse_sqnorm (second argument: the largest keeps[i]):
+ * k x grid doubles, grid = min(ceil((m / 8 + 1) / 256), 2048); 0 for k outside 1..8 */
+size_t fedfr_upload_sqnorm_workspace_bytes(int k, size_t n_or_max_keep);
+/* One pass over k <= 8 compressed uploads (HOST arrays of k device pointers codes / scales and k weights ws, as fedfr_delta_aggregate):
+ * every code and scale byte is read once, no fp32 state is touched (8 bits: 1.03 bytes per parameter and upload).  sq: DEVICE double[k],
+ * coef: DEVICE float[k], both written.  Code buffers 16-byte, sq and workspace 8-byte, coef 4-byte aligned.  FEDFR_ERR_ARG, before anything
+ * is launched, for bits other than 4 or 8, k outside 1..8, a NULL codes, scales, ws, sq, coef, workspace or array entry, n = 0, a NaN clip
+ * or a misaligned buffer; FEDFR_ERR_WORKSPACE if workspace_bytes < fedfr_upload_sqnorm_workspace_bytes(k, n). */
+int fedfr_delta_sqnorm(const void* const* codes, const unsigned char* const* scales, const float* ws, int k, int bits, size_t n, float clip,
+                       double* sq, float* coef, void* workspace, size_t workspace_bytes, void* stream);
+/* The same over k <= 8 top-k uploads (idx / val / keeps / ws as fedfr_sparse_aggregate; keeps[i] = 0 is an upload of norm 0).
+ * violations: DEVICE int[k], ADDED to (integer atomics: order-free); the caller zeroes it.  Index and value buffers 16-byte, sq and
+ * workspace 8-byte, coef and violations 4-byte aligned.  FEDFR_ERR_ARG, before anything is launched, for k outside 1..8, a NULL idx, val,
+ * keeps, ws, sq, coef, violations, workspace or array entry, keeps[i] > n, n = 0 or n >= 2^31, a NaN clip or a misaligned buffer;
+ * FEDFR_ERR_WORKSPACE if workspace_bytes < fedfr_upload_sqnorm_workspace_bytes(k, max keeps[i]). */
+int fedfr_sparse_sqnorm(const unsigned* const* idx, const float* const* val, const size_t* keeps, const float* ws, int k, size_t n, float clip,
+                        double* sq, float* coef, int* violations, void* workspace, size_t workspace_bytes, void* stream);
+/* fedfr_delta_aggregate, operation for operation, with coef[i] (DEVICE float[k], read once per thread) in the place of ws[i], and on the
+ * LAST pass of a chain, if noise_std > 0, before base is added:
+ *   s = s + noise_std * z(offset + j)                                                      (one fp32 multiply, one fp32 add)
+ * z as fedfr_gaussian_fill writes it for the same (seed, round, stream_id, offset + j), bit for bit: the value depends on nothing else,
+ * not on the grid, on k or on the number of passes.  Every pass of a chain must be given the chain's (noise_std, seed, round, stream_id,
+ * offset); only the pass with last != 0 draws.  With noise_std = 0 nothing is drawn or added and the result is fedfr_delta_aggregate's
+ * for ws = coef, bit for bit.  FEDFR_ERR_ARG, before anything is launched, for what fedfr_delta_aggregate refuses (coef for ws; coef
+ * 4-byte aligned), a noise_std that is negative or not finite, or an offset that is not a multiple of 4. */
+int fedfr_delta_aggregate_dp(float* dst, const float* base, const void* const* codes, const unsigned char* const* scales, const float* coef,
+                             int k, int bits, size_t n, int accumulate, int last, float noise_std, unsigned long long seed,
+                             unsigned long long round, unsigned stream_id, unsigned long long offset, void* stream);
+/* fedfr_sparse_aggregate in the same way.  The noise is DENSE: every element of every tile receives it, not only the touched ones. */
+int fedfr_sparse_aggregate_dp(float* dst, const float* base, const unsigned* const* idx, const float* const* val, const size_t* keeps,
+                              const float* coef, int k, size_t n, int accumulate, int last, float noise_std, unsigned long long seed,
+                              unsigned long long round, unsigned stream_id, unsigned long long offset, void* stream);
+
 int fedfr_pfc_rand(float* perm, int n, unsigned long long seed, unsigned long long step, void* stream);
 int fedfr_pfc_localize(long long* label, int n, long long class_start, int num_local, float* perm, void* stream);
 int fedfr_pfc_topk(const float* perm, int n, int k, long long* index, int* npos_out, void* stream);
