@@ -163,6 +163,10 @@ SIGNATURES = {
     "fedfr_chacha20_fill": (i32, [vp, sz, vp, u32, vp, vp]),
     "fedfr_secagg_mask": (i32, [vp, vp, vp, f32, i32, vp, vp, vp, i32, sz, vp, vp]),
     "fedfr_secagg_aggregate": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, f32, sz, i32, i32, vp]),
+    "fedfr_rht_padded_count": (sz, [sz]),
+    "fedfr_rht_fill": (i32, [vp, vp, sz, u64, u64, i32, vp]),
+    "fedfr_secagg_mask_narrow": (i32, [vp, vp, vp, f32, i32, i32, u64, u64, u64, vp, vp, vp, i32, u32, sz, vp, vp]),
+    "fedfr_secagg_aggregate_narrow": (i32, [vp, vp, vp, vp, i32, i32, u64, u64, vp, vp, vp, i32, u32, i32, f32, sz, i32, i32, vp]),
     "fedfr_dgauss_fill": (i32, [vp, sz, u64, u64, u32, u64, f64, vp, vp]),
     "fedfr_secagg_mask_dp": (i32, [vp, vp, vp, vp, i32, i32, u64, u64, u64, f64, vp, vp, vp, i32, sz, vp, vp, vp]),
     "fedfr_robust_trimmed_mean": (i32, [vp, vp, i32, i32, sz, vp]),

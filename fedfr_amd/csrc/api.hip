@@ -15,6 +15,7 @@
 #include "dp.h"
 #include "secagg.h"
 #include "ddp.h"
+#include "secagg_narrow.h"
 
 static thread_local char g_err[512] = "";
 extern int g_tn_use_tr;
@@ -933,6 +934,23 @@ int fedfr_secagg_aggregate(float* out, const float* x, unsigned* acc, const unsi
                            const unsigned* nonces, const int* signs, int k, int frac_bits, float rescale, size_t n, int first, int last,
                            void* stream) {
   return secagg_aggregate(out, x, acc, ys, ku, keys, nonces, signs, k, frac_bits, rescale, n, first, last, ST(stream));
+}
+size_t fedfr_rht_padded_count(size_t n) { return rht_padded(n); }
+int fedfr_rht_fill(float* dst, const float* src, size_t n, unsigned long long rotation_seed, unsigned long long round, int inverse, void* stream) {
+  return secagg_rht_fill(dst, src, n, rotation_seed, round, inverse, ST(stream));
+}
+int fedfr_secagg_mask_narrow(unsigned* y, const float* x, const float* xi, float coef, int participants, int bits, unsigned long long rotation_seed,
+                             unsigned long long private_seed, unsigned long long round, const unsigned* keys, const unsigned* nonces,
+                             const int* signs, int k, unsigned counter0, size_t n, int* counters, void* stream) {
+  return secagg_mask_narrow(y, x, xi, coef, participants, bits, rotation_seed, private_seed, round, keys, nonces, signs, k, counter0, n, counters,
+                            ST(stream));
+}
+int fedfr_secagg_aggregate_narrow(float* out, const float* x, unsigned* acc, const unsigned* const* ys, int ku, int bits,
+                                  unsigned long long rotation_seed, unsigned long long round, const unsigned* keys, const unsigned* nonces,
+                                  const int* signs, int k, unsigned counter0, int frac_bits, float rescale, size_t n, int first, int last,
+                                  void* stream) {
+  return secagg_aggregate_narrow(out, x, acc, ys, ku, bits, rotation_seed, round, keys, nonces, signs, k, counter0, frac_bits, rescale, n, first, last,
+                                 ST(stream));
 }
 int fedfr_dgauss_fill(int* dst, size_t n, unsigned long long seed, unsigned long long round, unsigned stream_id, unsigned long long offset,
                       double sigma, int* exhausted, void* stream) {

@@ -21,6 +21,12 @@ DISTRIBUTED DIFFERENTIAL PRIVACY.  With a ``privacy.DistributedDiscreteGaussian`
 integer Gaussian noise to the codes and masks the result (``SecAggClient.mask_dp``: fedfr_secagg_mask_dp, one pass); the sum the server
 unmasks then carries the noise of all surviving clients, and nobody ever holds an un-noised sum.  The sampler and its stream are stated in
 include/fedfr_hip.h, "THE DISCRETE NOISE STREAM"; what the guarantee covers: DESIGN.md section 3.27.
+
+NARROW WORDS.  ``SecAggClient(..., bits=8 or 16)`` uploads n_pad b / 8 bytes instead of 4 n: the update is rotated block by block with a
+PUBLIC random sign flip and a Walsh-Hadamard transform (so that no coordinate is large), rounded STOCHASTICALLY to b-bit codes with the
+client's private draws (so that the codes are unbiased), packed 32 / b to a word and masked and summed FIELD-WISE mod 2^b
+(``fedfr_secagg_mask_narrow`` / ``fedfr_secagg_aggregate_narrow``; the format: include/fedfr_hip.h, "NARROW WORDS"; how to choose
+``frac_bits``: INTEGRATION.md section 19).  ``bits=32`` is the path above, unchanged.  Distributed DP at narrow widths is not provided.
 """
 from __future__ import annotations
 
@@ -178,9 +184,30 @@ def shamir_combine(shares: Sequence[Share]) -> bytes:
 Stream = Tuple[Tuple[int, ...], Tuple[int, int, int], int]      # (8 key words, 3 nonce words, sign +1 / -1)
 
 
-def code_limit(participants: int) -> int:
-    """L = (2^31 - 1) // K: the sum of K codes in [-L, L] cannot leave the signed 32-bit range"""
-    return (2 ** 31 - 1) // int(participants)
+WIDTHS = (8, 16, 32)                 # bits of a code on the wire
+ROTATION_BLOCK = 4096                # elements of one rotation block of the narrow widths
+
+
+def check_bits(bits, who: str) -> int:
+    if isinstance(bits, bool) or not isinstance(bits, (int, np.integer)) or int(bits) not in WIDTHS:
+        raise ValueError("%s: secagg_bits must be 8, 16 or 32 (got %r)" % (who, bits))
+    return int(bits)
+
+
+def check_rotation_seed(seed, who: str) -> int:
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+        raise ValueError("%s: secagg_rotation_seed must be an integer in 0 ... 2^64 - 1 (got %r)" % (who, seed))
+    return int(seed)
+
+
+def code_limit(participants: int, bits: int = 32) -> int:
+    """L = (2^(bits-1) - 1) // K: the sum of K codes in [-L, L] cannot leave the signed range of ``bits`` bits"""
+    return (2 ** (int(bits) - 1) - 1) // int(participants)
+
+
+def padded_count(n: int) -> int:
+    """n_pad: ``n`` rounded up to whole rotation blocks (the narrow widths encode, mask and sum n_pad elements)"""
+    return (int(n) + ROTATION_BLOCK - 1) // ROTATION_BLOCK * ROTATION_BLOCK
 
 
 def code_coef(weight: float, frac_bits: int) -> float:
@@ -216,12 +243,16 @@ class MaskedUpdate:
     back only when ``saturated_count()`` / ``nonfinite_count()`` are asked for.  ``table`` / ``layers`` describe the state the upload
     belongs to (FlatStateDict).  An upload of ``SecAggClient.mask_dp`` carries a third counter, {..., exhausted} (elements whose noise
     sampler ran out of attempts: an error), and ``sqnorm``: a DEVICE int64 holding the exact sum of its squared codes mod 2^64, taken
-    before the noise (``sqnorm_value()``), which the server holds against the mechanism's sensitivity."""
+    before the noise (``sqnorm_value()``), which the server holds against the mechanism's sensitivity.
+    ``bits`` is the width of a code: 32 (one word per parameter), or 8 / 16, where ``y`` holds padded_count(n) bits / 32 PACKED words of the
+    rotated update and ``rotation_seed`` / ``round`` name the public rotation the server needs to turn the sum back (both public; with them
+    the counters cover the padded_count(n) rotated elements)."""
 
-    def __init__(self, y, n, frac_bits, stats, counters, code_counters, table=None, layers=None, sqnorm=None):
+    def __init__(self, y, n, frac_bits, stats, counters, code_counters, table=None, layers=None, sqnorm=None, bits=32, rotation_seed=0, round=0):
         self.y, self.n, self.frac_bits = y, int(n), int(frac_bits)
         self.stats, self.counters, self.code_counters = stats, counters, code_counters
         self.table, self.layers, self.sqnorm = table, layers, sqnorm
+        self.bits, self.rotation_seed, self.round = int(bits), int(rotation_seed), int(round)
 
     @property
     def nbytes(self) -> int:
@@ -251,20 +282,32 @@ class MaskedUpdate:
 
 class SecAggClient:
     """The protocol state of ONE client.  ``begin_round`` draws a fresh X25519 key pair and a 32-byte self seed b_i; ``make_shares`` hands
-    out Shamir shares of the secret key and of b_i, one pair per participant; ``mask`` makes the upload."""
+    out Shamir shares of the secret key and of b_i, one pair per participant; ``mask`` makes the upload.  With ``bits`` = 8 or 16 the upload
+    is one of NARROW WORDS (the module's docstring): ``rotation_seed`` is the public seed all clients and the server share, and
+    ``begin_round`` also draws the 64-bit seed of the client's private rounding draws."""
 
-    def __init__(self, cid: int, frac_bits: int = 24, rng: Optional[Rng] = None):
+    def __init__(self, cid: int, frac_bits: int = 24, rng: Optional[Rng] = None, bits: int = 32, rotation_seed: int = 0):
         self.cid, self.frac_bits, self.rng = int(cid), check_frac_bits(frac_bits, "SecAggClient"), rng
+        self.rounding_seed = None       # the 64-bit seed of the client's rounding draws of the round (narrow widths): drawn in begin_round, never sent
+        self.set_width(bits, rotation_seed)
         self.round = None
         self.secret_key = self.public_key = self.self_seed = None
         self.noise_seed = None          # the 64-bit seed of the client's noise share of the round (mask_dp): drawn here, never sent
         self._clipper = None            # mask_dp keeps the workspace of its norm pass here
+
+    def set_width(self, bits: int = 32, rotation_seed: int = 0):
+        """the width of the codes (8, 16 or 32) and, for the narrow ones, the public rotation seed; takes effect at the next ``begin_round``"""
+        self.bits = check_bits(bits, "SecAggClient")
+        self.rotation_seed = check_rotation_seed(rotation_seed, "SecAggClient")
+        return self
 
     def begin_round(self, round: int) -> bytes:
         """fresh secrets for ``round``; returns the public key"""
         self.round = int(round)
         self.secret_key, self.public_key = keypair(self.rng)
         self.self_seed = (self.rng or os.urandom)(32)
+        # (drawn behind the secrets of the 32-bit path and at the narrow widths only: that path draws what it always drew)
+        self.rounding_seed = int.from_bytes((self.rng or os.urandom)(8), "little") if self.bits != 32 else None
         return self.public_key
 
     def make_shares(self, participants: Sequence[int], threshold: int) -> Dict[int, Tuple[Share, Share]]:
@@ -307,8 +350,18 @@ class SecAggClient:
         _check_states(x, [xi], "SecAggClient")
         n, dev = x.numel(), x.device
         keys, nonces, signs = stream_arrays(self.streams(participants, public_keys, round))
-        y = torch.empty(n, dtype=torch.int32, device=dev)
         cc = torch.zeros(2, dtype=torch.int32, device=dev)
+        if self.bits != 32:
+            # NARROW WORDS: ONE call of fedfr_secagg_mask_narrow (rotation, stochastic rounding, packing and masks in one pass)
+            if self.rounding_seed is None:
+                raise RuntimeError("SecAggClient.mask: the secrets at hand were drawn for 32-bit words; set_width(...) and begin_round again")
+            y = torch.empty(padded_count(n) * self.bits // 32, dtype=torch.int32, device=dev)
+            if n:
+                _C.call("fedfr_secagg_mask_narrow", y.data_ptr(), x.data_ptr(), xi.data_ptr(), code_coef(weight, self.frac_bits), K, self.bits,
+                        self.rotation_seed, self.rounding_seed, int(round) & 0xFFFFFFFF, keys, nonces, signs, K, 0, n, cc.data_ptr(), _C.stream())
+            return MaskedUpdate(y, n, self.frac_bits, stats, counters, cc, client_state.table, client_state.layers, bits=self.bits,
+                                rotation_seed=self.rotation_seed, round=int(round) & 0xFFFFFFFF)
+        y = torch.empty(n, dtype=torch.int32, device=dev)
         if n:
             _C.call("fedfr_secagg_mask", y.data_ptr(), x.data_ptr(), xi.data_ptr(), code_coef(weight, self.frac_bits), code_limit(K), keys, nonces,
                     signs, K, n, cc.data_ptr(), _C.stream())
@@ -330,6 +383,8 @@ class SecAggClient:
             raise RuntimeError("fedfr_amd.SecAggClient: the global and the client state must be FlatStateDicts (client.flat_state_dict)")
         if not isinstance(mech, DistributedDiscreteGaussian):
             raise RuntimeError("fedfr_amd.SecAggClient.mask_dp: mech must be a privacy.DistributedDiscreteGaussian (got %r)" % (type(mech).__name__,))
+        if self.bits != 32:
+            raise ValueError("SecAggClient.mask_dp: distributed differential privacy at %d-bit words is not provided" % self.bits)
         K = len(participants)
         if not 2 <= K <= MAX_PARTICIPANTS or len(set(participants)) != K:
             raise ValueError("SecAggClient.mask_dp: 2 to %d distinct participants (got %d: %s)" % (MAX_PARTICIPANTS, K, list(participants)))

@@ -593,34 +593,47 @@ def FedCompressed(global_state, updates, weights: Sequence[float], server_opt=No
 
 
 # ---- secure aggregation: csrc/secagg.hip secagg_mask_kernel (client side, secagg.py) / secagg_aggregate_kernel
-def _masked_sum(what, x: torch.Tensor, uploads, recovery_streams, frac_bits: int, rescale: float, add_x: bool, mismatch: str) -> torch.Tensor:
+def _masked_sum(what, x: torch.Tensor, uploads, recovery_streams, frac_bits: int, rescale: float, add_x: bool, mismatch: str, bits: int = 32) -> torch.Tensor:
     """(``add_x``: x +) float(int32(S)) 2^-``frac_bits`` ``rescale`` as a new tensor, S = Σ_i y_i + Σ_r sign_r m_r mod 2^32 over the masked
     ``uploads`` and the ``recovery_streams`` (fedfr_secagg_aggregate: ≤ 8 uploads and ≤ 32 streams per pass; more chain passes through an
     integer buffer, and the last pass alone scales and adds x).  RuntimeError for an upload of other fraction bits or parameter count
-    (``mismatch``: the sentence, the upload's two numbers left open) or whose ``y`` is not n contiguous int32 words on x's device."""
-    from .secagg import stream_arrays
+    (``mismatch``: the sentence, the upload's two numbers left open) or whose ``y`` is not n contiguous int32 words on x's device.
+    ``bits`` = 8 or 16: the uploads are NARROW WORDS (secagg.py), all of that width and of one public rotation; S is the FIELD-WISE sum mod
+    2^bits of their padded_count(n) bits / 32 packed words and the streams, and the last pass turns the rotation back
+    (fedfr_secagg_aggregate_narrow, chained in the same way): x + rescale D 2^-6 H (S 2^-``frac_bits``)."""
+    from .secagg import padded_count, stream_arrays
     n = x.numel()
+    words = n if bits == 32 else padded_count(n) * bits // 32
     for u in uploads:
         if u.frac_bits != frac_bits or u.n != n:
             raise RuntimeError("fedfr_amd.%s: %s" % (what, mismatch % (u.frac_bits, u.n)))
-        if u.y.dtype != torch.int32 or u.y.numel() != n or u.y.device != x.device or not u.y.is_contiguous():
-            raise RuntimeError("fedfr_amd.%s: y must be a contiguous int32 tensor of %d words on %s" % (what, n, x.device))
+        if u.bits != bits:
+            raise RuntimeError("fedfr_amd.%s: an upload of %d-bit words among uploads of %d-bit words" % (what, u.bits, bits))
+        if bits != 32 and (u.rotation_seed, u.round) != (uploads[0].rotation_seed, uploads[0].round):
+            raise RuntimeError("fedfr_amd.%s: an upload rotated with (seed %d, round %d) among uploads rotated with (seed %d, round %d)"
+                               % (what, u.rotation_seed, u.round, uploads[0].rotation_seed, uploads[0].round))
+        if u.y.dtype != torch.int32 or u.y.numel() != words or u.y.device != x.device or not u.y.is_contiguous():
+            raise RuntimeError("fedfr_amd.%s: y must be a contiguous int32 tensor of %d words on %s" % (what, words, x.device))
     streams = list(recovery_streams)
     passes = max((len(uploads) + 7) // 8, (len(streams) + 31) // 32)
-    acc = torch.empty(n, dtype=torch.int32, device=x.device) if passes > 1 else None
+    acc = torch.empty(words, dtype=torch.int32, device=x.device) if passes > 1 else None
     P = torch.empty_like(x)
     for p in range(passes):
         grp, sgrp = uploads[8 * p:8 * p + 8], streams[32 * p:32 * p + 32]
         last = p == passes - 1
         keys, nonces, signs = stream_arrays(sgrp)
-        if n:
+        if n and bits == 32:
             _C.call("fedfr_secagg_aggregate", P.data_ptr(), x.data_ptr() if last and add_x else None, _C.ptr(acc),
                     _C.ptr_array([u.y for u in grp]), len(grp), keys, nonces, signs, len(sgrp), frac_bits, rescale, n, 1 if p == 0 else 0,
                     1 if last else 0, _C.stream())
+        elif n:
+            _C.call("fedfr_secagg_aggregate_narrow", P.data_ptr(), x.data_ptr() if last and add_x else None, _C.ptr(acc),
+                    _C.ptr_array([u.y for u in grp]), len(grp), bits, uploads[0].rotation_seed, uploads[0].round, keys, nonces, signs, len(sgrp), 0,
+                    frac_bits, rescale, n, 1 if p == 0 else 0, 1 if last else 0, _C.stream())
     return P
 
 
-def FedSecAgg(global_state, uploads, weights: Sequence[float], recovery_streams, rescale: float = 1.0, server_opt=None):
+def FedSecAgg(global_state, uploads, weights: Sequence[float], recovery_streams, rescale: float = 1.0, server_opt=None, bits=None):
     """One round from masked uploads (``secagg.MaskedUpdate``, all of one ``frac_bits``): the PARAMETERS of the new global state are
     x + float(int32(S)) 2^-f rescale with x = ``global_state``'s parameters and S = Σ_i y_i + Σ_r sign_r m_r mod 2^32 over the uploads
     and the ``recovery_streams`` ([(8 key words, 3 nonce words, sign)], ``secagg.SecAggServer.recovery_streams``), which cancel what the
@@ -630,8 +643,19 @@ def FedSecAgg(global_state, uploads, weights: Sequence[float], recovery_streams,
     ``ServerOptimizer``) the same sum WITHOUT x is the pseudo-gradient Δ and goes through ``server_opt.apply_delta``; ``clip_norm`` > 0
     raises ``ValueError`` (the clip needs per-client norms, which masked uploads hide by design).  BN running statistics and
     ``num_batches_tracked`` arrive UNMASKED and are averaged over the uploads with ``weights`` exactly as ``FedPavg`` averages them.  Only a
-    GPU ``FlatStateDict`` is accepted as ``global_state``."""
-    from .secagg import MaskedUpdate
+    GPU ``FlatStateDict`` is accepted as ``global_state``.
+    The width of the words is read from the uploads (``MaskedUpdate.bits``): all must have one, and with ``bits`` (the server's setting) that
+    one.  At 8 or 16 bits the uploads are NARROW WORDS (secagg.py): S is the field-wise sum mod 2^bits of the packed words, and the
+    parameters are x + rescale D 2^-6 H (S 2^-f), the rotation turned back (fedfr_secagg_aggregate_narrow); everything behind the sum is the
+    same."""
+    from .secagg import MaskedUpdate, check_bits
+    if bits is not None:
+        bits = check_bits(bits, "FedSecAgg")
+    width = {u.bits for u in uploads if isinstance(u, MaskedUpdate)}
+    if len(width) > 1:
+        raise RuntimeError("fedfr_amd.FedSecAgg: uploads of different widths (%s bits): all clients of a round encode at one width" % sorted(width))
+    if bits is not None and width and width != {bits}:
+        raise RuntimeError("fedfr_amd.FedSecAgg: uploads of %d-bit words, the server expects %d-bit words" % (width.pop(), bits))
     rescale = float(np.float32(rescale))
     if not (np.isfinite(rescale) and rescale >= 1.0):
         raise ValueError("FedSecAgg: rescale is fp32(1 / sum of the survivors' weights), a finite number >= 1 (got %r)" % (rescale,))
@@ -640,7 +664,8 @@ def FedSecAgg(global_state, uploads, weights: Sequence[float], recovery_streams,
                                "clip_norm > 0 needs per-client norms of the updates, which masked uploads hide by design")
     frac_bits = uploads[0].frac_bits
     P = _masked_sum("FedSecAgg", x, uploads, recovery_streams, frac_bits, rescale, server_opt is None,
-                    "an upload of %%d fraction bits and %%d parameters among uploads of %d bits for %d parameters" % (frac_bits, x.numel()))
+                    "an upload of %%d fraction bits and %%d parameters among uploads of %d bits for %d parameters" % (frac_bits, x.numel()),
+                    **({} if uploads[0].bits == 32 else {"bits": uploads[0].bits}))
     return _upload_round_tail(global_state, P, x, uploads, ws, server_opt)
 
 
@@ -955,6 +980,15 @@ class Server(object):
         return_all = bool(getattr(a, "return_all", False))
         clip_uploads = bool(getattr(a, "clip_uploads", False))               # the clip (and DP noise) ON compressed / top-k uploads: absent or False = off
         dp_delta = ddp_mech = secagg_frac_bits = secagg_threshold = None     # (resolved below where their feature is on)
+        secagg_bits, secagg_rotation_seed = getattr(a, "secagg_bits", None), 0   # narrow masked uploads (a build extension): absent or 32 = one word per parameter
+        if secagg_bits is not None:
+            from .secagg import check_bits
+            secagg_bits = check_bits(secagg_bits, "Server.train")
+            if not secagg_on:
+                raise ValueError("Server.train: secagg_bits=%d needs secure_aggregation: it is the width of a masked upload's codes" % (secagg_bits,))
+            if ddp_on and secagg_bits != 32:
+                raise ValueError("Server.train: secagg_bits=%d cannot be combined with distributed_dp: discrete Gaussian noise in a ring of %d "
+                                 "bits needs its own sensitivity and wrap-around analysis, which is not provided" % (secagg_bits, secagg_bits))
         secagg_drop = []
         if aggr_alg not in ("FedAvg", "FedProx") and aggr_alg not in AGGR_ALG_KINDS and aggr_alg not in ROBUST_ALG_KINDS:      # before a round of client training is spent on it
             raise ValueError("Server.train: unknown aggr_alg %r (FedAvg, FedProx, %s, %s)"
@@ -1052,6 +1086,9 @@ class Server(object):
             if not 2 <= K <= MAX_PARTICIPANTS:
                 raise ValueError("Server.train: secure_aggregation needs 2 to %d participants (got %d)" % (MAX_PARTICIPANTS, K))
             secagg_frac_bits = check_frac_bits(getattr(a, "secagg_frac_bits", 24), "Server.train")
+            if secagg_bits in (8, 16):
+                from .secagg import check_rotation_seed
+                secagg_rotation_seed = check_rotation_seed(getattr(a, "secagg_rotation_seed", 0), "Server.train")      # public: shared by all clients and the server
             secagg_threshold = getattr(a, "secagg_threshold", None)
             if secagg_threshold is None:
                 secagg_threshold = K // 2 + 1
@@ -1076,6 +1113,7 @@ class Server(object):
         return SimpleNamespace(aggr_alg=aggr_alg, dp_sigma=dp_sigma, clip_norm=clip_norm, dp_delta=dp_delta, ddp_on=ddp_on, ddp_mech=ddp_mech,
                                compress_bits=compress_bits, topk_ratio=topk_ratio, feedback=bool(getattr(a, "error_feedback", True)),
                                secagg_on=secagg_on, secagg_frac_bits=secagg_frac_bits, secagg_threshold=secagg_threshold, secagg_drop=secagg_drop,
+                               secagg_bits=secagg_bits or 32, secagg_rotation_seed=secagg_rotation_seed,
                                public=bool(getattr(a, "add_pretrained_data", False)), return_all=return_all,
                                clip_uploads=clip_uploads and clip_norm > 0)
 
@@ -1160,7 +1198,10 @@ class Server(object):
             from .secagg import SecAggServer
             up.sa_server = SecAggServer(order, s.secagg_threshold, self.global_round)
             for i in order:
-                up.sa_server.register(i, self.clients[i].secagg_client(i, s.secagg_frac_bits, self.secagg_rng).begin_round(self.global_round))
+                sa = self.clients[i].secagg_client(i, s.secagg_frac_bits, self.secagg_rng)
+                if (sa.bits, sa.rotation_seed) != (s.secagg_bits, s.secagg_rotation_seed):      # (32-bit words: nothing to tell the client)
+                    sa.set_width(s.secagg_bits, s.secagg_rotation_seed)
+                up.sa_server.register(i, sa.begin_round(self.global_round))
             for i in order:
                 up.sa_server.deliver_shares(i, self.clients[i].secagg.make_shares(order, s.secagg_threshold))
             up.public_w = _normalised([self.clients[i].get_data_size() for i in order])      # w_i = n_i / Σn: public, the factor each client encodes with
@@ -1246,8 +1287,10 @@ class Server(object):
             if s.ddp_on:
                 aggr_state_dict = FedSecAggDP(up.global_state, kept, streams, s.ddp_mech, opt)
             else:
-                aggr_state_dict = FedSecAgg(up.global_state, kept, [data_sizes[pos] for pos in keep], streams, survivor_rescale(up.public_w, keep), opt)
-            bad = self._report_uploads('Masked uploads (%d fraction bits, threshold %d)' % (s.secagg_frac_bits, s.secagg_threshold), models,
+                aggr_state_dict = FedSecAgg(up.global_state, kept, [data_sizes[pos] for pos in keep], streams, survivor_rescale(up.public_w, keep), opt,
+                                            **({} if s.secagg_bits == 32 else {"bits": s.secagg_bits}))
+            bad = self._report_uploads('Masked uploads (%d fraction bits, threshold %d%s)'
+                                       % (s.secagg_frac_bits, s.secagg_threshold, "" if s.secagg_bits == 32 else ", %d-bit words" % s.secagg_bits), models,
                                        '; %d dropped, %d recovery streams' % (len(models) - len(keep), len(streams)), survivors,
                                        [u.code_counters for u in kept],
                                        'Client %s sent %d saturated and %d non-finite elements (clamped to the code range / sent as 0)')

@@ -778,6 +778,61 @@ int fedfr_secagg_mask_dp(unsigned* y, const float* x, const float* xi, const flo
                          unsigned long long* sqnorm, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * narrow secure aggregation — no reference counterpart.  The masked upload above is one 32-bit word per parameter: as large as the fp32
+ * state it hides.  Here a client uploads b = 8 or 16 bits per parameter and the server still learns only a sum, now in the small ring
+ * Z / 2^b, by the recipe of Kairouz, Liu, Steinke (ICML 2021, sections 4 and 5): rotate the update so that no coordinate is large, round
+ * stochastically so that the codes are unbiased, mask and sum modulo 2^b.  Block scales or indices (the compressed and top-k uploads)
+ * cannot go under masks: they are per-client side information.  A fixed public scale can.
+ * NARROW WORDS.  The constants of the format:
+ *   ROTATION BLOCK.  B = 4096 elements; n_pad = ceil(n / B) B (fedfr_rht_padded_count); elements n ... n_pad - 1 of the update are 0.
+ *   UPDATE.  u_e = x_i[e] - x[e], one fp32 subtraction, as above.
+ *   ROTATION.  v = 2^-6 H_B (D u), block by block.  D is a PUBLIC Rademacher sign: element e is negated (its sign bit flipped) when bit
+ *   e % 32 of word e / 32 of the Philox stream (rotation_seed, round, stream_id 0x52485444 "RHTD") of THE NOISE STREAM is 1 (word j =
+ *   lane j % 4 of block j / 4).  H_B is the unnormalised Walsh-Hadamard butterfly, levels h = 1, 2, 4, ..., 2048 IN THAT ORDER; a level
+ *   maps the pair (a, b) at distance h (a at an index whose bit h is clear) to (a + b, a - b), single fp32 operations.  The level order
+ *   is part of the format: any parallel decomposition that keeps it gives the same bits.  The product with 2^-6 is exact.
+ *   CODE.  t = v_e coef (one fp32 multiplication; coef = c_i of the ENCODING above);  fl = floor(t);  q = fl + [r 2^-24 < t - fl], with
+ *   t - fl one fp32 subtraction and r the top 24 bits of word e of the client's PRIVATE Philox stream (private_seed, round, stream_id
+ *   0x53525244 "SRRD"): a per-round seed the client draws and never sends.  q is clamped to +-L, L = (2^(b-1) - 1) / K (integer
+ *   division, K participants); a t that is NaN or infinite gives 0.  Both cases count in {saturated, nonfinite} as above, over the n_pad
+ *   rotated elements (one NaN in the update makes every element of its rotation block non-finite).  E[q] = t up to the
+ *   rounding of t - fl (below 2^-24 of a code, and only for |t| < 2^-24 or so): the codes are unbiased.
+ *   PACKING.  F = 32 / b codes per 32-bit word: element e is field e % F (little end first) of word e / F, as b-bit two's complement.
+ *   An upload is n_pad / F words = n_pad b / 8 bytes.
+ *   MASKS.  Packed word p takes word p of each ChaCha20 stream of THE MASK STREAM (counter0: the block of word 0; the counter check
+ *   covers n_pad / F words).  Streams are added or subtracted FIELD-WISE mod 2^b: no carry or borrow crosses a field.  The server's sum
+ *   of uploads and its recovery streams are field-wise too; the sum of K codes in +-L never wraps.
+ *   DECODE.  Every field of the unmasked sum, sign-extended, is S;  s = float(S) 2^-f (exact);  u' = D (2^-6 H_B s): the same butterfly
+ *   (the transform is its own inverse up to the scale);  out[e] = x[e] + rescale u'_e for e < n (one fp32 multiplication, one addition;
+ *   u' alone when x is NULL); elements e >= n are dropped.
+ * Field-wise addition is associative and commutative: the sum has ONE bit pattern whatever the order, the chaining or the grid.
+ * tests/secagg_narrow_cases.py restates all of it in numpy, bit for bit.  How to choose f: INTEGRATION.md section 19.
+ * ------------------------------------------------------------------------------------------------ */
+size_t fedfr_rht_padded_count(size_t n);
+/* The rotation alone: dst[0 .. n_pad) = 2^-6 H (D src) (inverse = 0) or D (2^-6 H src) (inverse != 0), src[e] = 0 for e >= n.  dst holds
+ * n_pad floats, src n; both 16-byte aligned and distinct; n = 0 is a no-op. */
+int fedfr_rht_fill(float* dst, const float* src, size_t n, unsigned long long rotation_seed, unsigned long long round, int inverse,
+                   void* stream);
+/* y[0 .. n_pad / F) = pack(code(rotate(xi - x))) (+) the k streams (0 <= k <= 32), as above, with L = (2^(bits-1) - 1) / participants.
+ * counters: DEVICE int32[2] {saturated, nonfinite}, added to (atomically), may be NULL.  One pass: x and xi are read once, y is written
+ * once, nothing else touches memory.  bits 8 or 16; 1 <= participants <= 2^(bits-1) - 1; y, x, xi 16-byte aligned and distinct; n = 0 is
+ * a no-op.  Bad arguments, and a counter0 whose last block would pass 2^32 - 1, return FEDFR_ERR_ARG before anything is launched. */
+int fedfr_secagg_mask_narrow(unsigned* y, const float* x, const float* xi, float coef, int participants, int bits,
+                             unsigned long long rotation_seed, unsigned long long private_seed, unsigned long long round,
+                             const unsigned* keys, const unsigned* nonces, const int* signs, int k, unsigned counter0, size_t n,
+                             int* counters, void* stream);
+/* One pass of the narrow aggregate over ku uploads (HOST array of 0 ... 8 device pointers, n_pad / F words each) and k recovery streams
+ * (0 ... 32), ku + k > 0, all sums field-wise:
+ *   S = (first ? 0 : acc) (+) sum ys (+) sum_r sign_r m_r;   last ? out = DECODE(S) : acc = S.
+ * Chained as fedfr_secagg_aggregate (acc: n_pad / F words; with one call first = last = 1 and acc may be NULL).  x is read on the last
+ * pass only; out may be x.  frac_bits 0 ... 30, rescale finite; all buffers 16-byte aligned; n = 0 is a no-op.  Bad arguments and a
+ * counter overflow return FEDFR_ERR_ARG before anything is launched. */
+int fedfr_secagg_aggregate_narrow(float* out, const float* x, unsigned* acc, const unsigned* const* ys, int ku, int bits,
+                                  unsigned long long rotation_seed, unsigned long long round, const unsigned* keys, const unsigned* nonces,
+                                  const int* signs, int k, unsigned counter0, int frac_bits, float rescale, size_t n, int first, int last,
+                                  void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * robust aggregation — no reference counterpart: every rule above is a weighted sum, so one client that returns a poisoned, diverged or NaN
  * state moves (or wipes out) the global model.  Coordinate-wise trimmed mean / median (Yin et al., 2018) and Krum / Multi-Krum (Blanchard
  * et al., 2017) over k <= 32 flat fp32 client states (HOST arrays of k device pointers, as fedfr_fedavg_multi), as streaming passes.
