@@ -19,10 +19,11 @@ from __future__ import annotations
 
 import ctypes
 import logging
+import math
 import os
 import threading
 from collections import OrderedDict
-from typing import Iterable, Optional, Tuple
+from typing import Iterable, NamedTuple, Optional, Tuple
 
 import torch
 from torch import nn
@@ -276,12 +277,37 @@ class _LossScaleGuard:
         return hit
 
 
+class DriftTerms(NamedTuple):
+    """What a client adds to the backbone's update against client drift (``fedfr_sgd_step_drift``): ``anchor`` with ``prox`` is FedProx's
+    proximal pull prox (p - anchor) towards the round's global parameters, ``corr`` SCAFFOLD's correction c - c_i.  Two fp32 device tensors
+    of the backbone's ``trainable_count()`` elements, or None for a term that is off; head parameters are client-local and get neither."""
+    anchor: Optional[torch.Tensor] = None
+    prox: float = 0.0
+    corr: Optional[torch.Tensor] = None
+
+
+def step_mass_term(lr: float, mu: float, k: int) -> float:
+    """lr_k (1 - mu^k) / (1 - mu) = lr_k (1 + mu + ... + mu^(k-1)) in fp64: what step k = 1, 2, ... of a heavy-ball run adds to the total
+    weight of its gradients (``_BackboneTrainer.step_mass``; derivation: DESIGN.md section 3.30).  mu = 0: lr_k."""
+    lr, mu = float(lr), float(mu)
+    return lr * (float(k) if mu == 1.0 else (1.0 - mu ** k) / (1.0 - mu))
+
+
+def check_prox_mu(v, who: str) -> float:
+    """``args.prox_mu`` as a float: absent, None or 0 is off; a negative or non-finite value is refused"""
+    v = float(v or 0.0)
+    if not (v >= 0.0 and math.isfinite(v)):
+        raise ValueError("%s: prox_mu must be a finite number >= 0 (got %r)" % (who, v))
+    return v
+
+
 class _BackboneTrainer(_LossScaleGuard):
     """The backbone half of every fused train step: ``fedfr_net_forward``, one ``fedfr_net_backward2*`` call from d(loss)/d(features)
     (weight-gradient GEMMs on the aux stream), the flat SGD update of the backbone and the rebuild of its dgrad-layout weight copies.
     One optimiser lifetime (= one FL round for one client: the reference re-creates SGD every round, F8)."""
 
-    def __init__(self, backbone: "backbones.IResNet", lr: float, momentum: float, weight_decay: float, aux_slot: int):
+    def __init__(self, backbone: "backbones.IResNet", lr: float, momentum: float, weight_decay: float, aux_slot: int,
+                 drift: Optional[DriftTerms] = None):
         bb = self.bb = backbone
         self.lr, self.mu, self.wd = float(lr), float(momentum), float(weight_decay)
         bb._ensure_device_state()
@@ -302,6 +328,23 @@ class _BackboneTrainer(_LossScaleGuard):
         self._grads_scaled = False          # fp16-storage library: the rest of the gradient buffer still carries the loss scale ...
         self._scale_used = 1.0              # ... namely this one (another trainer's poll may lower the device's scale before the update)
         self._init_loss_scale(bb.device)
+        # drift terms of the backbone update (None: today's calls and nothing else), and the weight heavy-ball momentum has given the
+        # gradients of this run so far: step_mass = sum_k lr_k (1 - mu^k) / (1 - mu) over the steps k = 1, 2, ... in fp64
+        self.drift = self._check_drift(drift)
+        self.step_mass = 0.0
+        self._steps = 0
+
+    def _check_drift(self, drift):
+        if drift is None or (drift.anchor is None and drift.corr is None and not drift.prox):
+            return None
+        prox = float(drift.prox)
+        if (drift.anchor is None) != (prox == 0.0) or not math.isfinite(prox):
+            raise ValueError("%s: DriftTerms.anchor and a finite non-zero prox go together (got prox %r)" % (type(self).__name__, drift.prox))
+        for t, what in ((drift.anchor, "anchor"), (drift.corr, "corr")):
+            if t is not None and (_C.require_gpu_tensor(t, f32, "DriftTerms." + what).numel() != self.n_train or t.device != self.mom.device):
+                raise ValueError("%s: DriftTerms.%s must hold the backbone's %d trainable elements on %s"
+                                 % (type(self).__name__, what, self.n_train, self.mom.device))
+        return DriftTerms(drift.anchor, prox, drift.corr)
 
     def set_lr(self, lr: float):
         self.lr = float(lr)
@@ -362,7 +405,11 @@ class _BackboneTrainer(_LossScaleGuard):
             return
         done = ctypes.c_longlong(0)
         sgd = (self.mom.data_ptr(), self.lr, self.mu, self.wd, 1 if self.first else 0)
-        if self.guarded:
+        if self.drift is not None:
+            d = self.drift
+            _C.call("fedfr_net_backward2_sgd_drift", *args, *sgd, 1.0 / S if self.guarded else 1.0,
+                    self._overflow.data_ptr() if self.guarded else None, _C.ptr(d.anchor), d.prox, _C.ptr(d.corr), ctypes.byref(done), st, aux)
+        elif self.guarded:
             _C.call("fedfr_net_backward2_sgd_scaled", *args, *sgd, 1.0 / S, self._overflow.data_ptr(), ctypes.byref(done), st, aux)
         else:
             _C.call("fedfr_net_backward2_sgd", *args, *sgd, ctypes.byref(done), st, aux)
@@ -374,7 +421,10 @@ class _BackboneTrainer(_LossScaleGuard):
         n = self.n_train if self._sgd_done_from is None else self._sgd_done_from
         gscale = 1.0 / self._scale_used if self._grads_scaled else 1.0
         self._sgd_done_from, self._grads_scaled = None, False
-        if n > 0:
+        if n > 0 and self.drift is not None:
+            ops.sgd_step(bb._flat_params, bb._flat_grads, self.mom, bb._shadow, n, self.lr, self.mu, self.wd, self.first, gscale,
+                         self._sgd_overflow, *self.drift)
+        elif n > 0:
             ops.sgd_step(bb._flat_params, bb._flat_grads, self.mom, bb._shadow, n, self.lr, self.mu, self.wd, self.first, gscale,
                          self._sgd_overflow)
 
@@ -392,6 +442,8 @@ class _BackboneTrainer(_LossScaleGuard):
         else:
             bb.refresh_shadows(False)
         self.first = False
+        self._steps += 1
+        self.step_mass += step_mass_term(self.lr, self.mu, self._steps)
 
 
 class FusedTrainer(_BackboneTrainer):
@@ -400,7 +452,8 @@ class FusedTrainer(_BackboneTrainer):
     """
 
     def __init__(self, backbone: "backbones.IResNet", fc, loss_name: str = "CosFace", s: float = 30.0,
-                 m: float = 0.4, lr: float = 0.1, momentum: float = 0.9, weight_decay: float = 5e-4, aux_slot: int = 0):
+                 m: float = 0.4, lr: float = 0.1, momentum: float = 0.9, weight_decay: float = 5e-4, aux_slot: int = 0,
+                 drift: Optional[DriftTerms] = None):
         """``fc``: a dense class-weight tensor [C, 512] (FC_module.fc.data), or a ``PartialFC`` instance — then the head is the
         sampled / class-sharded softmax (its margin comes from the PartialFC's own ``margin_softmax``)."""
         from .partial_fc import PartialFC
@@ -412,7 +465,7 @@ class FusedTrainer(_BackboneTrainer):
         self.fc = _C.require_gpu_tensor(fc, f32, "fc weight")
         self.arc = loss_name == "ArcFace"
         self.s, self.m = float(s), float(m)
-        super().__init__(backbone, lr, momentum, weight_decay, aux_slot)
+        super().__init__(backbone, lr, momentum, weight_decay, aux_slot, drift)
         if self.pfc is None:
             self.fc_mom = torch.empty_like(self.fc)
             self.fc_grad = torch.empty_like(self.fc)
@@ -505,12 +558,12 @@ class FusedHeadTrainer(_BackboneTrainer):
     SGD kernel (torch.optim.SGD semantics: coupled weight decay, momentum buffer created on first use)."""
 
     def __init__(self, backbone: "backbones.IResNet", head_params: Iterable[nn.Parameter], lr: float = 0.1,
-                 momentum: float = 0.9, weight_decay: float = 5e-4, aux_slot: int = 0):
+                 momentum: float = 0.9, weight_decay: float = 5e-4, aux_slot: int = 0, drift: Optional[DriftTerms] = None):
         self.head_params = list(head_params)
         for hp in self.head_params:
             _C.require_gpu_tensor(hp.data, f32, "head parameter")
         self.head_mom = {}
-        super().__init__(backbone, lr, momentum, weight_decay, aux_slot)
+        super().__init__(backbone, lr, momentum, weight_decay, aux_slot, drift)
 
     def _backward_and_update(self, plan, imgs, dfeats):
         """backbone backward from d(loss)/d(features), then opt.step() for the backbone (flat) and every head parameter with a grad."""
@@ -580,7 +633,7 @@ class FusedBranchTrainer(_BackboneTrainer):
     def __init__(self, backbone: "backbones.IResNet", fc_module: FC_module, bce_module: Optional[BCE_module] = None,
                  loss_name: str = "CosFace", s: float = 30.0, m: float = 0.4, detach: bool = False, mu: float = 0.0,
                  temperature: float = 0.5, bce_weight: float = 10.0, bce_r: float = 30.0, bce_lambda: float = 0.7, lr: float = 0.1,
-                 momentum: float = 0.9, weight_decay: float = 5e-4, aux_slot: int = 0):
+                 momentum: float = 0.9, weight_decay: float = 5e-4, aux_slot: int = 0, drift: Optional[DriftTerms] = None):
         if loss_name not in ("CosFace", "ArcFace"):
             raise ValueError("loss must be CosFace or ArcFace")
         self.arc, self.s, self.m = loss_name == "ArcFace", float(s), float(m)
@@ -603,7 +656,7 @@ class FusedBranchTrainer(_BackboneTrainer):
         self.head_grads = {}
         self.head_mom = {}
         self._ws = None
-        super().__init__(backbone, lr, momentum, weight_decay, aux_slot)
+        super().__init__(backbone, lr, momentum, weight_decay, aux_slot, drift)
 
     def _grad(self, p):
         g = self.head_grads.get(p)
@@ -684,8 +737,9 @@ class ShardedHeadTrainer(FusedHeadTrainer):
     """
 
     def __init__(self, backbone, pfc, bce_module=None, id_base: int = 0, lr: float = 0.1, momentum: float = 0.9,
-                 weight_decay: float = 5e-4, bce_weight: float = 10.0, aux_slot: int = 0):
-        super().__init__(backbone, list(bce_module.parameters()) if bce_module is not None else [], lr, momentum, weight_decay, aux_slot=aux_slot)
+                 weight_decay: float = 5e-4, bce_weight: float = 10.0, aux_slot: int = 0, drift: Optional[DriftTerms] = None):
+        super().__init__(backbone, list(bce_module.parameters()) if bce_module is not None else [], lr, momentum, weight_decay, aux_slot=aux_slot,
+                         drift=drift)
         self.pfc, self.bce_module, self.id_base, self.bce_weight = pfc, bce_module, int(id_base), float(bce_weight)
         self.bce_loss = losses.BCE_loss() if bce_module is not None else None
         if bce_module is not None:
@@ -904,12 +958,58 @@ class Client(object):
         if use_bce:
             torch.save(portable_state_dict(self.bce_module), os.path.join(out, "bce_module.pth"))
 
+    def _round_drift(self, backbone, who: str) -> Optional[DriftTerms]:
+        """The drift terms of this round's backbone updates, from the global state just loaded into ``backbone``; None (today's trainers,
+        call for call) unless ``args.prox_mu`` > 0 or the server runs SCAFFOLD (``self.scaffold_on``, with its control variate
+        ``self.scaffold_c``: None while that is still zero).  FedProx: anchor = a clone of the trainable range of the global parameters,
+        prox = prox_mu.  SCAFFOLD: corr = c - c_i, None while both are zero (the first round); the global parameters are kept for the
+        end-of-round pass either way."""
+        prox = check_prox_mu(getattr(self.args, "prox_mu", 0), who)
+        scaffold = bool(getattr(self, "scaffold_on", False))
+        self._round_x = None
+        if not prox and not scaffold:
+            return None
+        n = backbone.trainable_count()
+        x = self._round_x = backbone.flat_state()[0][:n].clone()
+        corr = None
+        if scaffold:
+            c, ci = getattr(self, "scaffold_c", None), getattr(self, "scaffold_ci", None)
+            if c is not None and ci is not None:
+                corr = torch.sub(c, ci)
+            elif c is not None:
+                corr = c.clone()
+            elif ci is not None:
+                corr = -ci
+        if not prox and corr is None:
+            return None
+        return DriftTerms(x if prox else None, prox, corr)
+
+    def _finish_drift(self, backbone, trainer):
+        """SCAFFOLD's end-of-round pass (``ops.scaffold_control``): c_i <- c_i - c + (x - y_i) / step_mass in place, and the control update
+        dc = c_i+ - c_i the server collects with ``get_control_update()``.  Nothing under FedProx alone."""
+        x, self._round_x = getattr(self, "_round_x", None), None
+        if not getattr(self, "scaffold_on", False):
+            return
+        n = trainer.n_train
+        if getattr(self, "scaffold_ci", None) is None:
+            self.scaffold_ci = torch.zeros(n, dtype=f32, device=x.device)
+        if trainer.step_mass > 0.0:
+            self.scaffold_dc = ops.scaffold_control(self.scaffold_ci, x, backbone.flat_state()[0][:n], trainer.drift.corr if trainer.drift else None,
+                                                    trainer.step_mass)
+        else:                                          # a client that took no step has nothing to report
+            self.scaffold_dc = torch.zeros_like(self.scaffold_ci)
+
+    def get_control_update(self):
+        """SCAFFOLD: dc_i = c_i+ - c_i of the round just trained, fp32 [n_train] on the device (None before the first SCAFFOLD round)"""
+        return getattr(self, "scaffold_dc", None)
+
     @_C.on_device(lambda self: self.device)
     def train(self, start_epoch=0, callback_verification=None):
         """reference client.py:511-571."""
         backbone = self._get_backbone()
         backbone.load_state_dict(self.backbone_state_dict)
         backbone.train()
+        drift = self._round_drift(backbone, "Client.train")
         self.fc_module.to(self.device)
         self.fc_module.train()
         if callback_verification is not None and start_epoch == 0:             # client.py:523-525
@@ -917,7 +1017,7 @@ class Client(object):
             callback_verification.veri_test(backbone, -1, self.target_ID, self.cid)
         trainer = FusedTrainer(backbone, self.fc_module.fc.data, self.loss_name, 30.0, 0.4,
                                lr=cfg.lr_func(start_epoch) * cfg.lr, momentum=cfg.momentum, weight_decay=cfg.weight_decay,
-                               aux_slot=getattr(self, "slot", 0))
+                               aux_slot=getattr(self, "slot", 0), **({} if drift is None else {"drift": drift}))
         loss_meter = AverageMeter()
         pending = []
         for epoch in range(start_epoch, start_epoch + self.local_epoch):
@@ -935,6 +1035,7 @@ class Client(object):
         for l in pending:
             loss_meter.update(l.item(), 1)
         trainer.finish()
+        self._finish_drift(backbone, trainer)
         self.loss_meter = loss_meter
         if callback_verification is not None:                                   # client.py:562-566
             self._local_verification(callback_verification, backbone, start_epoch + self.local_epoch - 1)
@@ -1016,6 +1117,8 @@ class Client(object):
         backbone = self._get_backbone()
         backbone.load_state_dict(self.backbone_state_dict)
         backbone.train()
+        drift = self._round_drift(backbone, "Client.train_with_public_data")
+        drift_kw = {} if drift is None else {"drift": drift}
         self.fc_module.update_with_pretrain(pretrained_fc)                         # [local | public] rows (client.py:312)
         self.fc_module.train()
         self.fc_module.to(self.device)
@@ -1042,10 +1145,10 @@ class Client(object):
                                          self.margin_softmax.s, self.margin_softmax.m, detach=detach, mu=cfg.mu if use_con else 0.0,
                                          temperature=self.temperature if use_con else 0.5, bce_weight=10.0, bce_r=self.bce_loss.r if use_bce else 30.0,
                                          bce_lambda=self.bce_loss.lambda_ if use_bce else 0.7, lr=cfg.lr, momentum=cfg.momentum,
-                                         weight_decay=cfg.weight_decay, aux_slot=getattr(self, "slot", 0))
+                                         weight_decay=cfg.weight_decay, aux_slot=getattr(self, "slot", 0), **drift_kw)
         else:
             trainer = FusedHeadTrainer(backbone, head_params, lr=cfg.lr, momentum=cfg.momentum, weight_decay=cfg.weight_decay,
-                                       aux_slot=getattr(self, "slot", 0))
+                                       aux_slot=getattr(self, "slot", 0), **drift_kw)
         state = {}
         head_loss = public_head_loss(self.margin_softmax, self.fc_module, self.bce_module if use_bce else None,
                                      self.bce_loss if use_bce else None, detach, self.reweight_cosface if reweight else None,
@@ -1081,6 +1184,7 @@ class Client(object):
                     drain()
         drain()
         trainer.finish()
+        self._finish_drift(backbone, trainer)
         self.cos_meter, self.con_meter, self.bce_meter = cos_meter, con_meter, bce_meter
         self.loss_meter = loss_meter
         if callback_verification is not None:                                   # client.py:478-488

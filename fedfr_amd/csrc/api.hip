@@ -371,6 +371,27 @@ int fedfr_net_backward2_sgd_scaled(const fedfr_net_t* n, const float* x, const f
   *done_from = sg.done_from;
   return rc;
 }
+// the drift-term arguments of the *_drift entry points, refused before anything is launched (fedfr_hip.h: DRIFT TERMS)
+static int drift_args_ok(const char* who, const float* anchor, float prox, const float* corr) {
+  FEDFR_REQUIRE(anchor || corr, "%s: neither anchor nor corr (the entry point without _drift is the one to call)", who);
+  FEDFR_REQUIRE(anchor || prox == 0.f, "%s: prox = %g without an anchor", who, (double)prox);
+  FEDFR_REQUIRE(!anchor || (prox != 0.f && prox - prox == 0.f), "%s: an anchor needs a finite non-zero prox (got %g)", who, (double)prox);
+  FEDFR_REQUIRE((((uintptr_t)anchor | (uintptr_t)corr) & 15) == 0, "%s: anchor / corr must be 16-byte aligned", who);
+  return FEDFR_OK;
+}
+int fedfr_net_backward2_sgd_drift(const fedfr_net_t* n, const float* x, const float* dfeats, float* params, uint16_t* shadow, void* act,
+                                  void* ws, float* grads, float* momentum, float lr, float mu, float wd, int first, float grad_scale,
+                                  unsigned* overflow, const float* anchor, float prox, const float* corr, long long* done_from, void* stream,
+                                  void* aux_stream) {
+  FEDFR_REQUIRE(aux_stream == nullptr || aux_stream != stream, "net_backward2_sgd_drift: aux_stream must differ from stream (pass NULL for single-stream)");
+  FEDFR_REQUIRE(momentum && done_from, "net_backward2_sgd_drift: null momentum buffer / done_from");
+  FEDFR_REQUIRE(grad_scale > 0.f, "net_backward2_sgd_drift: grad_scale must be positive");
+  FEDFR_TRY(drift_args_ok("net_backward2_sgd_drift", anchor, prox, corr));
+  NetSgd sg{params, BFM(shadow), momentum, lr, mu, wd, first, 0, grad_scale, overflow, anchor, prox, corr};
+  const int rc = net_backward(n, x, dfeats, params, BF(shadow), (unsigned char*)act, (unsigned char*)ws, grads, ST(stream), ST(aux_stream), &sg);
+  *done_from = sg.done_from;
+  return rc;
+}
 
 // ---- fp32 validation path (net_f32.hip) --------------------------------------------------------------------------------------
 size_t fedfr_net_f32_arena_floats(const fedfr_net_t* n) { return n ? net_f32_arena_floats(n) : 0; }
@@ -887,6 +908,16 @@ int fedfr_sgd_step_scaled(float* params, float* grads, float* buf, uint16_t* sha
                           int first_step, float grad_scale, unsigned* overflow, void* stream) {
   FEDFR_REQUIRE(grad_scale > 0.f, "sgd_step_scaled: grad_scale must be positive");
   return optim_sgd(params, grads, buf, BFM(shadow), n, lr, momentum, weight_decay, first_step, ST(stream), grad_scale, overflow);
+}
+int fedfr_sgd_step_drift(float* params, float* grads, float* buf, uint16_t* shadow, size_t n, float lr, float momentum, float weight_decay,
+                         int first_step, float grad_scale, unsigned* overflow, const float* anchor, float prox, const float* corr, void* stream) {
+  FEDFR_REQUIRE(grad_scale > 0.f, "sgd_step_drift: grad_scale must be positive");
+  FEDFR_REQUIRE(n > 0, "sgd_step_drift: n = 0");
+  FEDFR_TRY(drift_args_ok("sgd_step_drift", anchor, prox, corr));
+  return optim_sgd(params, grads, buf, BFM(shadow), n, lr, momentum, weight_decay, first_step, ST(stream), grad_scale, overflow, anchor, prox, corr);
+}
+int fedfr_scaffold_control(float* c_i, float* dc, const float* x, const float* y, const float* corr, float inv_mass, size_t n, void* stream) {
+  return optim_scaffold_control(c_i, dc, x, y, corr, inv_mass, n, ST(stream));
 }
 int fedfr_fedavg_axpy(float* dst, const float* src, float w, size_t n, int accumulate, void* stream) {
   return optim_fedavg_axpy(dst, src, w, n, accumulate, ST(stream));

@@ -3,7 +3,10 @@
 #include "common.h"
 
 int optim_sgd(float* p, float* g, float* buf, bf16_t* shadow, size_t n, float lr, float mu, float wd, int first,
-              hipStream_t st, float gscale = 1.f, unsigned* overflow = nullptr);   // gscale != 1: g holds gradient / gscale; it is multiplied in the kernel and stored back
+              hipStream_t st, float gscale = 1.f, unsigned* overflow = nullptr,    // gscale != 1: g holds gradient / gscale; it is multiplied in the kernel and stored back
+              const float* anchor = nullptr, float prox = 0.f, const float* corr = nullptr);      // DRIFT TERMS (fedfr_hip.h): d += prox (p - anchor); d += corr
+// SCAFFOLD's end-of-round pass: cn = fma(inv_mass, x - y, -corr); dc = cn - c_i; c_i = cn (corr null: +0.0)
+int optim_scaffold_control(float* ci, float* dc, const float* x, const float* y, const float* corr, float inv_mass, size_t n, hipStream_t st);
 int optim_fedavg_axpy(float* dst, const float* src, float w, size_t n, int accumulate, hipStream_t st);
 int optim_fedavg_multi(float* dst, const float* const* srcs, const float* ws, int k, size_t n, int accumulate, hipStream_t st);
 size_t optim_fedopt_sqnorm_ws_bytes(int k, size_t n);

@@ -10,11 +10,38 @@
 // SGD: g += wd*p ; buf = first ? g : mu*buf + g ; p -= lr*buf ; optional bf16 shadow of the new p.
 // Op order / fusion mirrors torch's vectorised CPU kernels (alpha-adds are fmadd, mul_ then add_ are two roundings).
 // ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float sgd_one(float p, float g, float& buf, float lr, float mu, float wd, int first) {
-  const float d = fmaf(wd, p, g);                                  // grad.add(param, alpha=wd)   (fmadd in torch)
+// DRIFT TERMS (include/fedfr_hip.h): with ANCHOR the proximal pull a (p - x) of FedProx, with CORR the control-variate correction c - c_i of
+// SCAFFOLD, both added to the decayed gradient BEFORE the momentum: d1 = fma(a, fsub(p, x), d0); d = fadd(d1, corr).  Without them (the two
+// instantiations training has always run) the function is the three operations it has always been.
+template <bool ANCHOR, bool CORR>
+__device__ __forceinline__ float sgd_one(float p, float g, float& buf, float lr, float mu, float wd, int first, float a, float x, float c) {
+  float d = fmaf(wd, p, g);                                        // grad.add(param, alpha=wd)   (fmadd in torch)
+  if (ANCHOR) d = fmaf(a, __fsub_rn(p, x), d);
+  if (CORR) d = __fadd_rn(d, c);
   const float b = first ? d : __fadd_rn(__fmul_rn(buf, mu), d);    // buf.mul_(mu).add_(d)        (two roundings)
   buf = b;
   return fmaf(-lr, b, p);                                          // param.add_(buf, alpha=-lr)  (fmadd in torch)
+}
+
+// vector i / element i of a drift stream (anchor, corr): read-only, re-read every step of the round.  FEDFR_DRIFT_LD_ONCE selects the
+// non-temporal load (multi_state.h: ld_once); which of the two is kept and why: DESIGN.md section 3.30
+#ifndef FEDFR_DRIFT_LD_ONCE
+#define FEDFR_DRIFT_LD_ONCE 0
+#endif
+__device__ __forceinline__ float4 drift_ld4(const float* __restrict__ s, size_t i) {
+#if FEDFR_DRIFT_LD_ONCE
+  const fvec<4> v = ld_once<4>(s, i);
+  return make_float4(v.x, v.y, v.z, v.w);
+#else
+  return reinterpret_cast<const float4*>(s)[i];
+#endif
+}
+__device__ __forceinline__ float drift_ld1(const float* __restrict__ s, size_t i) {
+#if FEDFR_DRIFT_LD_ONCE
+  return __builtin_nontemporal_load(s + i);
+#else
+  return s[i];
+#endif
 }
 
 // UNSCALE: the gradient buffer holds gs^-1 x the gradient (static loss scale of the fp16-storage build); the kernel multiplies by gs
@@ -22,16 +49,21 @@ __device__ __forceinline__ float sgd_one(float p, float g, float& buf, float lr,
 // torch.cuda.amp.GradScaler.step does for the reference's fp16 path, client.py:394-396, without its host synchronisation): an element whose
 // gradient is not finite is NOT updated (parameter, momentum and mirror keep their values; on the first step its momentum starts at 0) and
 // *ovf is set, so one overflowing pass cannot poison the weights; the host reads the word when it next synchronises and lowers the scale.
-template <bool UNSCALE>
+// ANCHOR / CORR: one more read-only stream each (anchor with its coefficient prox); the guard looks at the gradient alone, whatever they hold.
+template <bool UNSCALE, bool ANCHOR, bool CORR>
 __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ buf,
                                                   bf16_t* __restrict__ shadow, size_t n, float lr, float mu, float wd, int first, float gs,
-                                                  unsigned* __restrict__ ovf) {
+                                                  unsigned* __restrict__ ovf, const float* __restrict__ anchor, float prox,
+                                                  const float* __restrict__ corr) {
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   const size_t n4 = n / 4;
   bool bad = false;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
     float4 pv = reinterpret_cast<float4*>(p)[i];
     float4 gv = reinterpret_cast<const float4*>(g)[i];
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 xv = ANCHOR ? drift_ld4(anchor, i) : zero;
+    const float4 cv = CORR ? drift_ld4(corr, i) : zero;
     if (UNSCALE) {
       gv.x *= gs; gv.y *= gs; gv.z *= gs; gv.w *= gs;
       reinterpret_cast<float4*>(g)[i] = gv;
@@ -39,19 +71,19 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, float* 
     float4 bv = first ? make_float4(0.f, 0.f, 0.f, 0.f) : reinterpret_cast<float4*>(buf)[i];
     if (UNSCALE) {
       const float4 p0 = pv, b0 = bv;
-      pv.x = sgd_one(pv.x, gv.x, bv.x, lr, mu, wd, first);
-      pv.y = sgd_one(pv.y, gv.y, bv.y, lr, mu, wd, first);
-      pv.z = sgd_one(pv.z, gv.z, bv.z, lr, mu, wd, first);
-      pv.w = sgd_one(pv.w, gv.w, bv.w, lr, mu, wd, first);
+      pv.x = sgd_one<ANCHOR, CORR>(pv.x, gv.x, bv.x, lr, mu, wd, first, prox, xv.x, cv.x);
+      pv.y = sgd_one<ANCHOR, CORR>(pv.y, gv.y, bv.y, lr, mu, wd, first, prox, xv.y, cv.y);
+      pv.z = sgd_one<ANCHOR, CORR>(pv.z, gv.z, bv.z, lr, mu, wd, first, prox, xv.z, cv.z);
+      pv.w = sgd_one<ANCHOR, CORR>(pv.w, gv.w, bv.w, lr, mu, wd, first, prox, xv.w, cv.w);
       if (!isfinite(gv.x)) { pv.x = p0.x; bv.x = b0.x; bad = true; }
       if (!isfinite(gv.y)) { pv.y = p0.y; bv.y = b0.y; bad = true; }
       if (!isfinite(gv.z)) { pv.z = p0.z; bv.z = b0.z; bad = true; }
       if (!isfinite(gv.w)) { pv.w = p0.w; bv.w = b0.w; bad = true; }
     } else {
-      pv.x = sgd_one(pv.x, gv.x, bv.x, lr, mu, wd, first);
-      pv.y = sgd_one(pv.y, gv.y, bv.y, lr, mu, wd, first);
-      pv.z = sgd_one(pv.z, gv.z, bv.z, lr, mu, wd, first);
-      pv.w = sgd_one(pv.w, gv.w, bv.w, lr, mu, wd, first);
+      pv.x = sgd_one<ANCHOR, CORR>(pv.x, gv.x, bv.x, lr, mu, wd, first, prox, xv.x, cv.x);
+      pv.y = sgd_one<ANCHOR, CORR>(pv.y, gv.y, bv.y, lr, mu, wd, first, prox, xv.y, cv.y);
+      pv.z = sgd_one<ANCHOR, CORR>(pv.z, gv.z, bv.z, lr, mu, wd, first, prox, xv.z, cv.z);
+      pv.w = sgd_one<ANCHOR, CORR>(pv.w, gv.w, bv.w, lr, mu, wd, first, prox, xv.w, cv.w);
     }
     reinterpret_cast<float4*>(p)[i] = pv;
     reinterpret_cast<float4*>(buf)[i] = bv;
@@ -67,7 +99,7 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, float* 
     float gi = g[i];
     if (UNSCALE) { gi *= gs; g[i] = gi; }
     const float p0 = p[i], b0 = b;
-    float v = sgd_one(p0, gi, b, lr, mu, wd, first);
+    float v = sgd_one<ANCHOR, CORR>(p0, gi, b, lr, mu, wd, first, prox, ANCHOR ? drift_ld1(anchor, i) : 0.f, CORR ? drift_ld1(corr, i) : 0.f);
     if (UNSCALE && !isfinite(gi)) { v = p0; b = b0; bad = true; }
     p[i] = v;
     buf[i] = b;
@@ -76,19 +108,62 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, float* 
   if (UNSCALE && bad && ovf) *ovf = 1u;          // (every writer stores the same value)
 }
 
+// THE route to each of the eight instantiations: (guarded, anchor, corr) -> sgd_kernel<...>.  anchor / corr null: today's two kernels
 int optim_sgd(float* p, float* g, float* buf, bf16_t* shadow, size_t n, float lr, float mu, float wd, int first,
-              hipStream_t st, float gscale, unsigned* overflow) {
+              hipStream_t st, float gscale, unsigned* overflow, const float* anchor, float prox, const float* corr) {
   FEDFR_REQUIRE(p && g && buf && n > 0, "sgd: bad args");
   FEDFR_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf) & 15) == 0, "sgd: buffers must be 16-byte aligned");
+  FEDFR_REQUIRE((((uintptr_t)anchor | (uintptr_t)corr) & 15) == 0, "sgd: anchor / corr must be 16-byte aligned");
+  FEDFR_REQUIRE(anchor ? (prox != 0.f && prox - prox == 0.f) : prox == 0.f, "sgd: the proximal coefficient (%g) and the anchor go together", (double)prox);
   const size_t work = n / 4 + 1;
   const int grid = (int)((work + 255) / 256 > 4096 ? 4096 : (work + 255) / 256);
   const bool unscale = gscale != 1.f || overflow != nullptr;
-  ProfScope prof(26, (double)n * (first ? 16.0 : 20.0) + (shadow ? 2.0 * n : 0.0) + (unscale ? 4.0 * n : 0.0), st);      // p, g (, buf) read; p, buf (, bf16 mirror, unscaled g) written
-  if (unscale)
-    hipLaunchKernelGGL(sgd_kernel<true>, dim3(grid), dim3(256), 0, st, p, g, buf, shadow, n, lr, mu, wd, first, gscale, overflow);
-  else
-    hipLaunchKernelGGL(sgd_kernel<false>, dim3(grid), dim3(256), 0, st, p, g, buf, shadow, n, lr, mu, wd, first, 1.f, nullptr);
+  ProfScope prof(26, (double)n * (first ? 16.0 : 20.0) + (shadow ? 2.0 * n : 0.0) + (unscale ? 4.0 * n : 0.0) + (anchor ? 4.0 * n : 0.0) +
+                         (corr ? 4.0 * n : 0.0), st);      // p, g (, buf, anchor, corr) read; p, buf (, bf16 mirror, unscaled g) written
+  dispatch_int<0, 7>((unscale ? 1 : 0) | (anchor ? 2 : 0) | (corr ? 4 : 0), [&](auto kc) {
+    constexpr int V = decltype(kc)::value;
+    constexpr bool U = (V & 1) != 0;
+    hipLaunchKernelGGL((sgd_kernel<U, (V & 2) != 0, (V & 4) != 0>), dim3(grid), dim3(256), 0, st, p, g, buf, shadow, n, lr, mu, wd, first,
+                       U ? gscale : 1.f, U ? overflow : (unsigned*)nullptr, anchor, prox, corr);
+  });
   FEDFR_LAUNCH_CHECK("sgd");
+  return FEDFR_OK;
+}
+
+// SCAFFOLD's end-of-round pass (option II of Karimireddy et al.): with x the round's global parameters, y the client's trained ones, corr the
+// c - c_i it trained with (null: +0.0) and inv_mass = fl32(1 / step_mass),
+//   t = fsub(x, y);  cn = fma(inv_mass, t, -corr);  dc = fsub(cn, c_i);  c_i = cn
+// one pass, one rounding per operation, on the streaming skeleton of multi_state.h (x, y, corr are read once)
+template <bool CORR>
+__global__ __launch_bounds__(MULTI_STATE_BLOCK) void scaffold_control_kernel(float* __restrict__ ci, float* __restrict__ dc, const float* __restrict__ x,
+                                                                            const float* __restrict__ y, const float* __restrict__ corr,
+                                                                            float inv_mass, size_t n) {
+  for_each_vec_then_tail<4>(n, [&](auto width, size_t i) {
+    constexpr int W = decltype(width)::value;
+    const fvec<W> xv = ld_once<W>(x, i), yv = ld_once<W>(y, i);
+    fvec<W> cv = vec_at<W>(ci, i), dv;
+    fvec<W> rv;
+    if constexpr (CORR) rv = ld_once<W>(corr, i);
+#pragma unroll
+    for (int c = 0; c < W; ++c) {
+      float r = 0.f;
+      if constexpr (CORR) r = rv[c];
+      const float cn = fmaf(inv_mass, __fsub_rn(xv[c], yv[c]), -r);
+      dv[c] = __fsub_rn(cn, cv[c]);
+      cv[c] = cn;
+    }
+    vec_at<W>(ci, i) = cv;
+    vec_at<W>(dc, i) = dv;
+  });
+}
+int optim_scaffold_control(float* ci, float* dc, const float* x, const float* y, const float* corr, float inv_mass, size_t n, hipStream_t st) {
+  FEDFR_REQUIRE(ci && dc && x && y && n > 0, "scaffold_control: bad args");
+  FEDFR_REQUIRE(ci != dc, "scaffold_control: c_i and dc must be two buffers");
+  FEDFR_REQUIRE((((uintptr_t)ci | (uintptr_t)dc | (uintptr_t)x | (uintptr_t)y | (uintptr_t)corr) & 15) == 0, "scaffold_control: buffers must be 16-byte aligned");
+  FEDFR_REQUIRE(inv_mass > 0.f && inv_mass - inv_mass == 0.f, "scaffold_control: inv_mass must be a positive finite number (got %g)", (double)inv_mass);
+  if (corr) hipLaunchKernelGGL(scaffold_control_kernel<true>, dim3(multi_state_grid(n)), dim3(MULTI_STATE_BLOCK), 0, st, ci, dc, x, y, corr, inv_mass, n);
+  else hipLaunchKernelGGL(scaffold_control_kernel<false>, dim3(multi_state_grid(n)), dim3(MULTI_STATE_BLOCK), 0, st, ci, dc, x, y, corr, inv_mass, n);
+  FEDFR_LAUNCH_CHECK("scaffold_control");
   return FEDFR_OK;
 }
 

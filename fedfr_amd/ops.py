@@ -6,7 +6,10 @@ hand-written backward passes to ``loss.backward()`` for callers that use the ref
 """
 from __future__ import annotations
 
+import math
 from typing import Optional, Tuple
+
+import numpy as np
 
 import torch
 
@@ -226,19 +229,44 @@ def colsum(x: torch.Tensor) -> torch.Tensor:
 
 
 def sgd_step(param: torch.Tensor, grad: torch.Tensor, mom: torch.Tensor, shadow: Optional[torch.Tensor], n: int, lr: float, mu: float,
-             wd: float, first: bool, gscale: float = 1.0, overflow: Optional[torch.Tensor] = None) -> None:
+             wd: float, first: bool, gscale: float = 1.0, overflow: Optional[torch.Tensor] = None, anchor: Optional[torch.Tensor] = None,
+             prox: float = 0.0, corr: Optional[torch.Tensor] = None) -> None:
     """torch.optim.SGD step (coupled weight decay, momentum buffer set on ``first``) of elements [0, n) in place; ``shadow``: the 16-bit
     mirror the kernel rewrites alongside.  With the fp16-storage library's device word ``overflow`` it is the guarded kernel
     (``fedfr_sgd_step_scaled``: gradient times ``gscale`` stored back, non-finite elements skipped and flagged in the word); without one
-    the plain kernel, which has no scale to undo."""
+    the plain kernel, which has no scale to undo.  ``anchor`` with ``prox`` (FedProx) and / or ``corr`` (SCAFFOLD): fp32 device tensors of at
+    least n elements, the drift terms of ``fedfr_sgd_step_drift`` (d += prox (p - anchor); d += corr, before the momentum); without them the
+    calls above, argument for argument."""
     if overflow is None and gscale != 1.0:
         raise ValueError("sgd_step: a gradient scale needs the guarded kernel (pass the overflow word)")
     sh = shadow.data_ptr() if shadow is not None else None
-    if overflow is not None:
+    if anchor is not None or corr is not None or prox != 0.0:
+        for t, what in ((anchor, "anchor"), (corr, "corr")):
+            if t is not None and (_C.require_gpu_tensor(t, f32, what).numel() < n or not t.is_contiguous()):
+                raise ValueError("sgd_step: %s must be a contiguous fp32 tensor of at least %d elements" % (what, n))
+        _C.call("fedfr_sgd_step_drift", param.data_ptr(), grad.data_ptr(), mom.data_ptr(), sh, n, lr, mu, wd, 1 if first else 0, gscale,
+                overflow.data_ptr() if overflow is not None else None, _C.ptr(anchor) if anchor is not None else None, prox,
+                _C.ptr(corr) if corr is not None else None, _C.stream())
+    elif overflow is not None:
         _C.call("fedfr_sgd_step_scaled", param.data_ptr(), grad.data_ptr(), mom.data_ptr(), sh, n, lr, mu, wd, 1 if first else 0, gscale,
                 overflow.data_ptr(), _C.stream())
     else:
         _C.call("fedfr_sgd_step", param.data_ptr(), grad.data_ptr(), mom.data_ptr(), sh, n, lr, mu, wd, 1 if first else 0, _C.stream())
+
+
+def scaffold_control(c_i: torch.Tensor, x: torch.Tensor, y: torch.Tensor, corr: Optional[torch.Tensor], step_mass: float) -> torch.Tensor:
+    """SCAFFOLD's end-of-round pass (``fedfr_scaffold_control``): c_i <- (x - y) / step_mass - corr in place, returns dc = the new c_i
+    minus the old one.  All fp32 device vectors of one length; ``corr`` None reads as zero; ``step_mass`` the trainer's fp64 sum."""
+    if not (step_mass > 0.0 and math.isfinite(step_mass)):
+        raise ValueError("scaffold_control: step_mass must be a positive finite number (got %r)" % (step_mass,))
+    n = c_i.numel()
+    for t, what in ((c_i, "c_i"), (x, "x"), (y, "y"), (corr, "corr")):
+        if t is not None and (_C.require_gpu_tensor(t, f32, what).numel() != n or not t.is_contiguous()):
+            raise ValueError("scaffold_control: %s must be a contiguous fp32 tensor of %d elements" % (what, n))
+    dc = torch.empty_like(c_i)
+    _C.call("fedfr_scaffold_control", c_i.data_ptr(), dc.data_ptr(), x.data_ptr(), y.data_ptr(), _C.ptr(corr) if corr is not None else None,
+            float(np.float32(1.0 / step_mass)), n, _C.stream())
+    return dc
 
 
 def _need(t: torch.Tensor, name: str, fn: str, dtype=f32) -> torch.Tensor:

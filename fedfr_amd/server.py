@@ -907,6 +907,7 @@ class Server(object):
         self.upload_clip = None                      # the UploadClip of clip_uploads (built in train()) and what the last round read of it
         self.upload_sqnorms = self.upload_coefs = self.upload_violations = None
         self.dp_last_sqnorms = None                  # distributed_dp: the survivors' sums of squared codes of the last round (each <= delta_int^2)
+        self.scaffold_c = None                       # aggr_alg SCAFFOLD: the server's control variate c, fp32 [n_train] on the device (None = still zero)
         self.secagg_rng = None                       # n -> n random bytes for the secure-aggregation secrets (None: os.urandom)
 
     def enable_local_verification(self, callback, candidates=None):
@@ -990,9 +991,30 @@ class Server(object):
                 raise ValueError("Server.train: secagg_bits=%d cannot be combined with distributed_dp: discrete Gaussian noise in a ring of %d "
                                  "bits needs its own sensitivity and wrap-around analysis, which is not provided" % (secagg_bits, secagg_bits))
         secagg_drop = []
-        if aggr_alg not in ("FedAvg", "FedProx") and aggr_alg not in AGGR_ALG_KINDS and aggr_alg not in ROBUST_ALG_KINDS:      # before a round of client training is spent on it
-            raise ValueError("Server.train: unknown aggr_alg %r (FedAvg, FedProx, %s, %s)"
+        if aggr_alg not in ("FedAvg", "FedProx", "SCAFFOLD") and aggr_alg not in AGGR_ALG_KINDS and aggr_alg not in ROBUST_ALG_KINDS:      # before a round of client training is spent on it
+            raise ValueError("Server.train: unknown aggr_alg %r (FedAvg, FedProx, SCAFFOLD, %s, %s)"
                              % (aggr_alg, ", ".join(AGGR_ALG_KINDS), ", ".join(sorted(ROBUST_ALG_KINDS))))
+        from .client import check_prox_mu
+        prox_mu = check_prox_mu(getattr(a, "prox_mu", 0), "Server.train")   # FedProx's proximal coefficient (client-side): absent or 0 = off, whatever aggr_alg is
+        scaffold = aggr_alg == "SCAFFOLD"
+        if scaffold:                                                         # the control updates travel in the clear and unclipped, beside whole states
+            why = "the clients' control updates travel in the clear and unclipped"
+            if secagg_on:
+                raise ValueError("Server.train: aggr_alg='SCAFFOLD' cannot be combined with secure_aggregation: %s" % why)
+            if compress_bits:
+                raise ValueError("Server.train: aggr_alg='SCAFFOLD' cannot be combined with compress_bits=%r: %s" % (compress_bits, why))
+            if topk_ratio:
+                raise ValueError("Server.train: aggr_alg='SCAFFOLD' cannot be combined with topk_ratio=%r: %s" % (topk_ratio, why))
+            if dp_sigma:
+                raise ValueError("Server.train: aggr_alg='SCAFFOLD' cannot be combined with dp_noise_multiplier=%r: %s" % (dp_sigma, why))
+            if clip_norm > 0:
+                raise ValueError("Server.train: aggr_alg='SCAFFOLD' cannot be combined with clip_norm=%r: %s" % (clip_norm, why))
+            if return_all:
+                raise ValueError("Server.train: aggr_alg='SCAFFOLD' cannot be combined with return_all: %s, and the public class centres "
+                                 "have no control variate" % why)
+            if float(getattr(a, "server_lr", 1.0)) != 1.0:
+                raise ValueError("Server.train: aggr_alg='SCAFFOLD' runs with the global step size 1 (got server_lr=%r): another one is not "
+                                 "provided" % (a.server_lr,))
         if clip_uploads:                                                     # what the setting itself cannot serve; the pairings follow below
             if secagg_on:
                 raise ValueError("Server.train: clip_uploads cannot be combined with secure_aggregation: the clip needs per-client norms of the "
@@ -1115,7 +1137,7 @@ class Server(object):
                                secagg_on=secagg_on, secagg_frac_bits=secagg_frac_bits, secagg_threshold=secagg_threshold, secagg_drop=secagg_drop,
                                secagg_bits=secagg_bits or 32, secagg_rotation_seed=secagg_rotation_seed,
                                public=bool(getattr(a, "add_pretrained_data", False)), return_all=return_all,
-                               clip_uploads=clip_uploads and clip_norm > 0)
+                               clip_uploads=clip_uploads and clip_norm > 0, prox_mu=prox_mu, scaffold=scaffold)
 
     def _train_clients(self, s) -> List[int]:
         """Stage 2: every client of ``current_client_list`` receives the global model and trains, one after another or
@@ -1134,6 +1156,8 @@ class Server(object):
             c.slot = slot
             c.backbone_state_dict = flat_state_dict(self.federated_model)       # "server sends backbone"
             c.local_epoch = self.local_epoch
+            if s.scaffold or getattr(c, "scaffold_on", False):                  # "server sends c" (None while it is still zero)
+                c.scaffold_on, c.scaffold_c = s.scaffold, self.scaffold_c if s.scaffold else None
             veri = {}                                                           # server.py:291-298: candidates train with the local test
             if self.callback_local_veri is not None and c.cid in self.local_candidates:
                 veri = {"callback_verification": self.callback_local_veri}
@@ -1300,6 +1324,9 @@ class Server(object):
             aggr_state_dict = self._aggregate_dp(models, data_sizes, aggr_alg, s.dp_sigma, s.clip_norm, s.dp_delta)
         elif aggr_alg in ("FedAvg", "FedProx"):
             aggr_state_dict = FedPavg(models, data_sizes)
+        elif s.scaffold:
+            aggr_state_dict = FedPavg(models, data_sizes)                      # global step size 1: the new model is today's FedAvg
+            self._scaffold_update_c([self.clients[i].get_control_update() for i in order])
         elif aggr_alg in AGGR_ALG_KINDS:
             aggr_state_dict = FedOpt(flat_state_dict(self.federated_model), models, data_sizes, opt)
         else:
@@ -1312,6 +1339,20 @@ class Server(object):
                 self.logger.info('%s kept clients %s, rejected clients %s' % (aggr_alg, [cid[j] for j in sorted(kept)],
                                                                                [cid[j] for j in range(len(order)) if j not in kept]))
         return aggr_state_dict
+
+    def _scaffold_update_c(self, dcs):
+        """SCAFFOLD: c += (1 / N) sum_{i in S} dc_i over this round's clients S, N = all clients of the server: ``fedfr_fedavg_multi`` in
+        accumulate mode, up to 8 control updates per pass.  Logs what the round's uploads cost."""
+        if any(dc is None for dc in dcs):
+            raise RuntimeError("Server.train: aggr_alg='SCAFFOLD' needs every client's control update (Client.get_control_update)")
+        if self.scaffold_c is None:
+            self.scaffold_c = torch.zeros_like(dcs[0])
+        w = 1.0 / len(self.clients)
+        for c0 in range(0, len(dcs), 8):
+            _multi(self.scaffold_c, dcs[c0:c0 + 8], [w] * len(dcs[c0:c0 + 8]), True)
+        n = self.scaffold_c.numel()
+        self.logger.info('SCAFFOLD uploads: %d bytes from %d clients, 2 x %d bytes each (the parameters and the control update of %d '
+                         'elements, both fp32, in the clear)' % (2 * 4 * n * len(dcs), len(dcs), 4 * n, n))
 
     def _account_distributed_dp(self, mech, survivors, exhausted, uploads, delta):
         """what ``distributed_dp`` checks and accounts after the round's aggregation (the counters have been read): a sampler that ran out

@@ -184,6 +184,13 @@ int fedfr_net_backward2_sgd(const fedfr_net_t* net, const float* x, const float*
 int fedfr_net_backward2_sgd_scaled(const fedfr_net_t* net, const float* x, const float* dfeats, float* params, uint16_t* shadow, void* act,
                                    void* ws, float* grads, float* momentum, float lr, float mu, float wd, int first, float grad_scale,
                                    unsigned* overflow, long long* done_from, void* stream, void* aux_stream);
+/* the same with fedfr_sgd_step_drift as the update (DRIFT TERMS below): anchor / corr are indexed like params, so the ranges the pass updates
+ * itself read their own slices.  overflow == NULL with grad_scale == 1 is the unguarded update, anything else the guarded one.  The caller
+ * finishes with fedfr_sgd_step_drift on [0, *done_from); bit-identical to fedfr_net_backward2 + one flat fedfr_sgd_step_drift. */
+int fedfr_net_backward2_sgd_drift(const fedfr_net_t* net, const float* x, const float* dfeats, float* params, uint16_t* shadow, void* act,
+                                  void* ws, float* grads, float* momentum, float lr, float mu, float wd, int first, float grad_scale,
+                                  unsigned* overflow, const float* anchor, float prox, const float* corr, long long* done_from, void* stream,
+                                  void* aux_stream);
 
 /* fp32 VALIDATION path of the same plan (csrc/net_f32.hip): IResNet.forward / autograd backward (iresnet.py:46-57,158-172) with fp32
  * activations and exact-fp32 arithmetic (im2col + the fp32-MFMA GEMM, two-pass BatchNorm in fp64) — what the "1e-3 fp32" tolerance is
@@ -608,6 +615,31 @@ int fedfr_sgd_step(float* params, const float* grads, float* momentum_buf, uint1
  * momentum and mirror value, and the device word *overflow (optional) is set to 1; the caller reads and clears it when it next synchronises. */
 int fedfr_sgd_step_scaled(float* params, float* grads, float* momentum_buf, uint16_t* h16_shadow, size_t n, float lr, float momentum,
                           float weight_decay, int first_step, float grad_scale, unsigned* overflow, void* stream);
+/* ------------------------------------------------------------------------------------------------
+ * DRIFT TERMS — what a client optimises under FedProx (Li et al., MLSys 2020) and SCAFFOLD (Karimireddy et al., ICML 2020), inside the
+ * same SGD kernel: one or two more read-only streams, no extra pass.  anchor = the round's global parameters x [n], a = prox = the proximal
+ * coefficient, corr = the client's correction vector c - c_i [n].  Per element, every operation ONE fp32 rounding:
+ *     d0 = fma(wd, p, g)                                   (as fedfr_sgd_step)
+ *     d1 = anchor ? fma(a, fsub(p, anchor), d0) : d0
+ *     d  = corr   ? fadd(d1, corr)              : d1
+ *     buf = first ? d : fadd(fmul(buf, mu), d);   p = fma(-lr, buf, p)      (as fedfr_sgd_step)
+ * g is the unscaled gradient: grad_scale and the overflow guard are fedfr_sgd_step_scaled's (an element whose gradient is not finite keeps p,
+ * buf and its mirror value and sets *overflow, whatever anchor and corr hold there); overflow == NULL with grad_scale == 1 selects the
+ * unguarded kernel, anything else the guarded one.  The 16-bit mirror is written as by fedfr_sgd_step.  The proximal term is part of the
+ * update only: no loss value contains it.
+ * FEDFR_ERR_ARG before any launch: anchor == NULL with prox != 0; anchor != NULL with prox == 0 or a prox that is not finite; anchor and
+ * corr both NULL (fedfr_sgd_step / fedfr_sgd_step_scaled is the call to make); a buffer that is not 16-byte aligned; n == 0.
+ * ------------------------------------------------------------------------------------------------ */
+int fedfr_sgd_step_drift(float* params, float* grads, float* momentum_buf, uint16_t* h16_shadow, size_t n, float lr, float momentum,
+                         float weight_decay, int first_step, float grad_scale, unsigned* overflow, const float* anchor, float prox,
+                         const float* corr, void* stream);
+/* SCAFFOLD's end-of-round pass of a client (option II of the paper, c_i+ = c_i - c + (x - y_i) / mass), one pass over six streams:
+ *     t = fsub(x, y);  cn = fma(inv_mass, t, -corr);  dc = fsub(cn, c_i);  c_i = cn
+ * x = the parameters the round started from, y = the trained ones, corr = the c - c_i the client trained with (NULL reads as +0.0),
+ * inv_mass = fl32(1 / step_mass) with step_mass = sum_k lr_k (1 - mu^k) / (1 - mu) over the client's steps k = 1, 2, ... (the total weight
+ * heavy-ball momentum gives the gradients of the run; mu = 0: sum_k lr_k).  c_i [n] is updated in place, dc [n] (another buffer) receives
+ * the control update the client uploads.  FEDFR_ERR_ARG: a NULL or misaligned buffer, c_i == dc, n == 0, inv_mass not positive and finite. */
+int fedfr_scaffold_control(float* c_i, float* dc, const float* x, const float* y, const float* corr, float inv_mass, size_t n, void* stream);
 int fedfr_fedavg_axpy(float* dst, const float* src, float w, size_t n, int accumulate, void* stream);
 /* dst = (accumulate ? dst : 0) + sum_i ws[i] * srcs[i] over k <= 8 client states (HOST arrays of k device pointers / k weights) in one pass,
  * ascending i, one fp32 multiply and one fp32 add per term: bit-identical to k fedfr_fedavg_axpy calls = the loop of server.py:27-33 */
