@@ -172,6 +172,7 @@ SIGNATURES = {
     "fedfr_secagg_aggregate_narrow": (i32, [vp, vp, vp, vp, i32, i32, u64, u64, vp, vp, vp, i32, u32, i32, f32, sz, i32, i32, vp]),
     "fedfr_dgauss_fill": (i32, [vp, sz, u64, u64, u32, u64, f64, vp, vp]),
     "fedfr_secagg_mask_dp": (i32, [vp, vp, vp, vp, i32, i32, u64, u64, u64, f64, vp, vp, vp, i32, sz, vp, vp, vp]),
+    "fedfr_secagg_mask_narrow_dp": (i32, [vp, vp, vp, vp, i32, i32, i32, u64, u64, u64, u64, u64, u64, f64, vp, vp, vp, i32, u32, sz, vp, vp, vp]),
     "fedfr_robust_trimmed_mean": (i32, [vp, vp, i32, i32, sz, vp]),
     "fedfr_robust_pairdist_workspace_bytes": (sz, [i32, sz]),
     "fedfr_robust_pairdist": (i32, [vp, i32, sz, vp, vp, sz, vp]),

@@ -1242,7 +1242,7 @@ class Client(object):
         client's self mask, from the secrets of ``secagg_client(...).begin_round(round)``.  One kernel pass.  With ``dp`` (a
         ``privacy.DistributedDiscreteGaussian``) the client first clips its own update and adds its own share of discrete Gaussian noise
         (``SecAggClient.mask_dp``: the norm pass and one kernel pass); the mechanism's sensitivity is stated for ``weight`` = 1, and
-        anything else is refused."""
+        anything else is refused.  The width of the words is the ``SecAggClient``'s: at 16 bits ``dp`` must be a mechanism of 16-bit words."""
         sa = getattr(self, "secagg", None)
         if sa is None:
             raise RuntimeError("Client.get_masked_update: secagg_client(...).begin_round(round) first")

@@ -994,6 +994,14 @@ int fedfr_secagg_mask_dp(unsigned* y, const float* x, const float* xi, const flo
   return ddp_secagg_mask_dp(y, x, xi, clip_coef, frac_bits, code_limit, noise_seed, noise_round, noise_offset, sigma, keys, nonces, signs, k, n,
                             counters, sqnorm, ST(stream));
 }
+int fedfr_secagg_mask_narrow_dp(unsigned* y, const float* x, const float* xi, const float* clip_coef, int frac_bits, int code_limit, int bits,
+                                unsigned long long rotation_seed, unsigned long long private_seed, unsigned long long round,
+                                unsigned long long noise_seed, unsigned long long noise_round, unsigned long long noise_offset, double sigma,
+                                const unsigned* keys, const unsigned* nonces, const int* signs, int k, unsigned counter0, size_t n,
+                                int* counters, unsigned long long* sqnorm, void* stream) {
+  return ddp_secagg_mask_narrow_dp(y, x, xi, clip_coef, frac_bits, code_limit, bits, rotation_seed, private_seed, round, noise_seed, noise_round,
+                                   noise_offset, sigma, keys, nonces, signs, k, counter0, n, counters, sqnorm, ST(stream));
+}
 int fedfr_robust_trimmed_mean(float* dst, const float* const* srcs, int k, int trim, size_t n, void* stream) {
   return robust_trimmed_mean(dst, srcs, k, trim, n, ST(stream));
 }

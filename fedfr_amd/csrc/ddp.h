@@ -86,9 +86,23 @@ __device__ __forceinline__ int dgauss_queue(unsigned* __restrict__ out, int lane
   return exhausted;
 }
 
+// what every entry point that draws n elements behind `offset` checks first
+static inline int dgauss_args(const char* who, double sigma, size_t n, unsigned long long offset) {
+  FEDFR_REQUIRE(sigma >= 16.0 && sigma <= 0x1p26, "%s: sigma must be in [16, 2^26] (sigma=%g)", who, sigma);      // (NaN fails both)
+  FEDFR_REQUIRE(offset <= (1ull << 58) && n <= (1ull << 58) - offset,
+                "%s: offset + n must not pass 2^58: 64 blocks per element in a 64-bit block index (offset=%llu, n=%zu)", who, offset, n);
+  return FEDFR_OK;
+}
+
 int ddp_dgauss_fill(int* dst, size_t n, unsigned long long seed, unsigned long long round, unsigned stream_id, unsigned long long offset,
                     double sigma, int* exhausted, hipStream_t st);
 int ddp_secagg_mask_dp(unsigned* y, const float* x, const float* xi, const float* clip_coef, int frac_bits, int limit,
                        unsigned long long noise_seed, unsigned long long noise_round, unsigned long long noise_offset, double sigma,
                        const unsigned* keys, const unsigned* nonces, const int* signs, int k, size_t n, int* counters,
                        unsigned long long* sqnorm, hipStream_t st);
+// ddp_narrow.hip: the same mechanism on the 16-bit NARROW WORDS of secagg_narrow.h
+int ddp_secagg_mask_narrow_dp(unsigned* y, const float* x, const float* xi, const float* clip_coef, int frac_bits, int limit, int bits,
+                              unsigned long long rotation_seed, unsigned long long private_seed, unsigned long long round,
+                              unsigned long long noise_seed, unsigned long long noise_round, unsigned long long noise_offset, double sigma,
+                              const unsigned* keys, const unsigned* nonces, const int* signs, int k, unsigned counter0, size_t n, int* counters,
+                              unsigned long long* sqnorm, hipStream_t st);

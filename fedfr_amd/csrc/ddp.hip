@@ -115,13 +115,6 @@ __global__ __launch_bounds__(MULTI_STATE_BLOCK) void ddp_mask_kernel(unsigned* _
   }
 }
 
-static int dgauss_args(const char* who, double sigma, size_t n, unsigned long long offset) {
-  FEDFR_REQUIRE(sigma >= 16.0 && sigma <= 0x1p26, "%s: sigma must be in [16, 2^26] (sigma=%g)", who, sigma);      // (NaN fails both)
-  FEDFR_REQUIRE(offset <= (1ull << 58) && n <= (1ull << 58) - offset,
-                "%s: offset + n must not pass 2^58: 64 blocks per element in a 64-bit block index (offset=%llu, n=%zu)", who, offset, n);
-  return FEDFR_OK;
-}
-
 int ddp_dgauss_fill(int* dst, size_t n, unsigned long long seed, unsigned long long round, unsigned stream_id, unsigned long long offset,
                     double sigma, int* exhausted, hipStream_t st) {
   FEDFR_REQUIRE(dst && exhausted, "dgauss_fill: null pointer (dst=%p exhausted=%p)", (void*)dst, (void*)exhausted);

@@ -80,15 +80,58 @@ class DistributedDiscreteGaussian:
     when tau n >= 1e-12 (at sigma_int >= 16 tau underflows to 0 in fp64); the message names the ``secagg_frac_bits`` that would work.  One
     round is then (delta_int / (sqrt(T) sigma_int))^2 / 2-zCDP, which is RDP(alpha) = alpha / (2 z_eff^2): ``accountant()`` returns
     ``RDPAccountant(1.0, z_eff)``.  Rounds are accounted at q = 1 whatever the sampling rate: valid and conservative (the amplification
-    bound of ``RDPAccountant`` is proven for the continuous Gaussian only)."""
+    bound of ``RDPAccountant`` is proven for the continuous Gaussian only).
+
+    ``bits=16, wrap_sigmas=kappa`` is the same mechanism on the NARROW WORDS of secure aggregation (``SecAggClient(bits=16).mask_dp``:
+    fedfr_secagg_mask_narrow_dp): the clipped update is rotated block by block, rounded STOCHASTICALLY with the client's private draws,
+    noised and summed field-wise in Z / 2^16.  With n_pad = padded_count(n), the coordinates of the rotated vector (after the rotation
+    every coordinate of the padded last block carries the update: every one gets noise and counts toward the sensitivity):
+        sigma_int  = z C 2^f / sqrt(T)                                unchanged
+        delta_int  = C 2^f (1 + EPS_FP) (1 + EPS_ROT) + sqrt(n_pad)   the rotation is orthogonal; EPS_ROT bounds what its twelve fp32 butterfly
+                                                                      levels and the product with the coefficient add to the L2 NORM (DESIGN.md
+                                                                      section 3.31); stochastic rounding moves each of the n_pad coordinates by
+                                                                      less than 1.  The paper's worst-case bound (c + gamma sqrt(d))^2: no
+                                                                      conditional re-rounding.  The clamp only shrinks a code
+        code_limit = (32767 - ceil(kappa sigma_int sqrt(K))) // K     |sum of K codes| <= K code_limit, and the sum of K noises passes
+                                                                      kappa sigma_int sqrt(K) with probability <= 2 exp(-kappa^2 / 2) per
+                                                                      coordinate (a discrete Gaussian is sigma-sub-Gaussian: Canonne, Kamath,
+                                                                      Steinke 2020), so a field of the unmasked sum wraps at most that often
+        wrap_bound = n_pad 2 exp(-kappa^2 / 2)                        the expected number of wrapped coordinates per round (an attribute)
+        coordinate_sigmas = 64 code_limit / (C 2^f)                   code_limit does NOT bound a rotated coordinate: this is how many of its
+                                                                      sub-Gaussian standard deviations (scale C 2^f / 64) fit inside the clamp;
+                                                                      saturated codes are counted and logged
+        tau, z_eff                                                    the formulas above, tau held against n_pad
+    A wrapped field is POST-PROCESSING of the noised integer sum (reduction mod 2^16 is a ring homomorphism: the sum of the reduced uploads
+    is the reduction of the integer sum): it costs accuracy, never privacy.  ``ValueError`` for sigma_int outside the sampler's range,
+    code_limit < 1 or tau n_pad >= 1e-12 (with the ``secagg_frac_bits`` that would work), for ``bits=16`` without ``wrap_sigmas`` (finite,
+    >= 1), for ``wrap_sigmas`` at 32 bits (nothing wraps there), and for ``bits=8``.  Each step of ``secagg_frac_bits`` doubles C 2^f and
+    sigma_int, so only a few values fit between the sampler's smallest sigma and the wrap headroom."""
 
     EPS_FP = 2.0 ** -22
+    EPS_ROT = 13 * 2.0 ** -24                        # (1 + 2^-24)^13 - 1 to first order: 12 butterfly levels and one product (DESIGN.md section 3.31)
     SIGMA_MIN, SIGMA_MAX = 16.0, 2.0 ** 26
     TAIL = 37                                        # |noise| <= TAIL (floor(sigma_int) + 1): U1 >= 2^-53 and 53 ln 2 < 37
+    FIELD_MAX = 2 ** 15 - 1                          # the largest value of a 16-bit field
+    WHY_NOT_8 = ("8-bit words cannot carry distributed differential privacy: the sampler's smallest sigma_int, 16, times any wrap_sigmas >= 1 "
+                 "and sqrt(2) for the fewest participants already fills most of the +-127 of a field; use secagg_bits=16")
 
-    def __init__(self, noise_multiplier, clip_norm, frac_bits, participants, threshold, n):
-        from .secagg import MAX_PARTICIPANTS, check_frac_bits
+    def __init__(self, noise_multiplier, clip_norm, frac_bits, participants, threshold, n, bits=32, wrap_sigmas=None):
+        from .secagg import MAX_PARTICIPANTS, check_bits, check_frac_bits, padded_count
         who = "DistributedDiscreteGaussian"
+        self.bits = check_bits(bits, who)
+        if self.bits == 8:
+            raise ValueError("%s: %s" % (who, self.WHY_NOT_8))
+        if self.bits == 32 and wrap_sigmas is not None:
+            raise ValueError("%s: wrap_sigmas=%r belongs to 16-bit words: at 32 bits the clamp keeps every sum inside the word and nothing wraps"
+                             % (who, wrap_sigmas))
+        if self.bits == 16:
+            if wrap_sigmas is None:
+                raise ValueError("%s: 16-bit words need wrap_sigmas (ddp_wrap_sigmas): how many standard deviations of the summed noise the "
+                                 "fields keep free, which sets the code clamp and the expected number of wrapped coordinates" % who)
+            if isinstance(wrap_sigmas, bool) or not isinstance(wrap_sigmas, (int, float, np.integer, np.floating)) \
+                    or not (math.isfinite(wrap_sigmas) and wrap_sigmas >= 1.0):
+                raise ValueError("%s: wrap_sigmas must be a finite number >= 1 (got %r)" % (who, wrap_sigmas))
+        self.wrap_sigmas = None if wrap_sigmas is None else float(wrap_sigmas)
         self.noise_multiplier, self.clip_norm = float(noise_multiplier), float(clip_norm)
         if not (self.noise_multiplier > 0.0 and math.isfinite(self.noise_multiplier)):
             raise ValueError("%s: noise_multiplier must be finite and > 0 (got %r)" % (who, noise_multiplier))
@@ -100,32 +143,45 @@ class DistributedDiscreteGaussian:
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo or (hi is not None and v > hi):
                 raise ValueError("%s: %s must be an integer in %d ... %s (got %r)" % (who, name, lo, "" if hi is None else hi, v))
         self.participants, self.threshold, self.n = int(participants), int(threshold), int(n)
+        self.n_pad = padded_count(self.n) if self.bits == 16 else self.n      # the coordinates that carry noise
         ok = [f for f in range(8, 31) if self._refusal(f) is None]
         why = self._refusal(self.frac_bits)
         if why is not None:
             hint = ("secagg_frac_bits in %d ... %d would work" % (ok[0], ok[-1])) if ok else "no secagg_frac_bits in 8 ... 30 would work"
-            raise ValueError("%s: %s (noise_multiplier=%g, clip_norm=%g, secagg_frac_bits=%d, participants=%d, threshold=%d, n=%d): %s"
-                             % (who, why, self.noise_multiplier, self.clip_norm, self.frac_bits, self.participants, self.threshold, self.n, hint))
+            more = "" if self.bits == 32 else ", bits=%d, wrap_sigmas=%g" % (self.bits, self.wrap_sigmas)
+            raise ValueError("%s: %s (noise_multiplier=%g, clip_norm=%g, secagg_frac_bits=%d, participants=%d, threshold=%d, n=%d%s): %s"
+                             % (who, why, self.noise_multiplier, self.clip_norm, self.frac_bits, self.participants, self.threshold, self.n, more, hint))
         self.sigma_int, self.delta_int, self.code_limit, self.tau = self._numbers(self.frac_bits)
         self.z_eff = math.sqrt(self.threshold) * self.sigma_int / self.delta_int
+        # (32 bits: the clamp keeps code + noise inside the word, nothing wraps, and no coordinate is rotated)
+        self.wrap_bound = 0.0 if self.bits == 32 else self.n_pad * 2.0 * math.exp(-self.wrap_sigmas ** 2 / 2.0)
+        self.coordinate_sigmas = None if self.bits == 32 else 64.0 * self.code_limit / (self.clip_norm * 2.0 ** self.frac_bits)
 
     def _numbers(self, f):
         from .secagg import code_limit
         scale = self.clip_norm * 2.0 ** f
         sigma = self.noise_multiplier * scale / math.sqrt(self.threshold)
+        tau = 10.0 * sum(math.exp(-2.0 * math.pi ** 2 * sigma * sigma * k / (k + 1.0)) for k in range(1, self.threshold))
+        if self.bits == 16:
+            delta = scale * (1.0 + self.EPS_FP) * (1.0 + self.EPS_ROT) + math.sqrt(self.n_pad)
+            headroom = int(math.ceil(self.wrap_sigmas * min(sigma, 2.0 ** 40) * math.sqrt(self.participants)))
+            return sigma, delta, (self.FIELD_MAX - headroom) // self.participants, tau
         delta = scale * (1.0 + self.EPS_FP) + math.sqrt(self.n) / 2.0
         limit = code_limit(self.participants) - self.TAIL * (int(math.floor(min(sigma, 2.0 ** 40))) + 1)
-        tau = 10.0 * sum(math.exp(-2.0 * math.pi ** 2 * sigma * sigma * k / (k + 1.0)) for k in range(1, self.threshold))
         return sigma, delta, limit, tau
 
     def _refusal(self, f):
         sigma, delta, limit, tau = self._numbers(f)
         if not self.SIGMA_MIN <= sigma <= self.SIGMA_MAX:
             return "sigma_int = %.6g is outside the sampler's range [16, 2^26]" % sigma
-        if limit < delta:
+        if self.bits == 16:
+            if limit < 1:
+                return ("the code clamp (32767 - ceil(%g x %.6g x sqrt(%d))) // %d = %d is below 1: the noise headroom leaves no room for codes "
+                        "in a 16-bit field" % (self.wrap_sigmas, sigma, self.participants, self.participants, limit))
+        elif limit < delta:
             return "the code clamp L' = %d is below the sensitivity delta_int = %.6g: clipped updates would be clamped" % (limit, delta)
-        if tau * self.n >= 1e-12:
-            return "the sum of %d discrete Gaussians of sigma_int = %.6g is not close to one (tau n = %.3g >= 1e-12)" % (self.threshold, sigma, tau * self.n)
+        if tau * self.n_pad >= 1e-12:
+            return "the sum of %d discrete Gaussians of sigma_int = %.6g is not close to one (tau n = %.3g >= 1e-12)" % (self.threshold, sigma, tau * self.n_pad)
         return None
 
     def realised_multiplier(self, survivors: int) -> float:
@@ -137,7 +193,7 @@ class DistributedDiscreteGaussian:
         return RDPAccountant(1.0, self.z_eff)
 
     def same_as(self, other) -> bool:
-        keys = ("noise_multiplier", "clip_norm", "frac_bits", "participants", "threshold", "n")
+        keys = ("noise_multiplier", "clip_norm", "frac_bits", "participants", "threshold", "n", "bits", "wrap_sigmas")
         return isinstance(other, DistributedDiscreteGaussian) and all(getattr(self, k) == getattr(other, k) for k in keys)
 
 

@@ -26,7 +26,8 @@ NARROW WORDS.  ``SecAggClient(..., bits=8 or 16)`` uploads n_pad b / 8 bytes ins
 PUBLIC random sign flip and a Walsh-Hadamard transform (so that no coordinate is large), rounded STOCHASTICALLY to b-bit codes with the
 client's private draws (so that the codes are unbiased), packed 32 / b to a word and masked and summed FIELD-WISE mod 2^b
 (``fedfr_secagg_mask_narrow`` / ``fedfr_secagg_aggregate_narrow``; the format: include/fedfr_hip.h, "NARROW WORDS"; how to choose
-``frac_bits``: INTEGRATION.md section 19).  ``bits=32`` is the path above, unchanged.  Distributed DP at narrow widths is not provided.
+``frac_bits``: INTEGRATION.md section 19).  ``bits=32`` is the path above, unchanged.  Distributed DP is provided at 16-bit words
+(``mask_dp`` with a mechanism of ``bits=16``: fedfr_secagg_mask_narrow_dp; the analysis: INTEGRATION.md section 21), not at 8.
 """
 from __future__ import annotations
 
@@ -373,7 +374,11 @@ class SecAggClient:
         this client's ``frac_bits``), at weight 1: the norm pass (fedfr_fedopt_sqnorm, which leaves min(1, C / ||x_i - x||) ON THE DEVICE),
         then ONE call of fedfr_secagg_mask_dp, which clips, encodes at the clamp ``mech.code_limit``, sums the squared codes, adds the
         client's noise share of sigma_int and the masks.  No host synchronisation in between.  The 64-bit noise seed is drawn from
-        ``rng`` per call and stays here (``noise_seed``: the client knows its own share, nobody else does)."""
+        ``rng`` per call and stays here (``noise_seed``: the client knows its own share, nobody else does).
+        A client of 16-bit words takes a mechanism of 16-bit words (``DistributedDiscreteGaussian(..., bits=16, wrap_sigmas=kappa)``): the
+        norm pass, then ONE call of fedfr_secagg_mask_narrow_dp, and the upload is padded_count(n) / 2 packed words with the rotation
+        seed and the round the server turns the sum back with; its counters and ``sqnorm`` cover all padded_count(n) rotated coordinates,
+        every one of which carries noise.  A mechanism and a client of different widths raise ``ValueError``, and so do 8-bit words."""
         import torch
         from . import _C
         from .client import FlatStateDict
@@ -383,8 +388,12 @@ class SecAggClient:
             raise RuntimeError("fedfr_amd.SecAggClient: the global and the client state must be FlatStateDicts (client.flat_state_dict)")
         if not isinstance(mech, DistributedDiscreteGaussian):
             raise RuntimeError("fedfr_amd.SecAggClient.mask_dp: mech must be a privacy.DistributedDiscreteGaussian (got %r)" % (type(mech).__name__,))
-        if self.bits != 32:
-            raise ValueError("SecAggClient.mask_dp: distributed differential privacy at %d-bit words is not provided" % self.bits)
+        if self.bits == 8:
+            raise ValueError("SecAggClient.mask_dp: distributed differential privacy at %d-bit words is not provided: %s"
+                             % (self.bits, DistributedDiscreteGaussian.WHY_NOT_8))
+        if mech.bits != self.bits:
+            raise ValueError("SecAggClient.mask_dp: a mechanism of %d-bit words meets a client of %d-bit words (set_width, or "
+                             "DistributedDiscreteGaussian(bits=..., wrap_sigmas=...))" % (mech.bits, self.bits))
         K = len(participants)
         if not 2 <= K <= MAX_PARTICIPANTS or len(set(participants)) != K:
             raise ValueError("SecAggClient.mask_dp: 2 to %d distinct participants (got %d: %s)" % (MAX_PARTICIPANTS, K, list(participants)))
@@ -398,9 +407,22 @@ class SecAggClient:
         if self._clipper is None or self._clipper.clip_norm != mech.clip_norm:
             self._clipper = ServerOptimizer("AVGM", clip_norm=mech.clip_norm)
         self.noise_seed = int.from_bytes((self.rng or os.urandom)(8), "little")
-        y = torch.empty(n, dtype=torch.int32, device=dev)
         cc = torch.zeros(3, dtype=torch.int32, device=dev)
         sq = torch.zeros(1, dtype=torch.int64, device=dev)
+        if self.bits == 16:
+            # NARROW WORDS UNDER DISTRIBUTED DP: the norm pass, then ONE call of fedfr_secagg_mask_narrow_dp (clip, rotation, stochastic
+            # rounding, the sum of the squared codes, the noise of all n_pad rotated coordinates mod 2^16, packing and masks)
+            if self.rounding_seed is None:
+                raise RuntimeError("SecAggClient.mask_dp: the secrets at hand were drawn for 32-bit words; set_width(...) and begin_round again")
+            y = torch.empty(padded_count(n) // 2, dtype=torch.int32, device=dev)
+            if n:
+                coef = self._clipper.coefficients(x, [xi], [1.0])
+                _C.call("fedfr_secagg_mask_narrow_dp", y.data_ptr(), x.data_ptr(), xi.data_ptr(), coef.data_ptr(), self.frac_bits, mech.code_limit, 16,
+                        self.rotation_seed, self.rounding_seed, int(round) & 0xFFFFFFFF, self.noise_seed, int(round) & 0xFFFFFFFF, 0, mech.sigma_int,
+                        keys, nonces, signs, K, 0, n, cc.data_ptr(), sq.data_ptr(), _C.stream())
+            return MaskedUpdate(y, n, self.frac_bits, stats, counters, cc, client_state.table, client_state.layers, sqnorm=sq, bits=16,
+                                rotation_seed=self.rotation_seed, round=int(round) & 0xFFFFFFFF)
+        y = torch.empty(n, dtype=torch.int32, device=dev)
         if n:
             coef = self._clipper.coefficients(x, [xi], [1.0])
             _C.call("fedfr_secagg_mask_dp", y.data_ptr(), x.data_ptr(), xi.data_ptr(), coef.data_ptr(), self.frac_bits, mech.code_limit, self.noise_seed,

@@ -677,7 +677,11 @@ def FedSecAggDP(global_state, uploads, recovery_streams, mech, server_opt=None):
     MEAN of the clipped updates plus the noise of all uploads, or that mean as the pseudo-gradient of ``server_opt``.  (``FedSecAgg``
     itself takes a rescale >= 1 only, the reciprocal of a sum of public weights.)  BN running statistics and ``num_batches_tracked``
     arrive UNMASKED and are averaged uniformly, outside the mechanism.  At least ``mech.threshold`` uploads are required: with fewer the
-    sum carries less noise than the accountant is told."""
+    sum carries less noise than the accountant is told.
+    A mechanism of 16-bit words (``mech.bits`` = 16) takes the NARROW WORDS of ``mask_dp`` at that width: S is the FIELD-WISE sum mod 2^16
+    of the packed words and the streams, and the parameters are x + rescale D 2^-6 H (S 2^-f), the rotation turned back
+    (fedfr_secagg_aggregate_narrow, unchanged: no new server kernel).  All uploads must be of that width and of one public rotation.  A
+    field whose integer sum leaves +-32767 wraps: post-processing of the noised sum, expected ``mech.wrap_bound`` times per round."""
     from .privacy import DistributedDiscreteGaussian
     from .secagg import MaskedUpdate
     # the mechanism's own checks come first: what follows them reads the mechanism
@@ -694,7 +698,8 @@ def FedSecAggDP(global_state, uploads, recovery_streams, mech, server_opt=None):
         % (mech.frac_bits, mech.n, x.numel())
     if x.numel() != mech.n:
         raise RuntimeError("fedfr_amd.FedSecAggDP: %s" % (mismatch % (uploads[0].frac_bits, uploads[0].n)))
-    P = _masked_sum("FedSecAggDP", x, uploads, recovery_streams, mech.frac_bits, float(np.float32(1.0 / len(uploads))), server_opt is None, mismatch)
+    P = _masked_sum("FedSecAggDP", x, uploads, recovery_streams, mech.frac_bits, float(np.float32(1.0 / len(uploads))), server_opt is None, mismatch,
+                    **({} if mech.bits == 32 else {"bits": mech.bits}))
     return _upload_round_tail(global_state, P, x, uploads, ws, server_opt)
 
 
@@ -982,14 +987,27 @@ class Server(object):
         clip_uploads = bool(getattr(a, "clip_uploads", False))               # the clip (and DP noise) ON compressed / top-k uploads: absent or False = off
         dp_delta = ddp_mech = secagg_frac_bits = secagg_threshold = None     # (resolved below where their feature is on)
         secagg_bits, secagg_rotation_seed = getattr(a, "secagg_bits", None), 0   # narrow masked uploads (a build extension): absent or 32 = one word per parameter
+        ddp_wrap = getattr(a, "ddp_wrap_sigmas", None)                       # distributed DP at 16-bit words (kappa, the wrap headroom): absent or None = off
         if secagg_bits is not None:
             from .secagg import check_bits
             secagg_bits = check_bits(secagg_bits, "Server.train")
             if not secagg_on:
                 raise ValueError("Server.train: secagg_bits=%d needs secure_aggregation: it is the width of a masked upload's codes" % (secagg_bits,))
-            if ddp_on and secagg_bits != 32:
+            if ddp_on and secagg_bits != 32 and ddp_wrap is None:
                 raise ValueError("Server.train: secagg_bits=%d cannot be combined with distributed_dp: discrete Gaussian noise in a ring of %d "
-                                 "bits needs its own sensitivity and wrap-around analysis, which is not provided" % (secagg_bits, secagg_bits))
+                                 "bits needs its own sensitivity and wrap-around analysis, which is not provided%s"
+                                 % (secagg_bits, secagg_bits, " (set ddp_wrap_sigmas to opt into the 16-bit analysis: INTEGRATION.md section 21)"
+                                    if secagg_bits == 16 else ""))
+        if ddp_wrap is not None:                                             # the opt-in to distributed DP at 16-bit words: what it cannot serve
+            from .privacy import DistributedDiscreteGaussian
+            if not ddp_on:
+                raise ValueError("Server.train: ddp_wrap_sigmas=%r needs distributed_dp: it is the wrap headroom of the clients' noise shares"
+                                 % (ddp_wrap,))
+            if secagg_bits == 8:
+                raise ValueError("Server.train: secagg_bits=8 cannot be combined with distributed_dp: %s" % DistributedDiscreteGaussian.WHY_NOT_8)
+            if secagg_bits != 16:
+                raise ValueError("Server.train: ddp_wrap_sigmas=%r needs secagg_bits=16: at 32-bit words the clamp keeps every sum inside the "
+                                 "word and nothing wraps" % (ddp_wrap,))
         secagg_drop = []
         if aggr_alg not in ("FedAvg", "FedProx", "SCAFFOLD") and aggr_alg not in AGGR_ALG_KINDS and aggr_alg not in ROBUST_ALG_KINDS:      # before a round of client training is spent on it
             raise ValueError("Server.train: unknown aggr_alg %r (FedAvg, FedProx, SCAFFOLD, %s, %s)"
@@ -1127,7 +1145,8 @@ class Server(object):
             if ddp_on:                                                       # the mechanism's arithmetic, and what it refuses: also before anybody trains
                 from .privacy import DistributedDiscreteGaussian
                 ddp_mech = DistributedDiscreteGaussian(dp_sigma, clip_norm, secagg_frac_bits, K, int(secagg_threshold),
-                                                       int(self.federated_model.flat_state()[0].numel()))
+                                                       int(self.federated_model.flat_state()[0].numel()),
+                                                       **({} if ddp_wrap is None else {"bits": 16, "wrap_sigmas": ddp_wrap}))
                 if self.dp_accountant is not None and (self.dp_accountant.q, self.dp_accountant.sigma) != (1.0, ddp_mech.z_eff):
                     raise ValueError("Server.train: distributed_dp at an effective noise multiplier of %r after rounds accounted at %r (q = %g): "
                                      "the accountant composes rounds of one mechanism (set server.dp_accountant yourself to continue)"
@@ -1319,7 +1338,7 @@ class Server(object):
                                        [u.code_counters for u in kept],
                                        'Client %s sent %d saturated and %d non-finite elements (clamped to the code range / sent as 0)')
             if s.ddp_on:
-                self._account_distributed_dp(s.ddp_mech, survivors, [row[2] for row in bad], kept, s.dp_delta)
+                self._account_distributed_dp(s.ddp_mech, survivors, [row[2] for row in bad], kept, s.dp_delta, sum(row[0] for row in bad))
         elif s.dp_sigma:
             aggr_state_dict = self._aggregate_dp(models, data_sizes, aggr_alg, s.dp_sigma, s.clip_norm, s.dp_delta)
         elif aggr_alg in ("FedAvg", "FedProx"):
@@ -1354,10 +1373,12 @@ class Server(object):
         self.logger.info('SCAFFOLD uploads: %d bytes from %d clients, 2 x %d bytes each (the parameters and the control update of %d '
                          'elements, both fp32, in the clear)' % (2 * 4 * n * len(dcs), len(dcs), 4 * n, n))
 
-    def _account_distributed_dp(self, mech, survivors, exhausted, uploads, delta):
+    def _account_distributed_dp(self, mech, survivors, exhausted, uploads, delta, saturated=0):
         """what ``distributed_dp`` checks and accounts after the round's aggregation (the counters have been read): a sampler that ran out
         of attempts and an upload beyond the sensitivity bound are errors (the round's result is not installed); then the accountant's
-        step at q = 1 and the guaranteed noise multiplier, and ``self.dp_epsilon``"""
+        step at q = 1 and the guaranteed noise multiplier, and ``self.dp_epsilon``.  At 16-bit words the sensitivity bound is deterministic
+        (the rotation's norm bound plus sqrt(n_pad) of rounding), so the second check can only fire on a bug: it stays as the guard; the
+        log then also names the width, kappa, the expected wrapped coordinates and the ``saturated`` codes of the round."""
         for cid, nex in zip(survivors, exhausted):
             if nex > 0:
                 raise RuntimeError("Server.train: the noise sampler of client %s ran out of attempts on %d elements (they carry no noise): the "
@@ -1379,6 +1400,13 @@ class Server(object):
                          'whatever the sampling rate (the amplification bound is proven for the continuous Gaussian only)'
                          % (self.dp_epsilon, delta, acc.steps, mech.z_eff, mech.noise_multiplier, mech.sigma_int, mech.delta_int, mech.threshold,
                             mech.realised_multiplier(len(survivors)), len(survivors)))
+        if mech.bits != 32:
+            self.logger.info('Distributed differential privacy at %d-bit words: %d bytes of packed words per upload (2 x n_pad = 2 x %d); code clamp '
+                             '%d = %.3g standard deviations of a rotated coordinate (coordinate_sigmas); wrap headroom kappa = %g: expected wrapped '
+                             'coordinates per round wrap_bound = %.3g (post-processing of the noised sum: accuracy, not privacy); %d saturated '
+                             'codes among the %d uploads'
+                             % (mech.bits, 2 * mech.n_pad, mech.n_pad, mech.code_limit, mech.coordinate_sigmas, mech.wrap_sigmas, mech.wrap_bound,
+                                saturated, len(survivors)))
 
     def _upload_clip(self, s, data_sizes):
         """(clip, mech, weights) of a round from compressed or top-k uploads: (None, None, ``data_sizes``) unless ``clip_uploads`` is on; then

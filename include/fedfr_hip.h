@@ -865,6 +865,35 @@ int fedfr_secagg_aggregate_narrow(float* out, const float* x, unsigned* acc, con
                                   void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * distributed differential privacy on narrow words — no reference counterpart: the two halves of Kairouz, Liu, Steinke (ICML 2021)
+ * together.  A client clips, rotates, rounds stochastically, adds its share of discrete Gaussian noise mod 2^16, packs and masks.
+ * NARROW WORDS UNDER DISTRIBUTED DP.  b = 16 only.  In this order:
+ *   UPDATE, ROTATION.  As NARROW WORDS: v = 2^-6 H_B (D (x_i - x)) over the n_pad padded elements.
+ *   CODE.  coef = fl(clip_coef[0] 2^f) (exact: a power-of-two scaling of the clip factor fedfr_fedopt_sqnorm left on the device);  the CODE
+ *   of NARROW WORDS with this coef, the private draws of (private_seed, round, "SRRD") and the clamp +-code_limit, which the CALLER gives
+ *   (privacy.DistributedDiscreteGaussian: (32767 - ceil(kappa sigma sqrt(K))) / K, the headroom the noise needs), not 32767 / K.
+ *   SQUARED NORM.  sqnorm += sum of q_e^2 over ALL n_pad elements mod 2^64, taken before the noise.
+ *   NOISE.  Element e = 4096 rb + 16 t + j, the POSITION IN THE PADDED ROTATED VECTOR, takes the value of element noise_offset + e of THE
+ *   DISCRETE NOISE STREAM (noise_seed, noise_round, 0x44444750) at sigma: attempt a reads Philox block (noise_offset + e) 64 + a.  The
+ *   n_pad - n PADDING COORDINATES CARRY NOISE like every other: after the rotation each of them holds a part of the update.
+ *   noise_offset + n_pad must not pass 2^58.
+ *   SUM, PACKING, MASKS.  field = q_e + noise_e mod 2^16; PACKING and MASKS of NARROW WORDS (counter0, field-wise streams).
+ * The server's pass is fedfr_secagg_aggregate_narrow at bits = 16, unchanged: reduction mod 2^16 is a ring homomorphism, so a field of the
+ * unmasked sum that wraps is post-processing of the noised integer sum (it costs accuracy, never privacy).  tests/ddp_narrow_cases.py
+ * restates the pass from the restatements of its parts.
+ * ------------------------------------------------------------------------------------------------ */
+/* y[0 .. n_pad / 2) as above, one pass: x and xi read once, y written once.  counters: DEVICE int32[3] {saturated, nonfinite, exhausted},
+ * added to; sqnorm: DEVICE uint64, added to; both may be NULL.  FEDFR_ERR_ARG before anything is launched for bits != 16, frac_bits outside
+ * 8 ... 30, code_limit outside 1 ... 32767, sigma outside [16, 2^26], noise_offset + n_pad > 2^58, what fedfr_secagg_mask_narrow refuses of
+ * the streams, NULL y / x / xi / clip_coef, y / x / xi not 16-byte, clip_coef / counters not 4-byte or sqnorm not 8-byte aligned, and a
+ * counter0 whose last block would pass 2^32 - 1.  n = 0 is a no-op. */
+int fedfr_secagg_mask_narrow_dp(unsigned* y, const float* x, const float* xi, const float* clip_coef, int frac_bits, int code_limit, int bits,
+                                unsigned long long rotation_seed, unsigned long long private_seed, unsigned long long round,
+                                unsigned long long noise_seed, unsigned long long noise_round, unsigned long long noise_offset, double sigma,
+                                const unsigned* keys, const unsigned* nonces, const int* signs, int k, unsigned counter0, size_t n,
+                                int* counters, unsigned long long* sqnorm, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * robust aggregation — no reference counterpart: every rule above is a weighted sum, so one client that returns a poisoned, diverged or NaN
  * state moves (or wipes out) the global model.  Coordinate-wise trimmed mean / median (Yin et al., 2018) and Krum / Multi-Krum (Blanchard
  * et al., 2017) over k <= 32 flat fp32 client states (HOST arrays of k device pointers, as fedfr_fedavg_multi), as streaming passes.
