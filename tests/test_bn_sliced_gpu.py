@@ -5,7 +5,7 @@ fp32 kernel with a factor of four to spare, and tight enough to see one row, one
 instantiation it is for; the geometry it relies on is asserted against the library's own queries, so a retune fails here instead of silently
 leaving a branch untested.  Every output holds NaN before a call.  The worst error / tolerance of every quantity is printed before it is
 asserted (pytest -s) and collected per instantiation (test_zz_margins prints the table).  The storage type is the loaded library's
-(_C.storage_dtype()): the file runs unchanged on the fp16 and the bf16 build."""
+(_C.storage_dtype()): the file runs unchanged on the fp16 and the bf16 build, and tests/test_bf16_build_gpu.py runs it on the latter."""
 import pytest
 import torch
 

@@ -421,3 +421,43 @@ def test_head_cases_are_conditioned_for_fp32():
                 worst[kind] = max(worst.get(kind, 0.0), e)
     print("head cases: %d quantities, worst fp32 error per kind %s" % (n, worst))
     assert n > 2000 and set(worst) == {"fwd", "grad", "loss"}
+
+
+def test_every_storage_typed_gpu_file_runs_on_bf16():
+    """Every tests/test_*_gpu.py that reads the loaded library's storage type stands in exactly one of BF16_FILES (run again on the bf16
+    build, tests/test_bf16_build_gpu.py), COVERED_ELSEWHERE (a bf16 child of its own) or EXCLUDED (with its reason): a new direct test file
+    must decide where it stands, or its bf16 branches never meet a device."""
+    import glob
+    import test_bf16_build_gpu as B
+    here = os.path.dirname(os.path.abspath(__file__))
+    typed = set()
+    for path in glob.glob(os.path.join(here, "test_*_gpu.py")):
+        with open(path) as f:
+            if "storage_dtype" in f.read():
+                typed.add(os.path.basename(path))
+    assert len(typed) >= 14
+    places = [set(B.BF16_FILES), set(B.COVERED_ELSEWHERE), set(B.EXCLUDED)]
+    listed = set().union(*places)
+    assert sum(len(p) for p in places) == len(listed), "a file stands in two places"
+    assert typed - listed == set(), "reads the storage type, is never run on the bf16 build and gives no reason: %s" % sorted(typed - listed)
+    assert listed - typed == set(), "listed, but does not exist or does not read the storage type: %s" % sorted(listed - typed)
+    assert all(isinstance(r, str) and len(r) > 20 for r in list(B.COVERED_ELSEWHERE.values()) + list(B.EXCLUDED.values()))
+    # a row's child finishes well inside its limit; the children of COVERED_ELSEWHERE exist under the names the reasons give
+    assert all(isinstance(k, str) and 120 <= t <= 600 and t % 30 == 0 for k, t in B.BF16_FILES.values())
+    for name, test in (("test_rowslab_fwd_gpu.py", "def test_bf16_build_in_a_child_process("), ("test_e2e_gpu.py", "def test_bf16_build_reference_parity_subset(")):
+        with open(os.path.join(here, name)) as f:
+            assert test in f.read(), (name, test)
+    with open(os.path.join(here, "test_e2e_gpu.py")) as f:
+        assert '"test_block_gpu.py")' in f.read()                  # (the subset's child is given the block file as well)
+
+
+def test_bf16_child_reads_pytest_summaries_and_never_starts_a_grandchild():
+    import bf16_child as bc
+    assert bc.summary_counts("...\n138 passed, 2 deselected, 3 warnings in 34.92s\n") == {"passed": 138, "deselected": 2, "warnings": 3}
+    assert bc.summary_counts("x\n5 passed, 1 skipped in 0.51s (0:00:01)\n") == {"passed": 5, "skipped": 1}
+    assert bc.summary_counts("1 failed, 4 passed, 1 xfailed in 12.00s\ntrailing line\n") == {"failed": 1, "passed": 4, "xfailed": 1}
+    assert bc.summary_counts("no tests ran in 0.01s\n") == {} and bc.summary_counts("") == {}
+    for k in ("", "sgd or shadow"):
+        e = bc.child_k(k)
+        assert "not child_process" in e and "not bf16_build" in e and (not k or "(%s)" % k in e)
+    assert "os.exec" not in open(bc.__file__).read().split('"""', 2)[2]

@@ -5,7 +5,7 @@ of tests/step_cases.py (which tests/test_step_cases_cpu.py proves admissible and
 byte and integer buffers: a fill pattern) with a guard band behind every buffer; afterwards the guard is intact and every value that is
 due is the exact bits, or a number within its tolerance.  Each toleranced figure is printed, as a fraction of its tolerance, before it is
 asserted (pytest -s).  The storage type is the loaded library's (_C.storage_dtype()): the file runs unchanged on the fp16 and the bf16
-build."""
+build, and tests/test_bf16_build_gpu.py runs it on the latter."""
 import numpy as np
 import pytest
 import torch

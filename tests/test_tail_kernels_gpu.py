@@ -4,7 +4,8 @@ small aggregation / PartialFC entry points — against the float64 references an
 tests/test_tail_cases_cpu.py proves admissible and sharp).  Before every call the outputs hold NaN (16-bit and integer buffers: a fill
 pattern) and every ld padding, gap and guard band a sentinel; afterwards the padding is intact and every value that is due is a number
 within its tolerance, or the exact bits.  Each figure is printed, as a fraction of its tolerance, before it is asserted (pytest -s).  The
-storage type is the loaded library's (_C.storage_dtype()): the file runs unchanged on the fp16 and the bf16 build."""
+storage type is the loaded library's (_C.storage_dtype()): the file runs unchanged on the fp16 and the bf16 build, and
+tests/test_bf16_build_gpu.py runs it on the latter."""
 import contextlib
 import ctypes as C
 import os
