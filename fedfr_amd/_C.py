@@ -177,6 +177,9 @@ SIGNATURES = {
     "fedfr_robust_pairdist_workspace_bytes": (sz, [i32, sz]),
     "fedfr_robust_pairdist": (i32, [vp, i32, sz, vp, vp, sz, vp]),
     "fedfr_robust_krum_select": (i32, [vp, i32, i32, i32, vp, vp, vp]),
+    "fedfr_reweight_workspace_bytes": (sz, [i32, sz]),
+    "fedfr_reweight_step": (i32, [vp, vp, vp, vp, i32, sz, vp, sz, vp]),
+    "fedfr_reweight_weights": (i32, [i32, vp, f64, i32, i32, i32, sz, vp, sz, vp, vp, vp, vp]),
     "fedfr_delta_code_bytes": (sz, [i32, sz]),
     "fedfr_delta_scale_bytes": (sz, [sz]),
     "fedfr_delta_quantize": (i32, [vp, vp, vp, vp, vp, i32, sz, vp, vp]),

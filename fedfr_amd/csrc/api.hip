@@ -10,6 +10,7 @@
 #include "net.h"
 #include "optim.h"
 #include "robust.h"
+#include "reweight.h"
 #include "compress.h"
 #include "sparse.h"
 #include "dp.h"
@@ -1011,6 +1012,15 @@ int fedfr_robust_pairdist(const float* const* xs, int k, size_t n, double* dist,
 }
 int fedfr_robust_krum_select(const double* dist, int k, int f, int m, double* score, int* selected, void* stream) {
   return robust_krum_select(dist, k, f, m, score, selected, ST(stream));
+}
+size_t fedfr_reweight_workspace_bytes(int k, size_t n) { return reweight_ws_bytes(k, n); }
+int fedfr_reweight_step(float* dst, const float* z, const float* const* xs, const float* beta, int k, size_t n, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+  return reweight_step(dst, z, xs, beta, k, n, workspace, workspace_bytes, ST(stream));
+}
+int fedfr_reweight_weights(int rule, const double* alpha, double param, int slot, int iters, int k, size_t n, const void* workspace,
+                           size_t workspace_bytes, double* hist_d, float* hist_beta, double* info, void* stream) {
+  return reweight_weights(rule, alpha, param, slot, iters, k, n, workspace, workspace_bytes, hist_d, hist_beta, info, ST(stream));
 }
 size_t fedfr_delta_code_bytes(int bits, size_t n) { return delta_code_bytes(bits, n); }
 size_t fedfr_delta_scale_bytes(size_t n) { return delta_scale_bytes(n); }

@@ -457,6 +457,52 @@ def similarity_column_flags(a: torch.Tensor, b: torch.Tensor, threshold: float) 
     return flags
 
 
+REWEIGHT_RULES = {"GeoMedian": 0, "CenteredClip": 1}       # FEDFR_REWEIGHT_GEOMEDIAN / _CCLIP (include/fedfr_hip.h)
+
+
+def reweight_workspace_bytes(k: int, n: int) -> int:
+    """bytes of the fp64 workspace ``reweight_step`` / ``reweight_weights`` share for k clients of n elements (0: refused arguments)"""
+    return int(_C.lib().fedfr_reweight_workspace_bytes(int(k), int(n)))
+
+
+@torch.no_grad()
+def reweight_step(dst: Optional[torch.Tensor], z: torch.Tensor, xs, beta: Optional[torch.Tensor], workspace: torch.Tensor) -> None:
+    """One step pass of the reweighted rules (csrc/reweight.hip: reweight_step_kernel): ``dst`` = z + Σ_i beta_i (x_i - z) over the
+    clients with beta_i != 0 (``dst`` may be ``z``; None: the distance-only mode, nothing but the workspace is written) and, in the same
+    pass, the per-block partials of |x_i - dst|² into ``workspace`` (fp64, ``reweight_workspace_bytes``).  ``beta``: k fp32 on the device."""
+    z = _C.require_gpu_tensor(z, f32, "z")
+    for i, x in enumerate(xs):
+        if _C.require_gpu_tensor(x, f32, "client state %d" % i).numel() != z.numel():
+            raise RuntimeError("reweight_step: client state %d has %d elements, the centre %d" % (i, x.numel(), z.numel()))
+    if dst is not None and _C.require_gpu_tensor(dst, f32, "dst").numel() != z.numel():
+        raise RuntimeError("reweight_step: dst has %d elements, the centre %d" % (dst.numel(), z.numel()))
+    if dst is not None and (beta is None or _C.require_gpu_tensor(beta, f32, "beta").numel() < len(xs)):
+        raise RuntimeError("reweight_step: a step that writes the centre needs beta, k fp32 weights on the device")
+    workspace = _C.require_gpu_tensor(workspace, torch.float64, "workspace")
+    _C.call("fedfr_reweight_step", _C.ptr(dst), z.data_ptr(), _C.ptr_array(xs), _C.ptr(beta), len(xs), z.numel(), workspace.data_ptr(),
+            workspace.numel() * 8, _C.stream())
+
+
+@torch.no_grad()
+def reweight_weights(rule: str, alpha, param: float, slot: int, iters: int, k: int, n: int, workspace: torch.Tensor, hist_d: torch.Tensor,
+                     hist_beta: torch.Tensor, info: torch.Tensor) -> None:
+    """The weights of the next step from the partials of the last ``reweight_step`` (csrc/reweight.hip: reweight_weights_kernel).  ``rule``
+    "GeoMedian" (``param`` = nu) or "CenteredClip" (``param`` = tau, 0 = auto); ``alpha`` k host floats; the squared distances go to
+    ``hist_d[slot]`` ((iters + 1) x k fp64), the weights to ``hist_beta[slot]`` (iters x k fp32; not for slot == iters), tau / S / the
+    no-finite-client flag / the finite count to ``info`` (4 fp64): all on the device, nothing synchronises."""
+    if rule not in REWEIGHT_RULES:
+        raise ValueError("reweight_weights: rule must be one of %s (got %r)" % (sorted(REWEIGHT_RULES), rule))
+    if len(alpha) != k:
+        raise RuntimeError("reweight_weights: %d prior weights for %d clients" % (len(alpha), k))
+    workspace = _C.require_gpu_tensor(workspace, torch.float64, "workspace")
+    hist_d, info = _C.require_gpu_tensor(hist_d, torch.float64, "hist_d"), _C.require_gpu_tensor(info, torch.float64, "info")
+    hist_beta = _C.require_gpu_tensor(hist_beta, f32, "hist_beta")
+    if hist_d.numel() < (iters + 1) * k or hist_beta.numel() < iters * k or info.numel() < 4:
+        raise RuntimeError("reweight_weights: the history needs (iters + 1) x k doubles, iters x k floats and 4 doubles of info")
+    _C.call("fedfr_reweight_weights", REWEIGHT_RULES[rule], (_C.f64 * k)(*[float(a) for a in alpha]), float(param), int(slot), int(iters), int(k),
+            int(n), workspace.data_ptr(), workspace.numel() * 8, hist_d.data_ptr(), hist_beta.data_ptr(), info.data_ptr(), _C.stream())
+
+
 def cosine_linear(x, w, normalize_feat=True):
     return CosineLinearFn.apply(x, w, normalize_feat)
 

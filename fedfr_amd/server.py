@@ -3,7 +3,7 @@ averaging of client models, as HIP kernels over flat buffers (single process) or
 xGMI when every client is its own rank (one client = one MI355X); the spread-out step on the clients' class centres
 (reference server.py:48-63, :340-371) on one fused HIP kernel; and the round's 1:1 verification of the global model with its
 checkpoints (reference server.py:135-148).  Build extensions beyond the reference's FedAvg, one module-level round function each: the
-server optimisers (``FedOpt``), the robust rules (``FedRobust``), client-level differential privacy (``FedDP``; privacy.py), and the
+server optimisers (``FedOpt``), the robust rules (``FedRobust``, ``FedReweighted``), client-level differential privacy (``FedDP``; privacy.py), and the
 rounds from UPLOADS instead of states: 8 / 4-bit and top-k deltas with error feedback (``FedCompressed``, ``FedSparse``; compress.py),
 optionally clipped by their norm as the server applies them and noised by the Gaussian mechanism (``UploadClip``),
 pairwise-masked fixed-point updates (``FedSecAgg``; secagg.py) and those with the clients' own clip and discrete Gaussian noise
@@ -438,6 +438,115 @@ def FedRobust(models: List[dict], weights: Sequence[float], agg: RobustAggregato
     return FlatStateDict.from_flat((P, *_average_stats(models, ws, agg.trimmed_mean)), models[0].table, models[0].layers)
 
 
+# ---- reweighted aggregation: csrc/reweight.hip reweight_step_kernel / reweight_weights_kernel
+REWEIGHT_ALG_KINDS = {"GeoMedian", "CenteredClip"}
+
+
+class ReweightedAggregator:
+    """One reweighted rule over the clients' flat states.  ``kind``: "GeoMedian" (the geometric median by RFA, the smoothed Weiszfeld
+    iteration: weights alpha_i / max(``nu``, d_i), normalised) or "CenteredClip" (weights alpha_i min(1, ``tau`` / d_i); ``tau`` None or
+    "auto": the lower median of the clients' finite update norms of the round), d_i the distance of client i to the current centre;
+    ``iters`` weighted steps from the global parameters.  After a round ``last_dist`` ((iters + 1) x k: the distances before the first step
+    -- the clients' update norms -- and after every step), ``last_weights`` (iters x k: the weights of every step) and ``last_tau`` (None
+    for "GeoMedian") hold what the one blocking copy of the round brought back, for logging.  The workspace and the history buffer are
+    kept across rounds.  At most 32 clients."""
+
+    def __init__(self, kind, iters=3, nu=1e-6, tau=None):
+        if kind not in REWEIGHT_ALG_KINDS:
+            raise ValueError("ReweightedAggregator: kind must be one of %s (got %r)" % (sorted(REWEIGHT_ALG_KINDS), kind))
+        self.kind = kind
+        if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or not 1 <= iters <= 64:
+            raise ValueError("ReweightedAggregator: iters must be an integer in 1 ... 64 (got %r)" % (iters,))
+        self.iters = int(iters)
+        self.nu = float(nu)
+        if not (self.nu > 0 and np.isfinite(self.nu)):
+            raise ValueError("ReweightedAggregator: nu must be a positive finite number (got %r)" % (nu,))
+        if tau is None or (isinstance(tau, str) and tau == "auto"):
+            self.tau = None
+        else:
+            if isinstance(tau, (str, bool)) or not (float(tau) > 0 and np.isfinite(float(tau))):
+                raise ValueError("ReweightedAggregator: tau must be a positive finite number, None or 'auto' (got %r)" % (tau,))
+            self.tau = float(tau)
+        self.last_dist = self.last_weights = self.last_tau = None
+        self._ws = _Workspace()
+        self._hist = None
+
+    def validate(self, k: int):
+        """ValueError for a client count this rule cannot serve"""
+        if k < 1:
+            raise ValueError("ReweightedAggregator(%s): no client states" % self.kind)
+        if k > ROBUST_MAX_CLIENTS:
+            raise ValueError("ReweightedAggregator(%s): %d clients, at most %d in one aggregation" % (self.kind, k, ROBUST_MAX_CLIENTS))
+
+    def aggregate(self, z0: torch.Tensor, xs: Sequence[torch.Tensor], alpha: Sequence[float]) -> torch.Tensor:
+        """The new centre (a new tensor) after ``iters`` weighted steps from ``z0`` over the states ``xs`` with prior weights ``alpha``:
+        iters + 1 passes of fedfr_reweight_step (the first distance-only, the second out of place from ``z0``, the rest in place) with
+        fedfr_reweight_weights behind each, back to back on one stream; then ONE blocking copy of the history ((iters + 1) k distances,
+        iters k weights, tau, the no-finite-client flag): the one synchronisation of the round.  RuntimeError if no client was finite or
+        the final distance of a weighted client is not."""
+        from . import ops
+        k, R = len(xs), self.iters
+        self.validate(k)
+        _check_states(z0, xs, "FedReweighted")
+        if len(alpha) != k:
+            raise RuntimeError("fedfr_amd.FedReweighted: %d prior weights for %d client states" % (len(alpha), k))
+        n, dev = z0.numel(), z0.device
+        self._ws.ensure(ops.reweight_workspace_bytes(k, n), dev)
+        nd, nb = (R + 1) * k + 4, (R * k + 1) // 2                 # [D history | info | beta history (fp32, two per double)]
+        if self._hist is None or self._hist.numel() != nd + nb or self._hist.device != dev:
+            self._hist = torch.zeros(nd + nb, dtype=torch.float64, device=dev)
+        hist_d, info, hist_b = self._hist[:(R + 1) * k], self._hist[(R + 1) * k:nd], self._hist[nd:].view(f32)
+        param = self.nu if self.kind == "GeoMedian" else (self.tau or 0.0)
+        P = torch.empty_like(z0)
+        for slot in range(R + 1):
+            if slot == 0:
+                ops.reweight_step(None, z0, xs, None, self._ws.buf)
+            else:
+                ops.reweight_step(P, z0 if slot == 1 else P, xs, hist_b[(slot - 1) * k:slot * k], self._ws.buf)
+            ops.reweight_weights(self.kind, alpha, param, slot, R, k, n, self._ws.buf, hist_d, hist_b, info)
+        host = self._hist.cpu().numpy()                            # the synchronisation: one blocking copy
+        with np.errstate(invalid="ignore"):
+            self.last_dist = np.sqrt(host[:(R + 1) * k].reshape(R + 1, k))
+        self.last_weights = host[nd:].view(np.float32)[:R * k].reshape(R, k).copy()
+        self.last_tau = float(host[(R + 1) * k]) if self.kind == "CenteredClip" else None
+        if host[(R + 1) * k + 2] != 0.0:
+            raise RuntimeError("fedfr_amd.FedReweighted(%s): no client sent a finite state (distances %s)" % (self.kind, self.last_dist[0].tolist()))
+        used = self.last_weights[R - 1] != 0
+        if not np.all(np.isfinite(self.last_dist[R][used])):
+            raise RuntimeError("fedfr_amd.FedReweighted(%s): the final distance of a weighted client is not finite (distances %s, weights %s)"
+                               % (self.kind, self.last_dist[R].tolist(), self.last_weights[R - 1].tolist()))
+        return P
+
+    def stats_weights(self) -> List[float]:
+        """the convex weights the BN running statistics are combined with after a round: the final weights, and for "CenteredClip" one
+        more, 1 - sum(beta) >= 0, for the global state's statistics"""
+        ws = [float(b) for b in self.last_weights[-1]]
+        if self.kind == "CenteredClip":
+            ws.append(max(0.0, 1.0 - sum(ws)))
+        return ws
+
+
+def FedReweighted(global_state, models: List[dict], weights: Sequence[float], agg: ReweightedAggregator):
+    """One reweighted aggregation of GPU ``FlatStateDict``s (GeoMedian / CenteredClip): ``agg.iters`` weighted steps over the PARAMETER
+    buffer from ``global_state``'s parameters with UNWEIGHTED priors alpha_i = 1 / k (the data sizes are client-reported: see
+    ``FedRobust``).  The BN running statistics are a convex combination, ``_average_stats`` at the final weights (for CenteredClip with
+    1 - sum(beta) on the global state's; a client whose final weight is 0 is left out, as the step pass skips it), so a ``running_var``
+    stays >= 0; the ``num_batches_tracked`` counters take ``FedPavg``'s path
+    (data-size weights, float).  One host synchronisation, in ``ReweightedAggregator.aggregate``."""
+    ws = _client_weights("FedReweighted", models, weights, also=[global_state])
+    k = len(models)
+    agg.validate(k)
+    P = agg.aggregate(global_state.flat[0], [m.flat[0] for m in models], [1.0 / k] * k)
+    sw = agg.stats_weights()
+    extra = [global_state.flat[1]] if agg.kind == "CenteredClip" else []
+
+    def stats_rule(Bf, stats):      # what _average_stats does with the clients whose final weight is not zero (a skipped client's NaN must not reach 0 * NaN)
+        kept = [(t, w) for t, w in zip(list(stats) + extra, sw) if w != 0]
+        for c0 in range(0, len(kept), 8):
+            _multi(Bf, [t for t, _ in kept[c0:c0 + 8]], [w for _, w in kept[c0:c0 + 8]], c0 > 0)
+    return FlatStateDict.from_flat((P, *_average_stats(models, ws, stats_rule)), models[0].table, models[0].layers)
+
+
 # ---- compressed uploads: csrc/compress.hip delta_quantize_kernel (client side, compress.py) / delta_aggregate_kernel
 class _StatsOnly:
     """what ``_average_stats`` reads of a client state, for an upload that carries no fp32 parameters"""
@@ -459,7 +568,7 @@ def _upload_round_head(what, global_state, uploads, is_upload, noun, expected, w
         raise RuntimeError("fedfr_amd.%s: the client %s must be %s" % (what, noun, expected))
     if weights is not None and len(weights) != len(uploads):
         raise RuntimeError("fedfr_amd.%s: %d weights for %d client %s" % (what, len(weights), len(uploads), noun))
-    if isinstance(server_opt, RobustAggregator):
+    if isinstance(server_opt, (RobustAggregator, ReweightedAggregator)):
         raise ValueError("%s: a robust rule (%s) needs whole client states, %s" % (what, server_opt.kind, robust_why))
     if server_opt is not None and server_opt.clip_norm > 0 and clip is None:
         raise ValueError("%s: %s" % (what, clip_refusal))
@@ -812,9 +921,10 @@ def fedavg_all_reduce(backbone, data_size: float, total_size: float, comm=None, 
     if dp is not None:
         raise ValueError("fedavg_all_reduce: differential privacy is not supported on the all-reduce path (it needs every rank's own delta "
                          "clipped before the exchange, a different algorithm); use FedDP")
-    if isinstance(server_opt, RobustAggregator):
+    if isinstance(server_opt, (RobustAggregator, ReweightedAggregator)):
         raise ValueError("fedavg_all_reduce: a robust rule (%s) is not a sum and cannot ride a sum-all-reduce (every rank would need every "
-                         "state: an all-gather, not provided here); use FedRobust" % server_opt.kind)
+                         "state: an all-gather, not provided here); use %s"
+                         % (server_opt.kind, "FedRobust" if isinstance(server_opt, RobustAggregator) else "FedReweighted"))
     if server_opt is not None:
         if server_opt.clip_norm > 0:
             raise ValueError("fedavg_all_reduce: clip_norm > 0 is not supported on the all-reduce path (clipping a rank's own delta before "
@@ -907,6 +1017,7 @@ class Server(object):
         self.local_candidates = []
         self.server_opt = None                       # ServerOptimizer of aggr_alg FedAvgM / FedAdagrad / FedAdam / FedYogi (built in train())
         self.robust_agg = None                       # RobustAggregator of aggr_alg TrimmedMean / CoordMedian / Krum / MultiKrum (built in train())
+        self.reweight_agg = None                     # ReweightedAggregator of aggr_alg GeoMedian / CenteredClip (built in train())
         self.dp_mech = self.dp_accountant = None     # privacy.GaussianMechanism / RDPAccountant of dp_noise_multiplier > 0 (built in train())
         self.dp_epsilon = None                       # the (epsilon, dp_delta) guarantee after the rounds aggregated so far
         self.upload_clip = None                      # the UploadClip of clip_uploads (built in train()) and what the last round read of it
@@ -1009,9 +1120,10 @@ class Server(object):
                 raise ValueError("Server.train: ddp_wrap_sigmas=%r needs secagg_bits=16: at 32-bit words the clamp keeps every sum inside the "
                                  "word and nothing wraps" % (ddp_wrap,))
         secagg_drop = []
-        if aggr_alg not in ("FedAvg", "FedProx", "SCAFFOLD") and aggr_alg not in AGGR_ALG_KINDS and aggr_alg not in ROBUST_ALG_KINDS:      # before a round of client training is spent on it
-            raise ValueError("Server.train: unknown aggr_alg %r (FedAvg, FedProx, SCAFFOLD, %s, %s)"
-                             % (aggr_alg, ", ".join(AGGR_ALG_KINDS), ", ".join(sorted(ROBUST_ALG_KINDS))))
+        robust_like = aggr_alg in ROBUST_ALG_KINDS or aggr_alg in REWEIGHT_ALG_KINDS      # the rules that need whole client states in the clear
+        if aggr_alg not in ("FedAvg", "FedProx", "SCAFFOLD") and aggr_alg not in AGGR_ALG_KINDS and not robust_like:      # before a round of client training is spent on it
+            raise ValueError("Server.train: unknown aggr_alg %r (FedAvg, FedProx, SCAFFOLD, %s, %s, %s)"
+                             % (aggr_alg, ", ".join(AGGR_ALG_KINDS), ", ".join(sorted(ROBUST_ALG_KINDS)), ", ".join(sorted(REWEIGHT_ALG_KINDS))))
         from .client import check_prox_mu
         prox_mu = check_prox_mu(getattr(a, "prox_mu", 0), "Server.train")   # FedProx's proximal coefficient (client-side): absent or 0 = off, whatever aggr_alg is
         scaffold = aggr_alg == "SCAFFOLD"
@@ -1055,7 +1167,7 @@ class Server(object):
             if not clip_norm > 0:
                 raise ValueError("Server.train: dp_noise_multiplier=%r needs clip_norm > 0: the clip is the sensitivity bound of the mechanism"
                                  % (dp_sigma,))
-            if aggr_alg in ROBUST_ALG_KINDS:
+            if robust_like:
                 raise ValueError("Server.train: dp_noise_multiplier=%r cannot be combined with aggr_alg=%r: a robust rule provides no per-client "
                                  "norms to clip" % (dp_sigma, aggr_alg))
             if compress_bits and not clip_uploads:
@@ -1078,10 +1190,17 @@ class Server(object):
                 self.robust_agg = RobustAggregator(aggr_alg, trim_ratio=getattr(a, "trim_ratio", 0.1), num_byzantine=getattr(a, "num_byzantine", 1),
                                                    multi_m=getattr(a, "multi_krum_m", None))
             self.robust_agg.validate(len(self.current_client_list))
+        if aggr_alg in REWEIGHT_ALG_KINDS:                 # the same for the reweighted rules (the aggregator keeps workspace and history)
+            want = dict(iters=getattr(a, "rfa_iters" if aggr_alg == "GeoMedian" else "cclip_iters", 3), nu=getattr(a, "rfa_nu", 1e-6),
+                        tau=getattr(a, "cclip_tau", None))
+            if getattr(self, "reweight_agg", None) is None or self.reweight_agg.kind != aggr_alg or self._reweight_settings != want:
+                self.reweight_agg = ReweightedAggregator(aggr_alg, **want)      # one aggregator per server and setting
+                self._reweight_settings = want
+            self.reweight_agg.validate(len(self.current_client_list))
         if compress_bits:                                                    # what cannot be served: also before anybody trains
             from .compress import check_bits
             check_bits(compress_bits, "Server.train")
-            if aggr_alg in ROBUST_ALG_KINDS:
+            if robust_like:
                 raise ValueError("Server.train: compress_bits=%d cannot be combined with aggr_alg=%r: a robust rule needs whole client states"
                                  % (compress_bits, aggr_alg))
             if clip_norm > 0 and not clip_uploads:
@@ -1096,7 +1215,7 @@ class Server(object):
             if compress_bits:
                 raise ValueError("Server.train: topk_ratio=%r cannot be combined with compress_bits=%d: quantising the kept values is not provided"
                                  % (topk_ratio, compress_bits))
-            if aggr_alg in ROBUST_ALG_KINDS:
+            if robust_like:
                 raise ValueError("Server.train: topk_ratio=%r cannot be combined with aggr_alg=%r: a robust rule needs whole client states"
                                  % (topk_ratio, aggr_alg))
             if clip_norm > 0 and not clip_uploads:
@@ -1105,7 +1224,7 @@ class Server(object):
         if secagg_on:                                                        # the same: before anybody trains
             from .secagg import MAX_PARTICIPANTS, check_frac_bits
             K = len(self.current_client_list)
-            if aggr_alg in ROBUST_ALG_KINDS:
+            if robust_like:
                 raise ValueError("Server.train: secure_aggregation cannot be combined with aggr_alg=%r: a robust rule needs whole client states, "
                                  "which masked uploads hide" % (aggr_alg,))
             if compress_bits:
@@ -1348,6 +1467,15 @@ class Server(object):
             self._scaffold_update_c([self.clients[i].get_control_update() for i in order])
         elif aggr_alg in AGGR_ALG_KINDS:
             aggr_state_dict = FedOpt(flat_state_dict(self.federated_model), models, data_sizes, opt)
+        elif aggr_alg in REWEIGHT_ALG_KINDS:
+            # geometric median / centred clipping (a build extension): iters + 1 fused passes from the global parameters, one host synchronisation
+            agg = self.reweight_agg
+            aggr_state_dict = FedReweighted(flat_state_dict(self.federated_model), models, data_sizes, agg)
+            if agg.last_tau is not None:
+                self.logger.info('%s: tau %.9g (%s), %d steps' % (aggr_alg, agg.last_tau, "auto" if agg.tau is None else "given", agg.iters))
+            for pos, i in enumerate(order):
+                self.logger.info('Client %s: update norm %.9g, final distance %.9g, final weight %.9g'
+                                 % (getattr(self.clients[i], "cid", i), agg.last_dist[0][pos], agg.last_dist[-1][pos], agg.last_weights[-1][pos]))
         else:
             # ROBUST_ALG_KINDS (nothing else passed the check above).  Robust aggregation (a build extension): trimmed mean / median per
             # coordinate, or Krum's selection (one host synchronisation)

@@ -923,6 +923,54 @@ int fedfr_robust_pairdist(const float* const* xs, int k, size_t n, double* dist,
 int fedfr_robust_krum_select(const double* dist, int k, int f, int m, double* score, int* selected, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * reweighted aggregation — the two vector-wise robust rules that use every honest client: the geometric median (RFA, the smoothed
+ * Weiszfeld iteration of Pillutla, Kakade and Harchaoui, 2019) and centred clipping (Karimireddy, He and Jaggi, 2021).  Both are "weights
+ * from the distances to the current centre, one weighted step, repeat", so both run on ONE streaming pass and one single-block kernel:
+ * R iterations are R + 1 passes and R + 1 small launches, back to back on one stream, no host round trip in between.
+ * Notation: x_0 .. x_{k-1} the clients' flat fp32 states [n], k <= 32 (HOST array of k device pointers, as fedfr_fedavg_multi); z the centre
+ * [n]; beta a DEVICE array of k fp32 weights.
+ *
+ * STEP PASS (fedfr_reweight_step), for every element; every operation is one correctly rounded fp32 operation, nothing is contracted:
+ *   delta_i = x_i - z
+ *   acc = z;  for i = 0 .. k-1 ascending:  if beta[i] != 0:  acc = acc + beta[i] * delta_i        (one multiply, one add)
+ *   z' = acc                              a client with beta[i] == 0 is SKIPPED (a select, not a product with zero: its NaN or inf never reaches z')
+ *   e_i = x_i - z'                        for every client, the skipped ones included
+ *   D_i = D_i + (double) e_i * (double) e_i     in fp64 (the product is exact: one rounding per term)
+ * dst == NULL is the distance-only mode: beta is not read, nothing but the workspace is written, z' = z and D_i = |x_i - z|^2.  dst may be z
+ * (in place: a thread reads an element before it writes it); otherwise dst overlaps neither z nor a client state.  The D_i are NOT finished
+ * by this call: every block writes one fp64 partial per client into `workspace` ([k][grid], need not be initialised; lanes by a fixed
+ * shuffle tree, waves in ascending order); fedfr_reweight_weights adds the blocks in ascending order.  No atomics: two runs give the same bits.
+ *
+ * WEIGHTS (fedfr_reweight_weights), one block, fp64, each beta rounded to fp32 once.  D_i = the sum of client i's partials, d_i = sqrt(D_i);
+ * a client whose D_i is not finite gets beta_i = 0; alpha_i >= 0 are the prior weights (HOST array of k doubles):
+ *   rule 0, geometric median:  w_i = alpha_i / max(nu, d_i) (0 for a non-finite client);  S = w_0 + ... + w_{k-1} ascending;
+ *                              beta_i = (float) (w_i / S)   (S == 0: every beta_i = 0).                  param = nu > 0
+ *   rule 1, centred clipping:  beta_i = (float) (alpha_i * min(1, tau / d_i)), d_i == 0 gives alpha_i;  S = (double) beta_0 + ... ascending.
+ *                              param = tau > 0, or 0 for AUTO: tau = the lower median of the finite d_i of slot 0 (the distance-only pass:
+ *                              of m finite values sorted ascending, number (m - 1) / 2), computed at slot 0 and read back from info at
+ *                              every later slot of the round.
+ * `slot` 0 .. iters numbers the passes of a round.  The call writes D into hist_d[slot][0 .. k) (DEVICE, (iters + 1) x k doubles), and,
+ * for slot < iters, beta into hist_beta[slot][0 .. k) (DEVICE, iters x k floats: the weights of step slot + 1).  info (DEVICE, 4 doubles):
+ * [0] the tau in use (rule 1), [1] S of this slot, [2] 1.0 once a slot of the round had no finite client (slot 0 resets it to 0.0), [3] the
+ * number of finite clients of this slot.
+ * ------------------------------------------------------------------------------------------------ */
+#define FEDFR_REWEIGHT_GEOMEDIAN 0
+#define FEDFR_REWEIGHT_CCLIP 1
+/* bytes of the workspace of fedfr_reweight_step / _weights: k x grid doubles, grid as for fedfr_fedopt_sqnorm_workspace_bytes
+ * (multi_state_grid); 0 for k outside 1..32 or n = 0 */
+size_t fedfr_reweight_workspace_bytes(int k, size_t n);
+/* One step pass (above).  dst NULL (distance-only; beta may be NULL) or [n]; z [n]; xs HOST array of k device pointers; beta DEVICE [k].
+ * 1 <= k <= 32, n > 0; dst, z, xs[i] 16-byte aligned, beta 4-byte, workspace 8-byte aligned; FEDFR_ERR_WORKSPACE if workspace_bytes <
+ * fedfr_reweight_workspace_bytes(k, n).  Every state is read once (non-temporal loads); n % V trailing elements take a scalar path. */
+int fedfr_reweight_step(float* dst, const float* z, const float* const* xs, const float* beta, int k, size_t n, void* workspace,
+                        size_t workspace_bytes, void* stream);
+/* The weights of the next step from the partials fedfr_reweight_step left in `workspace` for the same (k, n) (above).  rule 0 / 1; alpha HOST
+ * array of k finite doubles >= 0; param: nu > 0 (rule 0), tau > 0 or 0 = auto (rule 1); 0 <= slot <= iters, iters >= 1.  hist_d, info,
+ * workspace 8-byte aligned, hist_beta 4-byte aligned. */
+int fedfr_reweight_weights(int rule, const double* alpha, double param, int slot, int iters, int k, size_t n, const void* workspace,
+                           size_t workspace_bytes, double* hist_d, float* hist_beta, double* info, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * compressed client uploads with error feedback — no reference counterpart (its clients hand over full fp32 states).  A client sends
  * Q(x_i - x + e_i) and keeps the quantisation error e_i for the next round.  Codes of bits = 8 or 4 with ONE shared power-of-two scale
  * per 32 elements (the OCP microscaling layout): 8.25 or 4.25 bits per parameter instead of 32.  Every scale is a power of two, so
